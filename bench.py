@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """bench.py — lip-clips/s, forward+backward, of the SBL hot path on synthetic 29x88x88 clips (BASELINE.json).
 
-    python bench.py --gpus 1 --steps K --warmup W                       # one GPU
+    python bench.py --gpus 1 --steps K --warmup W                       # one GPU: the headline only
+    python bench.py --gpus 1 --steps K --warmup W --full                # + per-pattern times, roofline, f32_exact, CPU baseline
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                          # one rank per GPU, RCCL over xGMI
 
@@ -22,7 +24,10 @@ The coin patterns are a stratified sample of Binomial(16, 1/2) (draw_coin_patter
 the expectation; round 2 used four raw draws with mean 7.25, i.e. ~0.45 ms less decoder work per step), the timed loop
 visits each pattern equally often (24 steps over 8 patterns), and `config.per_pattern` reports every pattern's own time.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; with
+--dump-outputs DIR it also writes what the last timed step computed (dump_outputs below).  The secondary measurements
+run only with --full, after the timed steps, and add to the line:
+  config.per_pattern — every coin pattern's own step time and the linear fit over the own-arg-max coin count
   f32_exact    — the same step re-captured and replayed under the exact fp32 MFMA (--precision f32 arithmetic), same run, same
                  patterns: the like-for-like number next to the split-bf16 headline (N = 1 only)
   roofline     — the dominant kernel family of the step by GPU time.  Every GEMM / convolution launch of the step
@@ -128,7 +133,16 @@ def parse():
     ap.add_argument("--dump-launches", default="", help="debug: write a per-shape table of the instrumented launches to this file")
     ap.add_argument("--hang-dump", type=int, default=0, help="debug: dump all Python stacks after this many seconds")
     ap.add_argument("--verbose", action="store_true", help="progress lines on stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary measurements: per-pattern step times, roofline (instrumented "
+                         "replays), the exact-fp32 step and the CPU baseline (each can still be turned off with its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches reports the instrumented replays of --full")
     if args.precision is None:
         args.precision = "bf16" if args.workload == "config5" else "bf16x6"
     if args.batch <= 0:
@@ -270,6 +284,26 @@ class LaunchRecorder:
         ops.call = call
 
 
+GRAD_SAMPLE_DRAWS = 1 << 22      # <= 16 MB of float32 gradient values
+
+
+def dump_outputs(path, loss, step_outs, flat):
+    """What a caller of the timed step receives after the last timed step, one DIR/<name>.npy each: the loss (float64),
+    the step's outputs (logits and targets of both decoder directions, or the frontend features; float32) and the
+    parameter gradient.  The flat gradient (81 M parameters, 309 MB for the full model) is written as a fixed seeded
+    sample, `grad_sample` (the sorted, distinct positions of 4 M draws from Generator(PCG64(0)), which depend only on the
+    model's size), plus `grad_norm`, the float64 L2 norm of every parameter's gradient in flat-buffer order."""
+    os.makedirs(path, exist_ok=True)
+    g = flat.flat_grad
+    idx = np.unique(np.random.default_rng(0).integers(0, g.numel(), GRAD_SAMPLE_DRAWS))
+    arrays = {"loss": loss.double()}
+    arrays.update({k: v.float() for k, v in step_outs.items()})
+    arrays["grad_sample"] = g[torch.from_numpy(idx).to(g.device)]
+    arrays["grad_norm"] = torch.stack([g[off:off + p.numel()].double().norm() for p, off, _ in flat.slots])
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def cpu_baseline(batch, T, hw):
     """CPU oracle fwd + loss + bwd on `batch` clips of the same synthetic workload and mode as the GPU step (train-mode
     BatchNorm, dropout ON: 0.1 in the transformer and the always-on 0.5 mask on the frontend features), SURVEY 8d: one
@@ -354,7 +388,8 @@ def main():
     ops.PACK_CACHE = not args.no_pack_cache
     for kv in args.tuning:
         ops.call("sbl_set_tuning", *[int(v) for v in kv.split("=")])
-    rec = LaunchRecorder()
+    kernel_timing = args.full and not args.no_kernel_timing
+    rec = LaunchRecorder() if kernel_timing else None
 
     B = args.batch
     model = build_model(dev, not args.no_dropout)
@@ -378,6 +413,9 @@ def main():
     model.decoder.batch_teacher_runs = not args.per_step_decoder
     drop = ops.dropout_state(dev)
     loss_out = torch.zeros((), device=dev)
+    # what the step hands its caller besides the loss and the gradient (--dump-outputs); inside a capture these are the
+    # graph's own buffers, which every replay rewrites, so capture() keeps them with the graph
+    outs = {}
 
     def fwd_bwd():
         drop.begin_step()
@@ -385,9 +423,11 @@ def main():
         if args.workload == "frontend":      # BASELINE config 2
             feats = model.visual_frontend(x.unsqueeze(1))
             loss = feats.square().mean()
+            outs["features"] = feats.detach()
         else:
             pl, gl, pr, gr = model(x, l2r, r2l)
             loss = 0.5 * (cal_performance_device(pl, gl, 0.1)[0] + cal_performance_device(pr, gr, 0.1)[0])
+            outs.update(pred_l2r=pl.detach(), gold_l2r=gl, pred_r2l=pr.detach(), gold_r2l=gr)
         loss.backward()
         ops.join_side_streams()          # the decoder's second stream rejoins before the step ends
         loss_out.copy_(loss.detach())
@@ -407,6 +447,7 @@ def main():
         enc, *_ = model.encoder(feats_d, lengths)
         pl, gl, pr, gr = model.decoder(l2r, r2l, enc, lengths)
         loss = 0.5 * (cal_performance_device(pl, gl, 0.1)[0] + cal_performance_device(pr, gr, 0.1)[0])
+        outs.update(pred_l2r=pl.detach(), gold_l2r=gl, pred_r2l=pr.detach(), gold_r2l=gr)
         loss.backward()
         ops.join_side_streams()
         loss_out.copy_(loss.detach())
@@ -444,6 +485,7 @@ def main():
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=pool, stream=cap_stream, capture_error_mode=cap_mode):
             fn()
+        g.outs = dict(outs)
         return g
 
     if not args.no_graph and args.mode != "eager":
@@ -581,10 +623,18 @@ def main():
     dt = float(tt.item())
     loss_val = float(loss_out.item())
     log(args, "timed region done: %.2f ms/step" % (dt / args.steps * 1e3))
+    if rank == 0 and args.dump_outputs:
+        if mode == "graph":
+            last = graphs[(step_no[0] - 1) % len(graphs)]
+            step_outs = (last[0] if use_split else last).outs
+        else:
+            step_outs = outs
+        dump_outputs(args.dump_outputs, loss_out, step_outs, flat)
+        log(args, "outputs written to %s" % args.dump_outputs)
 
     # ---- per-kernel GPU time inside replays of the same step (in-kernel stamps, see docstring)
     fam = {}
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and kernel_timing:
         CAP = 32768
         init = torch.zeros(CAP, 2, dtype=torch.int64, device=dev)
         init[:, 0] = -1                                   # as uint64: +inf for atomicMin
@@ -642,7 +692,7 @@ def main():
     # ---- step time per coin pattern (outside the timed region): the step is linear in the number of own-arg-max coins (one
     # more sequential decoder stage each), so the fit also says what the round-2 pattern set (mean 7.25 coins) would read
     per_pattern = None
-    if rank == 0 and world == 1 and graph is not None and not use_split and len(graphs) > 1:
+    if args.full and rank == 0 and world == 1 and graph is not None and not use_split and len(graphs) > 1:
         per_pattern_ms = []
         for g_ in graphs:
             g_.replay()
@@ -664,7 +714,7 @@ def main():
     # into a hipGraph at capture, so the step is re-captured under "f32" for every coin pattern and replayed once per
     # pattern after a warm-up replay (rank 0 / N = 1 only; the headline `value` above is untouched by it)
     f32_exact = None
-    if rank == 0 and world == 1 and graph is not None and args.precision == "bf16x6" and args.workload == "full" and not args.no_f32_exact:
+    if args.full and rank == 0 and world == 1 and graph is not None and args.precision == "bf16x6" and args.workload == "full" and not args.no_f32_exact:
         try:
             ops.set_matmul_precision("f32")
             fgraphs = []
@@ -743,7 +793,7 @@ def main():
                                "families": [{k: v for k, v in f.items() if k not in ("kid", "bytes")} for f in fams if f is not top]}
         else:
             out["roofline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.T, args.HW)
         print(json.dumps(out), flush=True)
     if world > 1:
