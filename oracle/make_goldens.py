@@ -180,6 +180,34 @@ def state_dict_keys():
     print("state_dict_keys", len(keys))
 
 
+def _init_record(prefix, sd):
+    """Per state-dict entry, in order: float64 sum, float64 sum of |x| and the first 16 flattened values (NaN-padded)."""
+    head = np.full((len(sd), 16), np.nan)
+    for i, v in enumerate(sd.values()):
+        flat = v.detach().reshape(-1)[:16].double().numpy()
+        head[i, :flat.size] = flat
+    return {prefix + "keys": np.array(list(sd.keys())),
+            prefix + "sum": np.array([float(v.double().sum()) for v in sd.values()]),
+            prefix + "abs_sum": np.array([float(v.double().abs().sum()) for v in sd.values()]),
+            prefix + "head": head}
+
+
+def init_seeded():
+    """The reference's seeded initialisation, no forward: Transformer (2 encoder + 2x2 decoder layers) built after
+    torch.manual_seed(0) and a bare Lipreading() after torch.manual_seed(1), both on the CPU."""
+    from transformer.decoder import Decoder
+    from transformer.encoder import Encoder
+    from transformer.transformer import Transformer
+    from transformer.video_frontend import Lipreading
+    torch.manual_seed(0)
+    m = Transformer(Encoder(512, 2, 8, 64, 64, 512, 2048), Decoder(0, 1, 58, 512, 2, 8, 64, 64, 512, 2048), None)
+    out = _init_record("transformer.", m.state_dict())
+    torch.manual_seed(1)
+    out.update(_init_record("lipreading.", Lipreading().state_dict()))
+    np.savez_compressed(os.path.join(OUT, "init_seeded.npz"), **out)
+    print("init_seeded", len(out["transformer.keys"]), len(out["lipreading.keys"]))
+
+
 def modules():
     """Module-level fixtures with their own tiny deterministic weights."""
     import transformer.attention as A
@@ -362,3 +390,5 @@ if __name__ == "__main__":
         eval_recognize("varied", 3, 29, 88, 88, 6, 6, salt=34, gains="varied", train_bn=True)
     if args.only in ("", "keys"):
         state_dict_keys()
+    if args.only in ("", "init"):
+        init_seeded()

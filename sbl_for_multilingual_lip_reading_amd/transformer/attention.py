@@ -1,5 +1,7 @@
-"""Mirror of SBL_Multilingual_Lip_reading/transformer/attention.py (same class names, constructor and
-forward signatures, state-dict keys); compute is libsbl_hip.so."""
+"""MultiHeadAttention and ScaledDotProductAttention with the class names, constructor and forward signatures and
+state-dict keys of the reference's transformer/attention.py; compute is libsbl_hip.so."""
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -32,15 +34,15 @@ class MultiHeadAttention(nn.Module):
         self.w_qs = nn.Linear(d_model, n_head * d_k)
         self.w_ks = nn.Linear(d_model, n_head * d_k)
         self.w_vs = nn.Linear(d_model, n_head * d_v)
-        nn.init.normal_(self.w_qs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_k)))
-        nn.init.normal_(self.w_ks.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_k)))
-        nn.init.normal_(self.w_vs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_v)))
+        for proj, d_head in ((self.w_qs, d_k), (self.w_ks, d_k), (self.w_vs, d_v)):     # N(0, 2 / (d_model + d_head))
+            nn.init.normal_(proj.weight, std=math.sqrt(2.0 / (d_model + d_head)))
 
         self.attention = ScaledDotProductAttention(temperature=np.power(d_k, 0.5), attn_dropout=dropout)
         self.layer_norm = nn.LayerNorm(d_model)
 
         self.fc = nn.Linear(n_head * d_v, d_model)
-        nn.init.xavier_normal_(self.fc.weight)
+        # Xavier-normal: N(0, 2 / (fan_in + fan_out))
+        nn.init.normal_(self.fc.weight, std=math.sqrt(2.0 / (n_head * d_v + d_model)))
 
         self.dropout = nn.Dropout(dropout)
 

@@ -1,4 +1,5 @@
-"""Mirror of SBL_Multilingual_Lip_reading/transformer/decoder.py (the SBL bidirectional decoder)."""
+"""Decoder (the SBL bidirectional decoder) and DecoderLayer with the constructor / forward signatures and state-dict
+keys of the reference's transformer/decoder.py."""
 import random
 
 import torch
@@ -7,14 +8,14 @@ import torch.nn as nn
 from ._env import config, ops
 from . import decoder_stages
 from .attention import MultiHeadAttention
-from .module import PositionalEncoding, PositionwiseFeedForward
-from .utils import get_attn_key_pad_mask, get_attn_pad_mask, get_non_pad_mask, get_subsequent_mask, pad_list
+from .module import PositionalEncoding, PositionwiseFeedForward, mask_rows
 
 IGNORE_ID = config.IGNORE_ID
 
 
 class Decoder(nn.Module):
-    ''' A decoder model with self attention mechanism (decoder.py:16-191, 301-385).
+    ''' Two n_layers-deep decoders, left-to-right and right-to-left, that attend to the same encoder output and swap
+    information after every layer; 16 greedy / teacher-forced steps each (decoder.py:16-191, 301-385).
 
     Same constructor / forward / recognize_beam signatures and state-dict keys as the reference.  What differs
     is how the same numbers are produced:
@@ -42,10 +43,9 @@ class Decoder(nn.Module):
             tgt_emb_prj_weight_sharing=True,
             pe_maxlen=5000):
         super(Decoder, self).__init__()
-        self.sos_id = sos_id  # Start of Sentence
-        self.eos_id = eos_id  # End of Sentence
+        self.sos_id = sos_id
+        self.eos_id = eos_id
         self.n_tgt_vocab = n_tgt_vocab
-
         self.d_word_vec = d_word_vec
         self.n_layers = n_layers
         self.n_head = n_head
@@ -60,18 +60,15 @@ class Decoder(nn.Module):
         self.positional_encoding = PositionalEncoding(d_model, max_len=pe_maxlen)
         self.dropout = nn.Dropout(dropout)
 
-        self.layer_first_l2r = DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout=dropout)
-        self.layer_stack_l2r = nn.ModuleList([
-            DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout=dropout)
-            for _ in range(self.n_layers - 1)])
+        def direction():        # one direction's layers: the first one, then the remaining n_layers - 1
+            layer = lambda: DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout)      # noqa: E731
+            return layer(), nn.ModuleList(layer() for _ in range(n_layers - 1))
 
-        self.layer_first_r2l = DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout=dropout)
-        self.layer_stack_r2l = nn.ModuleList([
-            DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout=dropout)
-            for _ in range(self.n_layers - 1)])
+        self.layer_first_l2r, self.layer_stack_l2r = direction()
+        self.layer_first_r2l, self.layer_stack_r2l = direction()
 
-        self.x_logit_scale = 1.
-        # 58 = 56 + <sos> + <eos>; hard-coded like decoder.py:59-60
+        self.x_logit_scale = 1.0
+        # output heads: 512 features -> 58 classes (56 tokens, <sos>, <eos>), fixed sizes as in decoder.py:59-60
         self.tgt_word_prj_l2r = nn.Linear(512, 58, bias=False)
         self.tgt_word_prj_r2l = nn.Linear(512, 58, bias=False)
 
@@ -97,14 +94,13 @@ class Decoder(nn.Module):
         n_valid = valid.sum(1, keepdim=True)
         pos = torch.arange(To, device=padded_input.device).unsqueeze(0)
         comp = torch.where(pos < n_valid, comp, torch.full_like(comp, self.eos_id))
-        ys_in_pad = padded_input.new_full((N, maxlen), self.eos_id)
-        ys_out_pad = padded_input.new_full((N, maxlen), self.eos_id)
-        ys_in_pad[:, 0] = self.sos_id
+        ys_in = padded_input.new_full((N, maxlen), self.eos_id)
+        ys_out = padded_input.new_full((N, maxlen), self.eos_id)
+        ys_in[:, 0] = self.sos_id
         w = min(To, maxlen - 1)
-        ys_in_pad[:, 1:1 + w] = comp[:, :w]
-        ys_out_pad[:, :min(To, maxlen)] = comp[:, :maxlen]
-        assert ys_in_pad.size() == ys_out_pad.size()
-        return ys_in_pad, ys_out_pad
+        ys_in[:, 1:1 + w] = comp[:, :w]
+        ys_out[:, :min(To, maxlen)] = comp[:, :maxlen]
+        return ys_in, ys_out
 
     def _preprocess_device(self, a, b=None):
         """preprocess on the GPU: one launch of sbl_decoder_preprocess for one target tensor or for both directions (instead
@@ -234,12 +230,8 @@ class Decoder(nn.Module):
 
     def forward(self, padded_input_l2r, padded_input_r2l, encoder_outputs,
                 encoder_input_lengths, return_attns=False):
-        """
-        Args:
-            padded_input: N x To
-            encoder_padded_outputs: N x Ti x H
-        Returns: (pred_l2r (N,16,58), gold_l2r (N,16), pred_r2l, gold_r2l)
-        """
+        """padded_input_l2r / _r2l (N, To) IGNORE_ID-padded targets, encoder_outputs (N, Ti, d_model).
+        Returns (pred_l2r (N,16,58), gold_l2r (N,16), pred_r2l, gold_r2l)."""
         dev = encoder_outputs.device
         if dev.type == "cuda" and padded_input_l2r.shape == padded_input_r2l.shape:
             ys_in_pad_l2r, ys_out_pad_l2r, ys_in_pad_r2l, ys_out_pad_r2l = self._preprocess_device(
@@ -268,7 +260,7 @@ class Decoder(nn.Module):
 
 
 class DecoderLayer(nn.Module):
-    ''' Compose with three layers (decoder.py:387-408) '''
+    ''' Causal self-attention, attention to the encoder output, position-wise FFN (decoder.py:387-408) '''
 
     def __init__(self, d_model, d_inner, n_head, d_k, d_v, dropout=0.1):
         super(DecoderLayer, self).__init__()
@@ -285,18 +277,8 @@ class DecoderLayer(nn.Module):
 
     def forward(self, dec_input, enc_output, non_pad_mask=None, slf_attn_mask=None, dec_enc_attn_mask=None,
                 enc_kv=None):
-        dec_output, dec_slf_attn = self.slf_attn(
-            dec_input, dec_input, dec_input, mask=slf_attn_mask)
-        if non_pad_mask is not None:
-            dec_output = ops.RowScaleFn.apply(dec_output, non_pad_mask)
-
-        dec_output, dec_enc_attn = self.enc_attn(
-            dec_output, enc_output, enc_output, mask=dec_enc_attn_mask, kv_proj=enc_kv)
-        if non_pad_mask is not None:
-            dec_output = ops.RowScaleFn.apply(dec_output, non_pad_mask)
-
-        dec_output = self.pos_ffn(dec_output)
-        if non_pad_mask is not None:
-            dec_output = ops.RowScaleFn.apply(dec_output, non_pad_mask)
-
-        return dec_output, dec_slf_attn, dec_enc_attn
+        h, self_attn = self.slf_attn(dec_input, dec_input, dec_input, mask=slf_attn_mask)
+        h = mask_rows(h, non_pad_mask)
+        h, cross_attn = self.enc_attn(h, enc_output, enc_output, mask=dec_enc_attn_mask, kv_proj=enc_kv)
+        h = mask_rows(h, non_pad_mask)
+        return mask_rows(self.pos_ffn(h), non_pad_mask), self_attn, cross_attn

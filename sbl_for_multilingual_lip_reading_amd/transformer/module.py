@@ -1,4 +1,4 @@
-"""Mirror of SBL_Multilingual_Lip_reading/transformer/module.py."""
+"""PositionalEncoding and PositionwiseFeedForward with the class surface of the reference's transformer/module.py."""
 import math
 
 import torch
@@ -8,23 +8,20 @@ from ._env import ops
 
 
 class PositionalEncoding(nn.Module):
-    """PE(pos, 2i) = sin(pos/10000^(2i/d)), PE(pos, 2i+1) = cos(...) — module.py:8-32.  The table is a buffer
-    named 'pe' of shape (1, max_len, d_model), built in log space in fp32 exactly like the reference (host-side,
-    construction time only)."""
+    """Sinusoidal position table as a buffer 'pe' of shape (1, max_len, d_model): column 2i holds sin(pos * w_i),
+    column 2i+1 holds cos(pos * w_i), with w_i = 10000^(-2i/d_model) evaluated as exp(2i * -ln(10000)/d_model) in
+    fp32 (the reference's rounding; the angle is one fp32 product).  Built once on the host at construction."""
 
     def __init__(self, d_model, max_len=5000):
         super(PositionalEncoding, self).__init__()
-        pe = torch.zeros(max_len, d_model, requires_grad=False)
-        position = torch.arange(0, max_len).unsqueeze(1).float()
-        div_term = torch.exp(torch.arange(0, d_model, 2).float() * -(math.log(10000.0) / d_model))
-        pe[:, 0::2] = torch.sin(position * div_term)
-        pe[:, 1::2] = torch.cos(position * div_term)
-        pe = pe.unsqueeze(0)
-        self.register_buffer('pe', pe)
+        freq = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float32) * -(math.log(10000.0) / d_model))
+        angle = torch.outer(torch.arange(max_len, dtype=torch.float32), freq)          # (max_len, d_model / 2)
+        table = torch.stack((angle.sin(), angle.cos()), dim=-1).flatten(1)            # sin, cos interleaved
+        self.register_buffer('pe', table.unsqueeze(0))
 
     def forward(self, input):
-        length = input.size(1)
-        return self.pe[:, :length]
+        """The first input.size(1) rows of the table, (1, T, d_model)."""
+        return self.pe[:, :input.size(1)]
 
 
 class PositionwiseFeedForward(nn.Module):
@@ -41,3 +38,8 @@ class PositionwiseFeedForward(nn.Module):
         drop_p = self.dropout.p if self.training else 0.0
         return ops.FFNFn.apply(x, self.w_1.weight, self.w_1.bias, self.w_2.weight, self.w_2.bias,
                                self.layer_norm.weight, self.layer_norm.bias, drop_p, self.layer_norm.eps)
+
+
+def mask_rows(x, non_pad_mask):
+    """x * non_pad_mask (zeroes the padded positions) as one tape node; x itself when there is no mask."""
+    return x if non_pad_mask is None else ops.RowScaleFn.apply(x, non_pad_mask)

@@ -1,32 +1,32 @@
-"""Mirror of SBL_Multilingual_Lip_reading/transformer/optimizer.py."""
+"""TransformerOptimizer (the reference's transformer/optimizer.py surface) and FusedAdam."""
+
+_SCHEDULE_D_MODEL = 512      # the schedule's model width is fixed, whatever the model's
 
 
 class TransformerOptimizer(object):
-    """A simple wrapper class for learning rate scheduling (optimizer.py:1-27): Noam schedule
-    lr = k * 512^-0.5 * min(step^-0.5, step * warmup^-1.5), set on every param group before each step."""
+    """Drives a torch-style optimizer with the Noam schedule: step n (counted from 1) runs at
+    lr = k / sqrt(512) * min(1 / sqrt(n), n / warmup_steps^1.5), i.e. a linear warm-up that turns into 1/sqrt(n)
+    decay at n = warmup_steps.  The rate is written into every param group just before the wrapped step."""
 
     def __init__(self, optimizer, warmup_steps=4000, k=0.2):
         self.optimizer = optimizer
         self.k = k
         self.warmup_steps = warmup_steps
-        d_model = 512
-        self.init_lr = d_model ** (-0.5)
-        self.lr = self.init_lr
-        self.step_num = 0
+        self.init_lr = _SCHEDULE_D_MODEL ** -0.5
+        self.lr, self.step_num = self.init_lr, 0
 
     def zero_grad(self):
-        self.optimizer.zero_grad()
+        return self.optimizer.zero_grad()
 
     def step(self):
         self._update_lr()
-        self.optimizer.step()
+        return self.optimizer.step()
 
     def _update_lr(self):
-        self.step_num += 1
-        self.lr = self.k * self.init_lr * min(self.step_num ** (-0.5),
-                                              self.step_num * (self.warmup_steps ** (-1.5)))
-        for param_group in self.optimizer.param_groups:
-            param_group['lr'] = self.lr
+        n = self.step_num = self.step_num + 1
+        self.lr = self.k * self.init_lr * min(n ** -0.5, n * self.warmup_steps ** -1.5)
+        for group in self.optimizer.param_groups:
+            group["lr"] = self.lr
 
 
 class FusedAdam(object):

@@ -1,53 +1,53 @@
-"""Mirror of the hot-path helpers of SBL_Multilingual_Lip_reading/transformer/utils.py (:1-9, :98-147).
-Host-side index/mask construction only (the reference builds them with the same torch calls); the ESPnet
-leftovers (:12-91) are out of scope."""
+"""Host-side mask and padding helpers with the names, dtypes and shapes of the reference's
+SBL_Multilingual_Lip_reading/transformer/utils.py (:1-9, :98-147), built batch-at-once (no per-sample loop).
+Of these, the encoder uses the two length masks (and only for ragged batches); the decoder builds its masks on the
+device.  The rest are kept for code written against the reference."""
 import torch
+
+_PAD_LEN = 16      # pad_list pads to a fixed length (the decoder's 16 steps), not to the longest sequence
 
 
 def pad_list(xs, pad_value):
-    # utils.py:1-9 — fixed max_len = 16
-    n_batch = len(xs)
-    max_len = 16
-    pad = xs[0].new(n_batch, max_len, *xs[0].size()[1:]).fill_(pad_value)
-    for i in range(n_batch):
-        pad[i, :xs[i].size(0)] = xs[i]
-    return pad
+    """Stack 1-d (or (L, ...)) tensors of lengths <= 16 into (len(xs), 16, ...) of xs[0]'s dtype, filled with
+    pad_value past each length."""
+    packed = torch.nn.utils.rnn.pad_sequence(xs, batch_first=True, padding_value=pad_value)
+    out = xs[0].new_full((len(xs), _PAD_LEN) + tuple(xs[0].shape[1:]), pad_value)
+    out[:, :packed.size(1)] = packed
+    return out
+
+
+def _valid_positions(padded_input, input_lengths):
+    """Bool (N, T, ...) over padded_input.shape[:-1]: True at time steps t < input_lengths[n]."""
+    n, t = padded_input.shape[:2]
+    lengths = torch.as_tensor(input_lengths, device=padded_input.device).view(n, 1)
+    valid = torch.arange(t, device=padded_input.device) < lengths
+    return valid.view(n, t, *(1,) * (padded_input.dim() - 3)).expand(padded_input.shape[:-1])
 
 
 def get_non_pad_mask(padded_input, input_lengths=None, pad_idx=None):
-    """padding position is set to 0, either use input_lengths or pad_idx (utils.py:98-113)"""
-    assert input_lengths is not None or pad_idx is not None
-    if input_lengths is not None:
-        N = padded_input.size(0)
-        non_pad_mask = padded_input.new_ones(padded_input.size()[:-1])  # N x T
-        for i in range(N):
-            non_pad_mask[i, input_lengths[i]:] = 0
-    if pad_idx is not None:
-        assert padded_input.dim() == 2
-        non_pad_mask = padded_input.ne(pad_idx).float()
-    return non_pad_mask.unsqueeze(-1)
+    """(..., 1) mask that is 1 on real positions and 0 on padding, from per-sample lengths (in padded_input's dtype)
+    or from the token id pad_idx of a 2-d id tensor (float32); pad_idx wins when both are given."""
+    if pad_idx is None:
+        assert input_lengths is not None, "get_non_pad_mask needs input_lengths or pad_idx"
+        return _valid_positions(padded_input, input_lengths).to(padded_input.dtype).unsqueeze(-1)
+    assert padded_input.ndim == 2, "a pad_idx mask is built from (N, T) token ids"
+    return padded_input.ne(pad_idx).float().unsqueeze(-1)
 
 
 def get_subsequent_mask(seq):
-    ''' For masking out the subsequent info (utils.py:116-124). '''
-    sz_b, len_s = seq.size()
-    subsequent_mask = torch.triu(
-        torch.ones((len_s, len_s), device=seq.device, dtype=torch.uint8), diagonal=1)
-    subsequent_mask = subsequent_mask.unsqueeze(0).expand(sz_b, -1, -1)  # b x ls x ls
-    return subsequent_mask
+    """Causal mask for ids seq (N, L): uint8 (N, L, L), 1 above the diagonal (the future keys), one shared (L, L)
+    table expanded over the batch."""
+    n, length = seq.shape
+    future = torch.ones((length, length), dtype=torch.uint8, device=seq.device).triu(1)
+    return future.expand(n, length, length)
 
 
 def get_attn_key_pad_mask(seq_k, seq_q, pad_idx):
-    ''' For masking out the padding part of key sequence (utils.py:127-137). '''
-    len_q = seq_q.size(1)
-    padding_mask = seq_k.eq(pad_idx)
-    padding_mask = padding_mask.unsqueeze(1).expand(-1, len_q, -1)  # b x lq x lk
-    return padding_mask
+    """Bool (N, Lq, Lk), True where key id seq_k[n, j] == pad_idx; a view expanded over the query length."""
+    return seq_k.eq(pad_idx).unsqueeze(1).expand(-1, seq_q.size(1), -1)
 
 
 def get_attn_pad_mask(padded_input, input_lengths, expand_length):
-    """mask position is set to 1 (utils.py:140-147)"""
-    non_pad_mask = get_non_pad_mask(padded_input, input_lengths=input_lengths)
-    pad_mask = non_pad_mask.squeeze(-1).lt(1)
-    attn_mask = pad_mask.unsqueeze(1).expand(-1, expand_length, -1)
-    return attn_mask
+    """Bool (N, expand_length, T), True on padded key positions; a view expanded over the query length."""
+    padded = ~_valid_positions(padded_input, input_lengths)
+    return padded.unsqueeze(1).expand(-1, expand_length, -1)

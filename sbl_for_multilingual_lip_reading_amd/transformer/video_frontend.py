@@ -1,8 +1,9 @@
 # coding: utf-8
-"""Mirror of SBL_Multilingual_Lip_reading/transformer/video_frontend.py: Conv3d stem + ResNet-18 trunk.
+"""The visual frontend with the class surface and state-dict keys of the reference's transformer/video_frontend.py:
+Conv3d stem + ResNet-18 trunk.
 
-The torch.nn conv / batch-norm modules below are parameter containers only (so state-dict keys, shapes,
-.to(), pickling and the reference's init code behave identically); their own forward is never called.
+The torch.nn conv / batch-norm modules below are parameter containers only (so state-dict keys, shapes, .to(),
+pickling and the seeded initialisation behave like the reference's); their own forward is never called.
 Activations flow channels-last: (N*T, h, w, C)."""
 import math
 
@@ -13,8 +14,21 @@ from ._env import config, ops
 
 
 def conv3x3(in_planes, out_planes, stride=1):
-    return nn.Conv2d(in_planes, out_planes, kernel_size=3, stride=stride,
-                     padding=1, bias=False)
+    """Bias-free 3x3 convolution, padding 1."""
+    return nn.Conv2d(in_planes, out_planes, 3, stride, 1, bias=False)
+
+
+def _he_init(modules):
+    """Conv kernels ~ N(0, 2 / (out_channels * kernel volume)) with zero biases, BatchNorm affines (1, 0); applied in
+    the iteration order of `modules`, which fixes the RNG draws."""
+    for m in modules:
+        if isinstance(m, (nn.Conv1d, nn.Conv2d, nn.Conv3d)):
+            nn.init.normal_(m.weight, 0.0, math.sqrt(2.0 / (m.out_channels * math.prod(m.kernel_size))))
+            if isinstance(m.bias, torch.Tensor):
+                nn.init.zeros_(m.bias)
+        elif isinstance(m, (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d)):
+            nn.init.ones_(m.weight)
+            nn.init.zeros_(m.bias)
 
 
 def _conv_bn(x, conv, bn, res, relu, training, box_out=None, box_in=None, ctl=None):
@@ -60,68 +74,51 @@ class BasicBlock(nn.Module):
 
 
 class ResNet(nn.Module):
+    """layer1..layer4 of ResNet-18 (the stem lives in Lipreading), then global average pooling."""
+
+    _STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))      # (planes, stride of the stage's first block)
 
     def __init__(self, block, layers):
-        self.inplanes = 64
         super(ResNet, self).__init__()
-        self.layer1 = self._make_layer(block, 64, layers[0])
-        self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
-        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
-        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        self.inplanes = 64         # channels entering the next stage (the stem's 64)
+        for i, ((planes, stride), n_blocks) in enumerate(zip(self._STAGES, layers)):
+            setattr(self, "layer%d" % (i + 1), self._stage(block, planes, n_blocks, stride))
         self.avgpool = nn.AdaptiveAvgPool2d(1)
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                n = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
-                m.weight.data.normal_(0, math.sqrt(2. / n))
-            elif isinstance(m, nn.BatchNorm2d):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
+        _he_init(self.modules())
 
-    def _make_layer(self, block, planes, blocks, stride=1):
-        downsample = None
-        if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(
-                nn.Conv2d(self.inplanes, planes * block.expansion,
-                          kernel_size=1, stride=stride, bias=False),
-                nn.BatchNorm2d(planes * block.expansion),
-            )
-
-        layers = []
-        layers.append(block(self.inplanes, planes, stride, downsample))
-        self.inplanes = planes * block.expansion
-        for i in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
-
-        return nn.Sequential(*layers)
+    def _stage(self, block, planes, n_blocks, stride):
+        """n_blocks blocks of `planes` channels; the first one strides and, when the shape changes, gets a 1x1 conv +
+        BatchNorm projection shortcut, built before the block itself (the RNG order depends on it)."""
+        width = planes * block.expansion
+        shortcut = None
+        if stride != 1 or self.inplanes != width:
+            shortcut = nn.Sequential(nn.Conv2d(self.inplanes, width, 1, stride, bias=False), nn.BatchNorm2d(width))
+        blocks = [block(self.inplanes, planes, stride, shortcut)]
+        self.inplanes = width
+        blocks += [block(width, planes) for _ in range(1, n_blocks)]
+        return nn.Sequential(*blocks)
 
     def forward(self, x):
         """x: (N*T, h, w, 64) channels-last -> (N*T, 512)   (video_frontend.py:82-89)"""
-        x = self.layer1(x)
-        x = self.layer2(x)
-        x = self.layer3(x)
-        x = self.layer4(x)
+        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
+            x = stage(x)
         return ops.AvgPoolFn.apply(x)
 
 
 class Lipreading(nn.Module):
+    """(N, 1, T, H, W) grayscale clips -> (N, T, 512) per-frame features: Conv3d 5x7x7 stem + BN + ReLU + 3x3 max-pool
+    (one fused kernel), the ResNet-18 trunk per frame, then the reference's always-on dropout."""
+
     def __init__(self, hiddenDim=512, embedSize=256):
         super(Lipreading, self).__init__()
-        self.inputDim = 512
-        self.hiddenDim = hiddenDim
-        self.embedSize = embedSize
-        self.nLayers = 3
-        # frontend3D (parameter containers; computed by the fused stem kernels)
-        self.frontend3D = nn.Sequential(
-            nn.Conv3d(1, 64, kernel_size=(5, 7, 7), stride=(1, 2, 2), padding=(2, 3, 3), bias=False),
-            nn.BatchNorm3d(64),
-            nn.ReLU(True),
-            nn.MaxPool3d(kernel_size=(1, 3, 3), stride=(1, 2, 2), padding=(0, 1, 1))
-        )
-        # resnet
+        self.inputDim, self.hiddenDim, self.embedSize, self.nLayers = 512, hiddenDim, embedSize, 3
+        self.frontend3D = nn.Sequential(           # parameter containers of the fused stem kernel (ops.StemFn)
+            nn.Conv3d(1, 64, (5, 7, 7), (1, 2, 2), (2, 3, 3), bias=False), nn.BatchNorm3d(64), nn.ReLU(True),
+            nn.MaxPool3d((1, 3, 3), (1, 2, 2), (0, 1, 1)))
         self.resnet18 = ResNet(BasicBlock, [2, 2, 2, 2])
         # the reference's always-on F.dropout(p=0.5) (video_frontend.py:122); set to 0.0 for parity runs
         self.frontend_dropout_p = config.FRONTEND_DROPOUT_P
-        self._initialize_weights()
+        _he_init(self.modules())      # again over the trunk too: its draws are overwritten but advance the RNG
 
     def _frontend_forward(self, x):
         """x: (N, 1, T, H, W) or (N, T, H, W) -> (N*T, 512)"""
@@ -133,40 +130,24 @@ class Lipreading(nn.Module):
         return self.resnet18(x)
 
     def forward(self, x):
-        frameLen = x.size(2) if x.dim() == 5 else x.size(1)
-        x = self._frontend_forward(x)
-        x = ops.dropout(x, self.frontend_dropout_p, True)      # active in eval too, like the reference
-        x = x.view(-1, frameLen, self.inputDim)
-        return x
-
-    def _initialize_weights(self):
-        for m in self.modules():
-            if isinstance(m, (nn.Conv3d, nn.Conv2d, nn.Conv1d)):
-                n = m.out_channels
-                for ksz in m.kernel_size:
-                    n *= ksz
-                m.weight.data.normal_(0, math.sqrt(2. / n))
-                if m.bias is not None:
-                    m.bias.data.zero_()
-            elif isinstance(m, (nn.BatchNorm3d, nn.BatchNorm2d, nn.BatchNorm1d)):
-                m.weight.data.fill_(1)
-                m.bias.data.zero_()
+        frames = x.size(2) if x.dim() == 5 else x.size(1)
+        feats = ops.dropout(self._frontend_forward(x), self.frontend_dropout_p, True)   # in eval too, like the reference
+        return feats.view(-1, frames, self.inputDim)
 
 
 device = config.device
 
 
 def visual_frontend(pt=None):
-    """video_frontend.py:176-190: build the frontend; with a local path, copy every name+shape-matching entry
-    of that state dict (tensor-only load)."""
-    model = Lipreading(hiddenDim=512, embedSize=256)
-    if pt is not None:
-        model_dict = model.state_dict()
-        pretrained_dict = torch.load(pt, map_location=device, weights_only=True)
-        print(len(pretrained_dict))
-        pretrained_dict = {k: v for k, v in pretrained_dict.items()
-                           if k in model_dict.keys() and v.size() == model_dict[k].size()}
-        print('loaded params/tot params:{}/{}'.format(len(pretrained_dict), len(model_dict)))
-        model_dict.update(pretrained_dict)
-        model.load_state_dict(model_dict)
+    """A new Lipreading frontend.  With a checkpoint path: every state-dict entry of that file (tensors only) whose
+    name and shape match one of the model's replaces it; everything else keeps its initial value."""
+    model = Lipreading()
+    if pt is None:
+        return model
+    own = model.state_dict()
+    saved = torch.load(pt, map_location=device, weights_only=True)
+    hits = {k: v for k, v in saved.items() if k in own and v.shape == own[k].shape}
+    print("visual_frontend: %d of the model's %d entries loaded from %s (%d entries in the file)"
+          % (len(hits), len(own), pt, len(saved)))
+    model.load_state_dict({**own, **hits})
     return model
