@@ -354,6 +354,32 @@ int sbl_smoothed_ce_fwd(const float* pred, const int64_t* gold, float* out3, int
 int sbl_smoothed_ce_bwd(const float* pred, const int64_t* gold, const float* out3, const float* gscale, float* dpred,
                         int R, int C, float eps, int ignore_id, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
+ * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
+ * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.
+ * Plain fp32 FMA in every sbl_set_matmul_precision mode; deterministic (no atomics, every sum in a fixed order).
+ * fwd (2 launches): pooled (N,D) = mean over t of enc (kept for bwd), pooled_t (D,N) scratch, logits1 (N,C1) =
+ * pooled W1^T + b1, logits2 (N,C2) = enc[:, lang_index] W2^T + b2 (the reference reads row 30 of its 31-frame clips). */
+int sbl_cls_head_fwd(const float* enc, const float* w1, const float* b1, const float* w2, const float* b2, float* pooled,
+                     float* pooled_t, float* logits1, float* logits2, int N, int T, int D, int C1, int C2, int lang_index,
+                     sbl_stream_t stream);
+/* loss = CE(logits1, tgt1) + lang_weight * CE(logits2, tgt2): CLS/train.py:127-130 (nn.CrossEntropyLoss, each a mean over the
+ * rows whose target != ignore_id).  stats6 = {loss sum, valid rows, correct} of head 1, then of head 2 (argmax ties go to the
+ * lowest index; CLS/train.py:115-121).  One launch, written by the call (nothing to zero).  bwd (one launch): dlogits =
+ * gscale[0] / valid * (softmax - onehot) for head 1, times lang_weight for head 2, 0 on ignored rows. */
+int sbl_cls_loss_fwd(const float* logits1, const float* logits2, const int64_t* tgt1, const int64_t* tgt2, int N, int C1,
+                     int C2, float lang_weight, int ignore_id, float* loss, float* stats6, sbl_stream_t stream);
+int sbl_cls_loss_bwd(const float* logits1, const float* logits2, const int64_t* tgt1, const int64_t* tgt2, const float* stats6,
+                     const float* gscale, float* dlogits1, float* dlogits2, int N, int C1, int C2, float lang_weight,
+                     int ignore_id, sbl_stream_t stream);
+/* head bwd (one launch): dW1 = dlogits1^T pooled, db1 = sum_n dlogits1, dW2 = dlogits2^T enc[:, lang_index], db2 = sum_n
+ * dlogits2; d_enc[n,t] = dlogits1[n] W1 / T, + dlogits2[n] W2 on t == lang_index.  accumulate = 1: the four parameter
+ * gradients are added to (persistent flat gradient buffers); d_enc is always written.  Any of the five outputs may be NULL
+ * (not computed). */
+int sbl_cls_head_bwd(const float* enc, const float* pooled, const float* dlogits1, const float* dlogits2, const float* w1,
+                     const float* w2, float* d_enc, float* dw1, float* db1, float* dw2, float* db2, int N, int T, int D,
+                     int C1, int C2, int lang_index, int accumulate, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- device input pipeline
  * uint8 grayscale frames (N,Tin,Hin,Win) -> fp32 clips (N,Tout,Hc,Wc): out = lut256[in[n, src_frame[n,t], y1[n]+y,
  * x1[n] + (flip[n] ? Wc-1-x : x)]], zero where src_frame < 0.  lut256[v] = float32((v/255. - mean)/std) computed in

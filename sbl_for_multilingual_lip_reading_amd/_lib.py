@@ -65,6 +65,10 @@ SIGNATURES = {
     "sbl_decoder_preprocess": [P, P, P, P, P, P, I, I, I, L, L, L, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
+    "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "sbl_cls_loss_fwd": [P, P, P, P, I, I, I, F, I, P, P, P],
+    "sbl_cls_loss_bwd": [P, P, P, P, P, P, P, P, I, I, I, F, I, P],
+    "sbl_cls_head_bwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
     "sbl_preprocess_clips": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_set_matmul_precision": [I],

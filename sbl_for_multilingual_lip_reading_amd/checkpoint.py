@@ -45,12 +45,24 @@ def save_checkpoint(path, model, optimizer=None, **meta):
     torch.save(out, path)
 
 
-def load_checkpoint(path, model, optimizer=None, strict=True):
+def load_checkpoint(path, model, optimizer=None, strict=True, prefix_map=None):
     """Loads tensors only (weights_only=True): a pickled-module checkpoint of the reference is refused by torch.
     Accepts either {'model_state_dict': ...} or a bare state dict; `visual_frontend.`-less keys of a frontend-only
-    file (`video_frontend.py:179-188`) are loaded into model.visual_frontend.  Returns the metadata dict."""
+    file (`video_frontend.py:179-188`) are loaded into model.visual_frontend.  Returns the metadata dict.
+
+    prefix_map (opt-in): {saved key prefix: model key prefix}, applied to the file's keys before matching.  The stage 1 -> 2
+    hand-off: a ClassifierTransformer checkpoint loaded into the SBL Transformer with strict=False loads the frontend by
+    name and drops `encoder_v.*` / `fc_*` (what SBL/train.py:92-103 does); with prefix_map={"encoder_v.": "encoder."} the
+    pre-trained encoder is loaded too."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
     sd = ck.get("model_state_dict", ck) if isinstance(ck, dict) else ck
+    if prefix_map:
+        def _rename(k):
+            for a, b in prefix_map.items():
+                if k.startswith(a):
+                    return b + k[len(a):]
+            return k
+        sd = {_rename(k): v for k, v in sd.items()}
     m = model.module if hasattr(model, "module") else model
     own = m.state_dict()
     if not any(k in own for k in sd) and hasattr(m, "visual_frontend") and all(("visual_frontend." + k) in own for k in sd):

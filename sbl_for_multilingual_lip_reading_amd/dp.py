@@ -58,19 +58,21 @@ class FlatModel:
     SEGMENTS: name prefixes in the order their gradients complete during backward (reverse autograd order: decoder,
     encoder, then the ResNet stages from the last to the first, the Conv3d stem at the very end); each becomes one
     contiguous range of the flat buffers, all-reduced in buckets of <= GradientExchange.bucket_bytes as soon as backward
-    has passed it.  Only layer1 + stem (0.6 MB) are left to exchange after the step."""
+    has passed it.  Only layer1 + stem (0.6 MB) are left to exchange after the step.  A model class may declare its own
+    layout as FLAT_SEGMENTS (transformer.classifier.ClassifierTransformer does); `self.segments` is the one in use."""
 
     SEGMENTS = ("decoder.", "encoder.", "visual_frontend.resnet18.layer4.", "visual_frontend.resnet18.layer3.",
                 "visual_frontend.resnet18.layer2.", "visual_frontend.")
 
     def __init__(self, model):
         self.model = model
+        self.segments = tuple(getattr(model, "FLAT_SEGMENTS", self.SEGMENTS))
         names = {id(p): n for n, p in model.named_parameters()}
         params = _ordered_params(model)
-        by_seg = {s: [] for s in self.SEGMENTS}
+        by_seg = {s: [] for s in self.segments}
         for p in params:
             n = names[id(p)]
-            seg = next((s for s in self.SEGMENTS if n.startswith(s)), self.SEGMENTS[-1])
+            seg = next((s for s in self.segments if n.startswith(s)), self.segments[-1])
             by_seg[seg].append(p)
         dev = params[0].device
         # 16-byte alignment of every tensor start (float4 loads in the kernels): pad numel to a multiple of 4
@@ -82,7 +84,7 @@ class FlatModel:
         self.slots = []          # (parameter, offset, padded numel) in buffer order
         off = 0
         with torch.no_grad():
-            for seg in self.SEGMENTS:
+            for seg in self.segments:
                 start = off
                 for p in by_seg[seg]:
                     n = p.numel()
@@ -157,8 +159,8 @@ class FlatModel:
 
     def span(self, prefix):
         """[lo, hi) of the flat buffers covering every segment whose name starts with `prefix` (segments are laid out in
-        SEGMENTS order, so e.g. "visual_frontend." spans the four frontend segments)."""
-        r = [self.ranges[s] for s in self.SEGMENTS if s.startswith(prefix)]
+        segment order, so e.g. "visual_frontend." spans the four frontend segments)."""
+        r = [self.ranges[s] for s in self.segments if s.startswith(prefix)]
         return min(a for a, _ in r), max(b for _, b in r)
 
 
@@ -192,17 +194,17 @@ class GradientExchange:
         encoder output for the decoder (all 16 steps and the hoisted K/V projections are behind it), the frontend
         features for the encoder, and the input of ResNet stage k for stage k.  Tensor hooks there launch the finished
         segment while the rest of backward runs.  (Parameter hooks cannot be used: the kernels accumulate into the flat
-        gradient buffer themselves and autograd never sees those gradients.)"""
+        gradient buffer themselves and autograd never sees those gradients.)  A model class may name its own (module,
+        segment) pairs as FLAT_FEEDS (the classifier: encoder_v output -> its heads, frontend output -> encoder_v)."""
         model = self.flat.model
+        feeds = getattr(model, "FLAT_FEEDS", (("encoder", "decoder."), ("visual_frontend", "encoder.")))
 
-        def on_encoder_out(mod, inp, out):
-            t = out[0] if isinstance(out, (tuple, list)) else out
-            if t.requires_grad:
-                t.register_hook(lambda g: self.launch("decoder."))
-
-        def on_frontend_out(mod, inp, out):
-            if out.requires_grad:
-                out.register_hook(lambda g: self.launch("encoder."))
+        def on_output(seg):
+            def hook(mod, inp, out):
+                t = out[0] if isinstance(out, (tuple, list)) else out
+                if t.requires_grad:
+                    t.register_hook(lambda g: self.launch(seg))
+            return hook
 
         def stage_pre_hook(seg):
             def pre(mod, inp):
@@ -211,8 +213,8 @@ class GradientExchange:
                     x.register_hook(lambda g: self.launch(seg))
             return pre
 
-        self._hooks.append(model.encoder.register_forward_hook(on_encoder_out))
-        self._hooks.append(model.visual_frontend.register_forward_hook(on_frontend_out))
+        for name, seg in feeds:
+            self._hooks.append(getattr(model, name).register_forward_hook(on_output(seg)))
         res = getattr(model.visual_frontend, "resnet18", None)
         if res is not None:
             for k in (4, 3, 2):
@@ -266,7 +268,7 @@ class GradientExchange:
         """Call after backward: exchanges whatever has not gone out yet (layer1 + stem) and joins the side stream."""
         if self.world <= 1:
             return
-        for seg in FlatModel.SEGMENTS:
+        for seg in getattr(self.flat, "segments", FlatModel.SEGMENTS):
             self.launch(seg, _from_finish=True)
         if self.cuda:
             torch.cuda.current_stream().wait_stream(self.stream)

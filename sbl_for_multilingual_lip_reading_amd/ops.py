@@ -1027,6 +1027,98 @@ class SmoothedCEFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- #
+# stage-1 classification heads (CLS pre-training model)
+# --------------------------------------------------------------------------- #
+class ClsHeadFn(torch.autograd.Function):
+    """fc_1500(mean over time) and fc_2(row lang_index) of the encoder output (N, T, 512): CLS/transformer/transformer.py:31-35
+    as oracle.sbl_oracle.cls_forward restates it.  Returns (logits1 (N, C1), logits2 (N, C2)).  Parameter gradients go
+    straight into the flat gradient buffers when the model is flattened (dp.FlatModel), like LinearFn's."""
+
+    @staticmethod
+    def forward(ctx, enc, w1, b1, w2, b2, lang_index):
+        _need_cuda(enc, w1, b1, w2, b2)
+        enc = enc.contiguous()
+        N, T, D = enc.shape
+        C1, C2 = w1.size(0), w2.size(0)
+        dev = enc.device
+        pooled = torch.empty(N, D, device=dev, dtype=torch.float32)
+        pooled_t = torch.empty(D, N, device=dev, dtype=torch.float32)
+        l1 = torch.empty(N, C1, device=dev, dtype=torch.float32)
+        l2 = torch.empty(N, C2, device=dev, dtype=torch.float32)
+        call("sbl_cls_head_fwd", _p(enc), _p(w1), _p(b1), _p(w2), _p(b2), _p(pooled), _p(pooled_t), _p(l1), _p(l2), N, T, D,
+             C1, C2, int(lang_index), _s())
+        ctx.save_for_backward(enc, pooled, w1, w2)
+        ctx.li = int(lang_index)
+        ctx.gb = (_gbuf(w1), _gbuf(b1), _gbuf(w2), _gbuf(b2))
+        return l1, l2
+
+    @staticmethod
+    @_bw
+    def backward(ctx, dl1, dl2):
+        enc, pooled, w1, w2 = ctx.saved_tensors
+        N, T, D = enc.shape
+        C1, C2 = w1.size(0), w2.size(0)
+        dev = enc.device
+        dl1, dl2 = dl1.contiguous(), dl2.contiguous()
+        need = ctx.needs_input_grad
+        d_enc = torch.empty_like(enc) if need[0] else None
+        # all four into the flat gradient (+=), or all four fresh (=) and handed to autograd
+        acc = int(all(g is not None for g in ctx.gb))
+        shapes = ((C1, D), (C1,), (C2, D), (C2,))
+        outs, rets = [], []
+        for k, shp in enumerate(shapes):
+            if not need[1 + k]:
+                outs.append(None)
+                rets.append(None)
+            elif acc:
+                outs.append(ctx.gb[k])
+                rets.append(None)
+            else:
+                t = torch.empty(shp, device=dev, dtype=torch.float32)
+                outs.append(t)
+                rets.append(t)
+        call("sbl_cls_head_bwd", _p(enc), _p(pooled), _p(dl1), _p(dl2), _p(w1), _p(w2), _p(d_enc), *[_p(t) for t in outs], N, T,
+             D, C1, C2, ctx.li, acc, _s())
+        return (d_enc,) + tuple(rets) + (None,)
+
+
+class ClsLossFn(torch.autograd.Function):
+    """CE(logits1, tgt1) + lang_weight * CE(logits2, tgt2), CLS/train.py:127-130, with the per-step correct counts of
+    :115-121.  Returns (loss, stats[6] = (loss sum, valid rows, correct) per head); only the loss is differentiable."""
+
+    @staticmethod
+    def forward(ctx, l1, l2, t1, t2, lang_weight, ignore_id):
+        _need_cuda(l1, l2, t1, t2)
+        l1, l2 = l1.contiguous(), l2.contiguous()
+        t1, t2 = t1.to(torch.int64).contiguous(), t2.to(torch.int64).contiguous()
+        (N, C1), C2 = l1.shape, l2.size(1)
+        if l2.size(0) != N or t1.numel() != N or t2.numel() != N:
+            raise _lib.SblHipError("cls loss: %d rows of logits1, %d of logits2, %d and %d targets" % (N, l2.size(0), t1.numel(), t2.numel()))
+        loss = torch.empty((), device=l1.device, dtype=torch.float32)
+        stats = torch.empty(6, device=l1.device, dtype=torch.float32)
+        call("sbl_cls_loss_fwd", _p(l1), _p(l2), _p(t1), _p(t2), N, C1, C2, float(lang_weight), int(ignore_id), _p(loss),
+             _p(stats), _s())
+        ctx.save_for_backward(l1, l2, t1, t2, stats)
+        ctx.cfg = (float(lang_weight), int(ignore_id))
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        return loss, stats
+
+    @staticmethod
+    @_bw
+    def backward(ctx, gloss, _gs):
+        if gloss is None:
+            return (None,) * 6
+        l1, l2, t1, t2, stats = ctx.saved_tensors
+        lw, ignore_id = ctx.cfg
+        (N, C1), C2 = l1.shape, l2.size(1)
+        gs = gloss.reshape(1).to(torch.float32).contiguous()
+        d1, d2 = torch.empty_like(l1), torch.empty_like(l2)
+        call("sbl_cls_loss_bwd", _p(l1), _p(l2), _p(t1), _p(t2), _p(stats), _p(gs), _p(d1), _p(d2), N, C1, C2, lw, ignore_id, _s())
+        return d1, d2, None, None, None, None
+
+
+# --------------------------------------------------------------------------- #
 # visual frontend
 # --------------------------------------------------------------------------- #
 # Packed convolution weights.  The state dict keeps OIHW; the kernels read OHWI (forward / weight gradient) and
