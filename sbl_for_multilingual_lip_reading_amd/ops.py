@@ -9,7 +9,14 @@ non-zero status raises.
 All Functions are hipGraph-capturable: no host sync, no host read of device data;
 dropout seeds and teacher-forcing coins live in device memory.
 """
+import ctypes as _ct
+import functools as _functools
+import threading as _threading
+import weakref as _weakref
+
+import numpy as _np
 import torch
+import torch.distributed as _dist
 
 try:
     from . import _lib
@@ -74,6 +81,14 @@ def zero_pool_take(dev, shape, dtype):
     return st["buf"][off:off + nbytes].view(dtype).view(*shape)
 
 
+def _zeros_or_empty(dev, shape, dtype):
+    """(tensor, pooled): a zero-filled tensor from the pool, or an uninitialised one that the C call has to zero."""
+    t = zero_pool_take(dev, shape, dtype)
+    if t is not None:
+        return t, True
+    return torch.empty(shape, device=dev, dtype=dtype), False
+
+
 def _need_cuda(*ts):
     for t in ts:
         if t is not None and not t.is_cuda:
@@ -99,9 +114,8 @@ class DropoutState:
             # data-parallel replicas draw independent masks (nn.DataParallel's replicas each use their device's
             # generator, SBL/train.py:115): fold the rank into the default seed
             seed = 0x5B1C0FFEE
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                seed ^= (dist.get_rank() * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
+            if _dist.is_available() and _dist.is_initialized():
+                seed ^= (_dist.get_rank() * 0x9E3779B97F4A7C15) & 0x7FFFFFFFFFFFFFFF
         self.seed = torch.tensor([seed], dtype=torch.int64, device=device)
         self._offset = 0
 
@@ -147,13 +161,20 @@ def set_main_stream(stream):
     _main_streams[stream.device_index] = stream
 
 
+def _on_side_stream():
+    """The current stream when it is this device's side stream, else None."""
+    cur = torch.cuda.current_stream()
+    side = _side_streams.get(cur.device_index)
+    return cur if side is not None and cur == side else None
+
+
 def _xs_in(*ts):
     """A tape node running on the side stream reads tensors that the main stream allocated (incoming grads):
     tell the caching allocator, or the block could be handed to a main-stream kernel while we still read it.
     Forward needs none of this (fork/join fences on both sides of every layer); backward's engine-inserted
     syncs are one-directional."""
-    cur = torch.cuda.current_stream()
-    if _side_streams.get(cur.device_index) is not None and cur == _side_streams[cur.device_index]:
+    cur = _on_side_stream()
+    if cur is not None:
         for t in ts:
             if t is not None:
                 t.record_stream(cur)
@@ -161,13 +182,12 @@ def _xs_in(*ts):
 
 def _xs_out(*ts):
     """...and what it hands back (allocated on the side stream) is consumed on the main stream."""
-    cur = torch.cuda.current_stream()
-    if _side_streams.get(cur.device_index) is not None and cur == _side_streams[cur.device_index]:
-        main = _main_streams.get(cur.device_index)
-        if main is not None:
-            for t in ts:
-                if t is not None:
-                    t.record_stream(main)
+    cur = _on_side_stream()
+    main = _main_streams.get(cur.device_index) if cur is not None else None
+    if main is not None:
+        for t in ts:
+            if t is not None:
+                t.record_stream(main)
 
 
 _side_join_state = {}      # per device: nn.DataParallel drives one replica per device from its own thread
@@ -195,11 +215,10 @@ def _arm_side_join():
 def _side_to_main():
     """Explicit fence when a side-stream tape node hands its result to the main stream (belt and braces next to the
     autograd engine's own producer/consumer event)."""
-    cur = torch.cuda.current_stream()
-    if _side_streams.get(cur.device_index) is not None and cur == _side_streams[cur.device_index]:
-        main = _main_streams.get(cur.device_index)
-        if main is not None:
-            main.wait_stream(cur)
+    cur = _on_side_stream()
+    main = _main_streams.get(cur.device_index) if cur is not None else None
+    if main is not None:
+        main.wait_stream(cur)
 
 
 class WgradCollector:
@@ -241,43 +260,14 @@ class WgradCollector:
             cur.wait_stream(side)              # operands produced by the other direction's stream
             side.wait_stream(cur)
             run = side
+        # weights whose stages have the same row structure (all layer weights of both directions) form one group
+        groups = {}
+        for e in self.entries.values():
+            groups.setdefault(tuple(e["rows"]), []).append(
+                (e["C"], e["ldc"], e["colsum"], e["A"], e["lda"], e["B"], e["ldb"], e["M"], e["N"]))
         with torch.cuda.stream(run):
-            # weights whose stages have the same row structure (all layer weights of both directions) form one group
-            groups = {}
-            for e in self.entries.values():
-                groups.setdefault(tuple(e["rows"]), []).append(e)
-            for rows0, ents in groups.items():
-                grouped = (len(ents) > 1 and len(rows0) <= 16 and all(r % 16 == 0 for r in rows0)
-                           and all(e["M"] % 4 == 0 and e["N"] % 4 == 0 for e in ents))
-                if grouped:
-                    # one launch for every weight: each 128x128 tile of each gradient is owned by one workgroup over
-                    # the whole K = all stages' rows (no split-K, no atomics; see sbl_wgrad_group_f32)
-                    n, k = len(ents), len(rows0)
-                    need = _lib.load().sbl_wgrad_group_table_bytes(n)
-                    key = (run.device_index, run.cuda_stream, len(groups) > 1 and rows0)
-                    tab = _group_tables.get(key)
-                    if tab is None or tab.numel() < need:
-                        tab = _group_tables[key] = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=torch.device("cuda", run.device_index))
-                    pa = (_ct.c_void_p * (n * k))(*[t.data_ptr() for e in ents for t in e["A"]])
-                    pb = (_ct.c_void_p * (n * k))(*[t.data_ptr() for e in ents for t in e["B"]])
-                    call("sbl_wgrad_group_f32", n, k, (_ct.c_int * k)(*rows0), pa, (_ct.c_long * n)(*[e["lda"] for e in ents]), pb,
-                         (_ct.c_long * n)(*[e["ldb"] for e in ents]), (_ct.c_int * n)(*[e["M"] for e in ents]),
-                         (_ct.c_int * n)(*[e["N"] for e in ents]), (_ct.c_void_p * n)(*[e["C"].data_ptr() for e in ents]),
-                         (_ct.c_long * n)(*[e["ldc"] for e in ents]), (_ct.c_void_p * n)(*[_p(e["colsum"]) for e in ents]),
-                         tab.data_ptr(), tab.numel(), _s())
-                for e in ents:
-                    if not grouped:
-                        n = len(e["rows"])
-                        for i in range(0, n, 16):
-                            A, B, rows = e["A"][i:i + 16], e["B"][i:i + 16], e["rows"][i:i + 16]
-                            k = len(rows)
-                            pa = (_ct.c_void_p * k)(*[t.data_ptr() for t in A])
-                            pb = (_ct.c_void_p * k)(*[t.data_ptr() for t in B])
-                            pr = (_ct.c_int * k)(*rows)
-                            call("sbl_wgrad_seg_f32", k, pa, e["lda"], pb, e["ldb"], pr, e["M"], e["N"], _p(e["C"]), e["ldc"],
-                                 _p(e["colsum"]), _s())
-                    for t in e["A"] + e["B"]:
-                        t.record_stream(run)
+            for seg_rows, problems in groups.items():
+                wgrad_group(problems, seg_rows, run, _wgrad_seg)
         self.entries = {}
         self.flushes += 1
 
@@ -294,7 +284,6 @@ class WgradCollector:
             lst.remove(self)
 
 
-_group_tables = {}
 _armed = {}       # device index -> collectors with pending entries
 
 
@@ -304,8 +293,6 @@ def flush_deferred():
     for c in list(_armed.get(torch.cuda.current_device(), [])):
         c.flush()
 
-
-import threading as _threading
 
 _tls = _threading.local()      # the collector of the forward pass running on THIS thread (nn.DataParallel: one per replica)
 
@@ -364,7 +351,53 @@ def gemm2(M, N, K, A0, A1, lda, B0, B1, ldb, C0, C1, ldc, bias0=None, bias1=None
          ws.data_ptr(), WS_BYTES, _s())
 
 
-import ctypes as _ct
+_group_tables = {}      # (device, stream, row structure) -> descriptor table of sbl_wgrad_group_f32
+
+
+def _wgrad_seg(C, ldc, colsum, A, lda, B, ldb, M, N, seg_rows):
+    """One weight's C += sum_s A_s^T B_s, at most 16 segments per launch."""
+    for i in range(0, len(seg_rows), 16):
+        rows = seg_rows[i:i + 16]
+        k = len(rows)
+        call("sbl_wgrad_seg_f32", k, (_ct.c_void_p * k)(*[t.data_ptr() for t in A[i:i + 16]]), lda,
+             (_ct.c_void_p * k)(*[t.data_ptr() for t in B[i:i + 16]]), ldb, (_ct.c_int * k)(*rows), M, N, _p(C), ldc, _p(colsum), _s())
+
+
+def _wgrad_splitk(C, ldc, colsum, A, lda, B, ldb, M, N, seg_rows):
+    """One weight's C += A^T B over a single segment as a split-K GEMM."""
+    (A,), (B,), (rows,) = A, B, seg_rows
+    gemm(1, 0, M, N, rows, A, lda, B, ldb, C, ldc, accumulate=1, colsum=colsum)
+
+
+def wgrad_group(problems, seg_rows, run, per_weight):
+    """C += sum_s A_s^T B_s (colsum += column sums of A) for every problem (C, ldc, colsum, A_list, lda, B_list, ldb, M, N);
+    segment s of every problem has seg_rows[s] rows.  `run` is the current stream.  One sbl_wgrad_group_f32 launch for all
+    of them - each 128x128 tile of each gradient is owned by one workgroup over the whole K = all segments' rows, no split-K,
+    no atomics - when the kernel takes them (several problems, at most 16 segments of a multiple of 16 rows, M and N
+    multiples of 4); else per_weight(*problem, seg_rows) for each."""
+    n, k = len(problems), len(seg_rows)
+    if n > 1 and k <= 16 and all(r % 16 == 0 for r in seg_rows) and all(p[7] % 4 == 0 and p[8] % 4 == 0 for p in problems):
+        need = _lib.load().sbl_wgrad_group_table_bytes(n)
+        # one table per row structure: two grouped launches in flight on one stream never share one
+        key = (run.device_index, run.cuda_stream, tuple(seg_rows))
+        tab = _group_tables.get(key)
+        if tab is None or tab.numel() < need:
+            if len(_group_tables) >= 64:      # (on the per-stage tape the row structure follows the coin pattern)
+                _group_tables.clear()
+            tab = _group_tables[key] = torch.empty(max(need, 1 << 16), dtype=torch.uint8, device=torch.device("cuda", run.device_index))
+        col = lambda i, ct: (ct * n)(*[p[i] for p in problems])      # noqa: E731
+        call("sbl_wgrad_group_f32", n, k, (_ct.c_int * k)(*seg_rows),
+             (_ct.c_void_p * (n * k))(*[t.data_ptr() for p in problems for t in p[3]]), col(4, _ct.c_long),
+             (_ct.c_void_p * (n * k))(*[t.data_ptr() for p in problems for t in p[5]]), col(6, _ct.c_long),
+             col(7, _ct.c_int), col(8, _ct.c_int), (_ct.c_void_p * n)(*[p[0].data_ptr() for p in problems]), col(1, _ct.c_long),
+             (_ct.c_void_p * n)(*[_p(p[2]) for p in problems]), tab.data_ptr(), tab.numel(), _s())
+    else:
+        for p in problems:
+            per_weight(*p, seg_rows)
+    for p in problems:
+        for t in p[3] + p[5]:
+            t.record_stream(run)
+
 
 _seg_arrays = {}
 
@@ -389,9 +422,6 @@ def _gbuf(p):
         return None
     return getattr(p, "_sbl_grad", None)
 
-
-import functools as _functools
-import weakref as _weakref
 
 _flat_models = _weakref.WeakSet()
 
@@ -1146,7 +1176,6 @@ def _pack_entry_alive(e):
 def packed_conv_weight(w, need_dg, stats):
     """(w_ohwi, w_dg) for an OIHW convolution weight; `stats` (fp64, 2*Cout, or None) is zero-filled for the caller either
     by the pack launch (as before) or, on a cache hit, here."""
-    import weakref
     Cout, Cin, KH, KW = w.shape
     dev = w.device
     e = _packed.get(id(w)) if PACK_CACHE else None
@@ -1161,7 +1190,7 @@ def packed_conv_weight(w, need_dg, stats):
     call("sbl_conv_weight_pack", _p(w.detach().contiguous()), _p(w_ohwi), _p(w_dg), Cout, Cin, KH, KW, _p(stats),
          stats.numel() if stats is not None else 0, _s())
     if PACK_CACHE:
-        _packed[id(w)] = {"ref": weakref.ref(w), "shape": tuple(w.shape), "key": _pack_key(w), "ohwi": w_ohwi, "dg": w_dg}
+        _packed[id(w)] = {"ref": _weakref.ref(w), "shape": tuple(w.shape), "key": _pack_key(w), "ohwi": w_ohwi, "dg": w_dg}
         if len(_packed) > 256:
             for k in [k for k, v in _packed.items() if not _pack_entry_alive(v)]:
                 del _packed[k]
@@ -1234,6 +1263,17 @@ class StemFn(torch.autograd.Function):
         return None, dw.view(64, 1, 5, 7, 7), dgamma, dbeta, None, None, None, None, None, None
 
 
+def _dgrad_weight(w, w_dg):
+    """The [Cin][kh][kw][Cout] image of an OIHW weight that the input-gradient kernels read: the one forward kept, or packed
+    now (forward ran without needing an input gradient)."""
+    if w_dg is None:
+        Cout, Cin, KH, KW = w.shape
+        w_ohwi = torch.empty(Cout, KH, KW, Cin, device=w.device, dtype=torch.float32)
+        w_dg = torch.empty(Cin, KH, KW, Cout, device=w.device, dtype=torch.float32)
+        call("sbl_conv_weight_pack", _p(w.contiguous()), _p(w_ohwi), _p(w_dg), Cout, Cin, KH, KW, None, 0, _s())
+    return w_dg
+
+
 class ConvBNFn(torch.autograd.Function):
     """conv (3x3 pad 1 | 1x1 pad 0, bias-free) -> BatchNorm2d -> [+ residual] -> [ReLU] on NHWC activations;
     video_frontend.py:28-41,69-71.  The BN batch statistics are reduced in the conv epilogue."""
@@ -1258,13 +1298,7 @@ class ConvBNFn(torch.autograd.Function):
         # the step's pooled memset (or are zeroed by the pack launch / a fill when the pool is not armed).
         # (Measured and not kept in round 2: all 19 packs on the side stream while the stem runs - same-box A/B 32.94 vs
         # 32.72 ms, the fork/join and the contention with the stem cost more than the 10 us per convolution they take off.)
-        stats = None
-        pooled_stats = False
-        if training:
-            stats = zero_pool_take(dev, (2 * Cout,), torch.float64)
-            pooled_stats = stats is not None
-            if not pooled_stats:
-                stats = torch.empty(2 * Cout, device=dev, dtype=torch.float64)
+        stats, pooled_stats = _zeros_or_empty(dev, (2 * Cout,), torch.float64) if training else (None, False)
         w_ohwi, w_dg = packed_conv_weight(w, training and ctx.needs_input_grad[0], None if pooled_stats else stats)
         conv = torch.empty(NIMG, Ho, Wo, Cout, device=dev, dtype=torch.float32)
         mean = torch.empty(Cout, device=dev, dtype=torch.float32)
@@ -1358,18 +1392,12 @@ class ConvBNFn(torch.autograd.Function):
         if ctx.needs_input_grad[0] and role == "ds" and not ctl["link"].get("main_done"):
             # 1x1 / stride-2: the gradient lives on the even/even pixels; hand the compact form to conv1's epilogue (this node
             # was created after conv1, so the engine runs it first) instead of a zero-filled full-size tensor + autograd add
-            if w_dg is None:
-                w_ohwi = torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32)
-                w_dg = torch.empty(Cin, KH, KW, Cout, device=dev, dtype=torch.float32)
-                call("sbl_conv_weight_pack", _p(w.contiguous()), _p(w_ohwi), _p(w_dg), Cout, Cin, KH, KW, None, 0, _s())
+            w_dg = _dgrad_weight(w, w_dg)
             dxc = torch.empty(NIMG, (H + 1) // 2, (W + 1) // 2, Cin, device=dev, dtype=torch.float32)
             call("sbl_conv1x1s2_dgrad_compact", _p(dconv), _p(w_dg), _p(dxc), NIMG, H, W, Cin, Cout, _workspace().data_ptr(), WS_BYTES, _s())
             ctl["link"]["dx_ds"] = dxc
         elif ctx.needs_input_grad[0]:
-            if w_dg is None:
-                w_ohwi = torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32)
-                w_dg = torch.empty(Cin, KH, KW, Cout, device=dev, dtype=torch.float32)
-                call("sbl_conv_weight_pack", _p(w.contiguous()), _p(w_ohwi), _p(w_dg), Cout, Cin, KH, KW, None, 0, _s())
+            w_dg = _dgrad_weight(w, w_dg)
             dx = torch.empty_like(x)
             bi = ctx.box_in
             if role == "conv1":
@@ -1378,13 +1406,9 @@ class ConvBNFn(torch.autograd.Function):
                 link["main_done"] = True
                 prev = ctl.get("prev")
                 fuse = prev is not None and addend is not None and prev.get("act") == x.data_ptr()
-                nsums = None
                 if fuse:
                     two = prev.get("conv2") is not None
-                    nsums = zero_pool_take(dev, ((4 if two else 2) * Cin,), torch.float64)
-                    pooled = nsums is not None
-                    if not pooled:
-                        nsums = torch.empty((4 if two else 2) * Cin, device=dev, dtype=torch.float64)
+                    nsums, pooled = _zeros_or_empty(dev, ((4 if two else 2) * Cin,), torch.float64)
                     call("sbl_conv2d_dgrad_fused", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
                          _workspace().data_ptr(), WS_BYTES, _p(addend), _p(x), _p(prev["conv"]), _p(prev["mean"]), _p(prev["invstd"]),
                          _p(prev.get("conv2")), _p(prev.get("mean2")), _p(prev.get("invstd2")), _p(nsums), int(pooled), _s())
@@ -1393,10 +1417,7 @@ class ConvBNFn(torch.autograd.Function):
                     call("sbl_conv2d_dgrad_fused", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
                          _workspace().data_ptr(), WS_BYTES, _p(addend), None, None, None, None, None, None, None, None, 0, _s())
             elif bi is not None and bi.get("conv") is not None:
-                nsums = zero_pool_take(dev, (2 * Cin,), torch.float64)
-                pooled = nsums is not None
-                if not pooled:
-                    nsums = torch.empty(2 * Cin, device=dev, dtype=torch.float64)
+                nsums, pooled = _zeros_or_empty(dev, (2 * Cin,), torch.float64)
                 call("sbl_conv2d_dgrad_bnstats", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
                      _workspace().data_ptr(), WS_BYTES, _p(x), _p(bi["conv"]), _p(bi["mean"]), _p(bi["invstd"]), _p(nsums), int(pooled), _s())
                 bi["sums"], bi["dx_ptr"] = nsums, dx.data_ptr()
@@ -1412,10 +1433,7 @@ class ConvBNFn(torch.autograd.Function):
             side = side_stream(dev)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                dw_ohwi = zero_pool_take(dev, (Cout, KH, KW, Cin), torch.float32)
-                pooled = dw_ohwi is not None
-                if not pooled:
-                    dw_ohwi = torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32)
+                dw_ohwi, pooled = _zeros_or_empty(dev, (Cout, KH, KW, Cin), torch.float32)
                 call("sbl_conv2d_wgrad", _p(x), _p(dconv), _p(dw_ohwi), NIMG, H, W, Cin, Cout, KH, KW, stride, pad, int(pooled), _s())
                 call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(gw), Cout, Cin, KH, KW, 1, _s())
             x.record_stream(side)
@@ -1424,9 +1442,6 @@ class ConvBNFn(torch.autograd.Function):
             return dx, None, dgamma, dbeta, None, None, dres_ret, None, None, None, None, None, None, None, None, None
         dw_ohwi = torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32)
         call("sbl_conv2d_wgrad", _p(x), _p(dconv), _p(dw_ohwi), NIMG, H, W, Cin, Cout, KH, KW, stride, pad, 0, _s())
-        if gw is not None:
-            call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(gw), Cout, Cin, KH, KW, 1, _s())
-            return dx, None, dgamma, dbeta, None, None, dres_ret, None, None, None, None, None, None, None, None, None
         dw = torch.empty_like(w)
         call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(dw), Cout, Cin, KH, KW, 0, _s())
         return dx, dw, dgamma, dbeta, None, None, dres_ret, None, None, None, None, None, None, None, None, None
@@ -1468,14 +1483,13 @@ def preprocess_clips(frames_u8, y1, x1, flip, src_frame, Tout=30, crop=(88, 88),
     """Device input pipeline (SBL/data_gen.py:276-296 + cvtransforms.py): uint8 (N,Tin,Hin,Win) grayscale frames ->
     normalised, cropped, flipped, frame-mapped, zero-padded fp32 clips (N,Tout,Hc,Wc) in one kernel.  y1/x1/flip:
     int32 (N,) device tensors; src_frame: int32 (N,Tout), -1 = zero frame."""
-    import numpy as np
     _need_cuda(frames_u8, y1, x1, flip, src_frame)
     assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     N, Tin, Hin, Win = frames_u8.shape
     key = (frames_u8.device.index, mean, std)
     lut = _LUT.get(key)
     if lut is None:   # float32((v/255. - mean)/std) in double, exactly the reference's numpy arithmetic
-        lut = _LUT[key] = torch.from_numpy(((np.arange(256, dtype=np.float64) / 255. - mean) / std).astype(np.float32)).to(frames_u8.device)
+        lut = _LUT[key] = torch.from_numpy(((_np.arange(256, dtype=_np.float64) / 255. - mean) / std).astype(_np.float32)).to(frames_u8.device)
     out = torch.empty(N, Tout, crop[0], crop[1], device=frames_u8.device, dtype=torch.float32)
     call("sbl_preprocess_clips", _p(frames_u8), _p(out), _p(lut), _p(y1.contiguous()), _p(x1.contiguous()), _p(flip.contiguous()),
          _p(src_frame.contiguous()), N, Tin, Hin, Win, Tout, crop[0], crop[1], _s())

@@ -13,6 +13,19 @@ from .module import PositionalEncoding, PositionwiseFeedForward, mask_rows
 IGNORE_ID = config.IGNORE_ID
 
 
+def stages_of(coins, maxlen):
+    """(first step, last step) of every stage: a stage is a maximal run of steps whose input tokens are known when it
+    starts, i.e. it ends with the first step whose coin says "feed back the own argmax" (or with the last step)."""
+    stages, i = [], 0
+    while i < maxlen:
+        j = i
+        while j < maxlen - 1 and not coins[j]:
+            j += 1
+        stages.append((i, j))
+        i = j + 1
+    return stages
+
+
 class Decoder(nn.Module):
     ''' Two n_layers-deep decoders, left-to-right and right-to-left, that attend to the same encoder output and swap
     information after every layer; 16 greedy / teacher-forced steps each (decoder.py:16-191, 301-385).
@@ -31,6 +44,10 @@ class Decoder(nn.Module):
         results are identical: every row-wise op is unchanged and attention / fusion / embedding work per segment.
         `batch_teacher_runs = False` restores the one-stage-per-step schedule (also used by greedy inference,
         where every coin is "own argmax").
+    A training forward takes one of two paths that compute the same numbers.  With persistent gradient buffers
+    (dp.FlatModel) and host coins, the 16 steps are ONE autograd node with a single fixed launch sequence and a backward
+    batched over all steps (decoder_stages.py; its supported() lists the conditions).  Otherwise, and for inference, `_run`
+    builds the per-stage tape of ops.* Functions.
     Set `self.coins_dev` to a device int32[16] tensor to take the coins from device memory (one captured hipGraph
     for every coin pattern; implies the per-step schedule), or `self.coins_host` to a list of 16 bools to fix them.
     '''
@@ -73,7 +90,6 @@ class Decoder(nn.Module):
         self.tgt_word_prj_r2l = nn.Linear(512, 58, bias=False)
 
         self.batched_backward = True     # one stage-batched backward over all 16 steps (decoder_stages.py) when possible
-        self.merge_directions = True     # ... whose forward runs both directions in shared launches (sbl_*2_* entry points)
         self.two_streams = True          # run the two directions' layers on two HIP streams (joined before each fusion)
         self.batch_teacher_runs = True   # batch the steps of a teacher-forced run (see class docstring)
         self.coins_dev = None            # optional device int32[16]: 1 = feed own argmax (graph replay, per-step schedule)
@@ -122,6 +138,21 @@ class Decoder(nn.Module):
         stack = self.layer_stack_l2r if direction == 0 else self.layer_stack_r2l
         return [first] + list(stack)
 
+    def _draw_coins(self, teacher_mode):
+        """The coins of one forward, True = feed back the own argmax after that step (kept in last_coins): all True for
+        greedy inference; None when they live on the device (coins_dev); coins_host if set; else one draw per step in the
+        order of decoder.py:176."""
+        if not teacher_mode:
+            coins = [True] * config.MAX_DECODE_LEN
+        elif self.coins_dev is not None:
+            coins = None
+        elif self.coins_host is not None:
+            coins = [bool(c) for c in self.coins_host]
+        else:
+            coins = [random.random() > config.TEACHER_COIN_THRESHOLD for _ in range(config.MAX_DECODE_LEN)]
+        self.last_coins = coins
+        return coins
+
     def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode):
         """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383)."""
         maxlen = config.MAX_DECODE_LEN
@@ -156,29 +187,11 @@ class Decoder(nn.Module):
         golds = (gold_l2r, gold_r2l)
         outs = ([None] * maxlen, [None] * maxlen)
 
-        # ---- coins (True = feed back the own argmax after that step)
-        dev_coins = teacher_mode and self.coins_dev is not None
-        if not teacher_mode:
-            coins = [True] * maxlen
-        elif dev_coins:
-            coins = None
-        elif self.coins_host is not None:
-            coins = [bool(c) for c in self.coins_host]
-        else:   # decoder.py:176, one draw per step, same order
-            coins = [random.random() > config.TEACHER_COIN_THRESHOLD for _ in range(maxlen)]
-        self.last_coins = coins
-
-        # ---- stages: maximal runs of steps whose input tokens are known when the run starts
+        coins = self._draw_coins(teacher_mode)
         if coins is None or not self.batch_teacher_runs:
             stages = [(i, i) for i in range(maxlen)]
         else:
-            stages, i = [], 0
-            while i < maxlen:
-                j = i
-                while j < maxlen - 1 and not coins[j]:
-                    j += 1
-                stages.append((i, j))
-                i = j + 1
+            stages = stages_of(coins, maxlen)
             for k in range(maxlen):              # teacher-forced tokens are known up front
                 if not coins[k]:
                     for d in (0, 1):
@@ -239,15 +252,10 @@ class Decoder(nn.Module):
         else:
             ys_in_pad_l2r, ys_out_pad_l2r = self.preprocess(padded_input_l2r.to(dev))
             ys_in_pad_r2l, ys_out_pad_r2l = self.preprocess(padded_input_r2l.to(dev))
-        if decoder_stages.supported(self, encoder_outputs):
-            # same coins, same order as _run / decoder.py:176
-            if self.coins_host is not None:
-                coins = [bool(c) for c in self.coins_host]
-            else:
-                coins = [random.random() > config.TEACHER_COIN_THRESHOLD for _ in range(config.MAX_DECODE_LEN)]
-            self.last_coins = coins
-            pl, pr = decoder_stages.DecoderStagesFn.apply(encoder_outputs, self.tgt_word_emb.weight, self, ys_out_pad_l2r,
-                                                          ys_out_pad_r2l, coins)
+        layers = decoder_stages.supported(self, encoder_outputs)
+        if layers is not None:
+            pl, pr = decoder_stages.DecoderStagesFn.apply(encoder_outputs, self.tgt_word_emb.weight, self, layers, ys_out_pad_l2r,
+                                                          ys_out_pad_r2l, self._draw_coins(True))
             return pl, ys_out_pad_l2r, pr, ys_out_pad_r2l
         outs, _ = self._run(encoder_outputs, ys_out_pad_l2r, ys_out_pad_r2l, teacher_mode=True)
         return torch.stack(outs[0], 1), ys_out_pad_l2r, torch.stack(outs[1], 1), ys_out_pad_r2l

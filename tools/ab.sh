@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of bench.py variants (box-to-box spread is +-2-3 %, far above most single changes): runs every variant
 # ROUNDS times, interleaved, and prints ms_per_step per run.  GPU box, repo root:
-#   tools/ab.sh 3 "" "--set fuse_stage_io=0" "--no-pack-cache"
+#   tools/ab.sh 3 "" "--set batched_backward=0" "--no-pack-cache"
 rounds=$1; shift
 for r in $(seq $rounds); do
   for v in "$@"; do
