@@ -354,6 +354,39 @@ int sbl_smoothed_ce_fwd(const float* pred, const int64_t* gold, float* out3, int
 int sbl_smoothed_ce_bwd(const float* pred, const int64_t* gold, const float* out3, const float* gscale, float* dpred,
                         int R, int C, float eps, int ignore_id, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- validation scoring (WER / PER of greedy decodes)
+ * SBL/train.py:251-276 with per_compute / wer_compute (:28-42), both directions of a batch in one launch, counters kept on
+ * the device.  Per direction and sample, with ys the (Ly,) row of recognize (Ly = 17, column 0 is sos) and gold the (To,)
+ * target row, To <= 15:
+ *   g = the entries of gold not in {sos, eos, ignore}, in order; c = len(g)                              (train.py:252-253)
+ *   p = the entries of ys[:c+1] not in {sos, eos, ignore}, in order (an eos is stripped where it stands)  (train.py:254)
+ *   dist = Levenshtein distance of p and g over ids, unit costs (editdistance.eval); PER of the sample = dist / c
+ *   word_err = 0 if p and g spell the same string, else 1 (the reference joins the names without a separator, so its
+ *   wer_compute is 0 or 1 per sample).  names == NULL: the spelling of an id is the id.  Else names[id], id < n_names, is
+ *   one 64-bit word: bits 56..58 the length L <= 7, the low L bytes the characters, first character most significant,
+ *   all other bits 0 (the caller packs and checks it); a kept id outside [0, n_names) spells the empty string.
+ * Deviations from the reference: (a) every sample counts once (train.py:262-263 extends the WER lists inside the sample
+ * loop, so sample j of a batch of B enters the reference's WER mean B - j times); (b) a sample with c = 0 (a division by
+ * zero there) is counted in n_empty and left out of every other counter; (c) rows n >= valid_rows[0] (device int32, NULL =
+ * all N rows: the short last batch of a replayed graph) are ignored.
+ * acc: uint64 (2, SBL_SCORE_COUNTERS), direction-major, ADDED to (the caller zeroes it once per epoch): n_scored, n_empty,
+ * n_word_err, sum of dist, sum of c, then dist_by_len[16] and count_by_len[16] (sum of dist / number of scored samples per
+ * gold length c).  mean(dist / c) = sum_c dist_by_len[c] / c / n_scored, formed in fp64 by the reader.  All state is
+ * integer: the result does not depend on the order of the atomics and sums exactly across calls, replays and ranks.
+ * per_sample: NULL, or int32 (2, 3, N) = per direction dist, c, word_err of every row (-1 on ignored rows).  N == 0 is a
+ * successful no-op. */
+#define SBL_SCORE_N_SCORED 0
+#define SBL_SCORE_N_EMPTY 1
+#define SBL_SCORE_N_WORD_ERR 2
+#define SBL_SCORE_SUM_DIST 3
+#define SBL_SCORE_SUM_LEN 4
+#define SBL_SCORE_DIST_BY_LEN 5
+#define SBL_SCORE_COUNT_BY_LEN 21
+#define SBL_SCORE_COUNTERS 37
+int sbl_seq_score(const int64_t* ys_l2r, const int64_t* ys_r2l, int Ly, const int64_t* gold_l2r, const int64_t* gold_r2l,
+                  int To, int N, int64_t sos, int64_t eos, int64_t ignore, const uint64_t* names, int n_names,
+                  const int32_t* valid_rows, int32_t* per_sample, uint64_t* acc, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
  * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.

@@ -63,6 +63,7 @@ SIGNATURES = {
     "sbl_fusion_bwd": [P, P, P, P, I, I, I, P],
     "sbl_argmax_select": [P, L, P, L, P, L, I, I, P, I, I, P],
     "sbl_decoder_preprocess": [P, P, P, P, P, P, I, I, I, L, L, L, P],
+    "sbl_seq_score": [P, P, I, P, P, I, I, L, L, L, P, I, P, P, P, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
     "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],

@@ -1494,3 +1494,119 @@ def preprocess_clips(frames_u8, y1, x1, flip, src_frame, Tout=30, crop=(88, 88),
     call("sbl_preprocess_clips", _p(frames_u8), _p(out), _p(lut), _p(y1.contiguous()), _p(x1.contiguous()), _p(flip.contiguous()),
          _p(src_frame.contiguous()), N, Tin, Hin, Win, Tout, crop[0], crop[1], _s())
     return out
+
+
+# --------------------------------------------------------------------------- #
+# validation scoring (sbl_seq_score)
+# --------------------------------------------------------------------------- #
+SCORE_COUNTERS = 37          # include/sbl_hip.h, SBL_SCORE_*: the counters of one direction
+SCORE_N_SCORED, SCORE_N_EMPTY, SCORE_N_WORD_ERR, SCORE_SUM_DIST, SCORE_SUM_LEN = range(5)
+SCORE_DIST_BY_LEN, SCORE_COUNT_BY_LEN = 5, 21
+SCORE_MAX_TO, SCORE_WINDOW = 15, 16
+
+
+def pack_names(names):
+    """The name table of sbl_seq_score from a list of `vocab` short strings (one per token id): int64 (vocab,) CPU tensor,
+    entry = length << 56 | the characters as a big-endian integer.  Checked here, on the host: ASCII without NUL, at most
+    7 bytes each."""
+    words = []
+    for i, s in enumerate(names):
+        try:
+            b = s.encode("ascii")
+        except (UnicodeEncodeError, AttributeError):
+            raise ValueError("name %d (%r) is not an ASCII string" % (i, s))
+        if len(b) > 7 or 0 in b:
+            raise ValueError("name %d (%r): at most 7 bytes, none of them NUL" % (i, s))
+        words.append(len(b) << 56 | int.from_bytes(b, "big"))
+    if not words:
+        raise ValueError("empty name table")
+    return torch.tensor(words, dtype=torch.int64)
+
+
+def _spelling_cpu(tok, kept, names):
+    """(N, 112) uint8: the concatenated spelling of the kept ids of every row, zero padded (torch form of the kernel's rule:
+    an id outside the table spells nothing)."""
+    N, Wd = tok.shape
+    inside = kept & (tok >= 0) & (tok < names.numel())
+    w = names[torch.where(inside, tok, torch.zeros_like(tok))]
+    length = torch.where(inside, (w >> 56) & 7, torch.zeros_like(w))
+    q = torch.arange(7)
+    ch = (w.unsqueeze(2) >> (8 * (length.unsqueeze(2) - 1 - q)).clamp(min=0)) & 0xFF      # (N, Wd, 7): character q
+    valid = (q < length.unsqueeze(2)).reshape(N, Wd * 7)
+    order = torch.argsort((~valid).to(torch.int8), dim=1, stable=True)                    # stable compaction to the left
+    out = torch.gather(torch.where(valid, ch.reshape(N, Wd * 7), torch.zeros((), dtype=torch.int64)), 1, order)
+    pad = out.new_zeros(N, SCORE_WINDOW * 7)
+    pad[:, :Wd * 7] = out
+    return pad.to(torch.uint8)
+
+
+def _seq_score_cpu(ys, gold, sos, eos, ignore, names):
+    """(dist, c, word_err) int64 (N,) of one direction: the definition of sbl_seq_score in vectorised torch (the kernel's
+    dynamic program: stripped target entries are transparent columns, stripped predictions leave the row unchanged)."""
+    N, To = gold.shape
+    p = ys[:, :SCORE_WINDOW]
+    gk = (gold != sos) & (gold != eos) & (gold != ignore)
+    c = gk.sum(1)
+    pk = (p != sos) & (p != eos) & (p != ignore) & (torch.arange(p.size(1)).unsqueeze(0) <= c.unsqueeze(1))
+    D = torch.cat([c.new_zeros(N, 1), gk.cumsum(1)], 1)
+    for i in range(p.size(1)):
+        cols = [D[:, 0] + 1]
+        for j in range(1, To + 1):
+            cell = torch.minimum(torch.minimum(D[:, j], cols[-1]) + 1, D[:, j - 1] + (p[:, i] != gold[:, j - 1]).long())
+            cols.append(torch.where(gk[:, j - 1], cell, cols[-1]))
+        D = torch.where(pk[:, i:i + 1], torch.stack(cols, 1), D)
+    dist = D[:, To]
+    if names is None:
+        werr = (dist != 0).long()
+    else:
+        werr = (_spelling_cpu(p, pk, names) != _spelling_cpu(gold, gk, names)).any(1).long()
+    return dist, c, werr
+
+
+def seq_score(ys_l2r, ys_r2l, gold_l2r, gold_r2l, acc, sos_id, eos_id, ignore_id, names=None, valid_rows=None, per_sample=None):
+    """Score one batch of greedy decodes against its targets, both directions, and ADD the counters to `acc`
+    (include/sbl_hip.h, sbl_seq_score: the definition, the reference lines and the three deviations).
+    ys_*: int64 (N, Ly) rows of Transformer.recognize; gold_*: int64 (N, To <= 15) IGNORE_ID-padded targets; acc: int64
+    (2, SCORE_COUNTERS); names: None or the int64 table of pack_names on the same device; valid_rows: None or int32[1] (rows
+    at or beyond it are ignored); per_sample: None or int32 (2, 3, N), filled with dist / c / word_err per direction.
+    On the GPU: one launch, no sync, no allocation.  CPU tensors take the same definition in vectorised torch, so that it can
+    be pinned without a GPU; that is not a fallback of the GPU path, which raises without the library.  Returns acc."""
+    N, Ly = ys_l2r.shape
+    To = gold_l2r.size(1)
+    toks = (ys_l2r, ys_r2l, gold_l2r, gold_r2l)
+    if ys_r2l.shape != (N, Ly) or gold_l2r.shape != (N, To) or gold_r2l.shape != (N, To):
+        raise ValueError("seq_score: shapes %s" % ([tuple(t.shape) for t in toks],))
+    if not all(t.dtype == torch.int64 and t.is_contiguous() for t in toks):
+        raise ValueError("seq_score: token tensors must be contiguous int64")
+    if acc.shape != (2, SCORE_COUNTERS) or acc.dtype != torch.int64 or not acc.is_contiguous():
+        raise ValueError("seq_score: acc must be a contiguous int64 (2, %d) tensor" % SCORE_COUNTERS)
+    if names is not None and (names.dtype != torch.int64 or names.dim() != 1 or names.numel() < 1 or not names.is_contiguous()):
+        raise ValueError("seq_score: names must be the int64 table of pack_names")
+    if valid_rows is not None and (valid_rows.dtype != torch.int32 or valid_rows.numel() != 1):
+        raise ValueError("seq_score: valid_rows must be an int32[1] tensor")
+    if per_sample is not None and (per_sample.shape != (2, 3, N) or per_sample.dtype != torch.int32 or not per_sample.is_contiguous()):
+        raise ValueError("seq_score: per_sample must be a contiguous int32 (2, 3, %d) tensor" % N)
+    every = toks + (acc,) + tuple(t for t in (names, valid_rows, per_sample) if t is not None)
+    if any(t.device != acc.device for t in every):
+        raise ValueError("seq_score: tensors on different devices")
+    if acc.is_cuda:
+        call("sbl_seq_score", _p(ys_l2r), _p(ys_r2l), Ly, _p(gold_l2r), _p(gold_r2l), To, N, sos_id, eos_id, ignore_id, _p(names),
+             0 if names is None else names.numel(), _p(valid_rows), _p(per_sample), _p(acc), _s())
+        return acc
+    if not 1 <= To <= SCORE_MAX_TO:
+        raise ValueError("seq_score: target width To=%d outside 1..%d" % (To, SCORE_MAX_TO))
+    live = torch.arange(N) < (N if valid_rows is None else min(max(int(valid_rows[0]), 0), N))
+    for d, (ys, gold) in enumerate(((ys_l2r, gold_l2r), (ys_r2l, gold_r2l))):
+        dist, c, werr = _seq_score_cpu(ys, gold, sos_id, eos_id, ignore_id, names)
+        if per_sample is not None:
+            per_sample[d] = torch.where(live, torch.stack((dist, c, werr)), torch.full((), -1, dtype=torch.int64)).to(torch.int32)
+        scored = live & (c > 0)
+        a = acc[d]
+        a[SCORE_N_SCORED] += scored.sum()
+        a[SCORE_N_EMPTY] += (live & (c == 0)).sum()
+        a[SCORE_N_WORD_ERR] += werr[scored].sum()
+        a[SCORE_SUM_DIST] += dist[scored].sum()
+        a[SCORE_SUM_LEN] += c[scored].sum()
+        a[SCORE_DIST_BY_LEN:SCORE_DIST_BY_LEN + 16].index_add_(0, c[scored], dist[scored])
+        a[SCORE_COUNT_BY_LEN:SCORE_COUNT_BY_LEN + 16].index_add_(0, c[scored], torch.ones_like(c[scored]))
+    return acc

@@ -1,0 +1,76 @@
+"""Validation metrics kept on the device: WER / PER of greedy decodes (the scoring of valid_lrw / valid_lrw1000,
+SBL/train.py:212-362 and SBL/test.py:146-300, with wer_compute / per_compute of train.py:28-42).
+
+Per direction and sample, with `ys` the (17,) row Transformer.recognize returns and `gold` the IGNORE_ID-padded target:
+  g = gold without sos / eos / IGNORE_ID, c = len(g);  p = ys[:c+1] without sos / eos / IGNORE_ID (an eos is stripped where
+  it stands; the row is not cut at the first eos);  dist = Levenshtein(p, g) over ids;  PER = mean of dist / c;
+  word error = 0 if p and g spell the same string, else 1, and WER = its mean.  The reference joins the phoneme NAMES without
+  a separator before it compares, so two different id sequences can be the same word ("a" + "n" against "an"): give the
+  meter the list of names (one short ASCII string per id) to compare spellings; without it the ids are compared.
+
+Deviations from the reference, on purpose:
+  (a) every sample counts once (train.py:262-263 extends the WER lists inside the per-sample loop, so sample j of a batch
+      of B enters the reference's WER mean B - j times);
+  (b) a sample whose target is empty (c = 0: a division by zero in the reference) is counted in "n_empty" and left out of
+      every mean;
+  (c) rows at or beyond an optional `valid_rows` count are ignored (the short last batch of a replayed graph).
+
+Tokens never leave the device: an update is one launch of sbl_seq_score that adds to an integer accumulator, and only
+result() synchronises.  All state is integer, so a result is independent of the order of the atomics, identical between
+eager launches and graph replays, and sums exactly across ranks."""
+import torch
+
+from ._env import config, ops
+
+
+class ErrorRateMeter:
+    """Accumulates the scoring counters of both directions over an epoch.
+
+    names: None, or a list of `vocab` ASCII strings of at most 7 bytes (the spelling of every token id).
+    device: where the accumulator lives (and where update()'s tensors must be)."""
+
+    def __init__(self, names=None, device=None, sos_id=config.sos_id, eos_id=config.eos_id, ignore_id=config.IGNORE_ID):
+        self.device = torch.device(config.device if device is None else device)
+        self.sos_id, self.eos_id, self.ignore_id = int(sos_id), int(eos_id), int(ignore_id)
+        self.names = None if names is None else ops.pack_names(names).to(self.device)
+        self.acc = torch.zeros(2, ops.SCORE_COUNTERS, dtype=torch.int64, device=self.device)
+
+    def update(self, ys_l2r, ys_r2l, gold_l2r, gold_r2l, valid_rows=None):
+        """Score one batch and add it: one launch on the current stream, no sync, no allocation (capturable).
+        valid_rows: None or a device int32[1]; rows at or beyond it are ignored."""
+        ops.seq_score(ys_l2r, ys_r2l, gold_l2r, gold_r2l, self.acc, self.sos_id, self.eos_id, self.ignore_id,
+                      names=self.names, valid_rows=valid_rows)
+
+    def all_reduce(self, group=None):
+        """Sum the counters over the ranks of a torch.distributed group (RCCL on the GPU, gloo on CPU tensors): every
+        rank then reads the result of the union of all ranks' samples."""
+        torch.distributed.all_reduce(self.acc, op=torch.distributed.ReduceOp.SUM, group=group)
+
+    def reset(self):
+        self.acc.zero_()
+
+    def result(self):
+        """The one synchronisation: read the counters and form the means in fp64.
+        {"l2r_wer", "l2r_per", "r2l_wer", "r2l_per"}: means over the scored samples (nan when there are none);
+        "n", "n_empty": scored / empty-target samples of the l2r direction ("r2l_n", "r2l_n_empty": of the other one);
+        "l2r_per_corpus", "r2l_per_corpus": sum of distances over sum of target lengths."""
+        a = self.acc.cpu().tolist()
+        nan = float("nan")
+        out = {}
+        for d, tag in enumerate(("l2r", "r2l")):
+            n = a[d][ops.SCORE_N_SCORED]
+            by_len = a[d][ops.SCORE_DIST_BY_LEN:ops.SCORE_DIST_BY_LEN + 16]
+            out[tag + "_wer"] = a[d][ops.SCORE_N_WORD_ERR] / n if n else nan
+            out[tag + "_per"] = sum(by_len[c] / c for c in range(1, 16)) / n if n else nan
+            out[tag + "_per_corpus"] = a[d][ops.SCORE_SUM_DIST] / a[d][ops.SCORE_SUM_LEN] if n else nan
+            out["n" if d == 0 else "r2l_n"] = n
+            out["n_empty" if d == 0 else "r2l_n_empty"] = a[d][ops.SCORE_N_EMPTY]
+        return out
+
+
+def wer_per(ys_l2r, ys_r2l, gold_l2r, gold_r2l, names=None):
+    """One-shot scoring of a batch: (l2r_wer, l2r_per, r2l_wer, r2l_per), the order valid_lrw returns (train.py:286)."""
+    meter = ErrorRateMeter(names, device=ys_l2r.device)
+    meter.update(ys_l2r, ys_r2l, gold_l2r, gold_r2l)
+    r = meter.result()
+    return r["l2r_wer"], r["l2r_per"], r["r2l_wer"], r["r2l_per"]

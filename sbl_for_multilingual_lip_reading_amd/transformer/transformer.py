@@ -35,3 +35,12 @@ class Transformer(nn.Module):
         """Greedy bidirectional decode of (N, T, H, W) crops: (ys_l2r, ys_r2l), int64 (N, 17)."""
         enc, _ = self._encode(input)
         return self.decoder.recognize_beam(enc)
+
+    def validate(self, padded_input, padded_target_l2r, padded_target_r2l, meter, valid_rows=None):
+        """One validation batch (the body of valid_lrw's loop, train.py:236-276): greedy decode, then score both directions
+        against the (N, To) IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device.  No host sync:
+        in eval() under torch.no_grad() the whole call is capturable as one hipGraph, like recognize; `valid_rows` (device
+        int32[1]) then masks the tail of a short last batch.  Returns the token tensors of recognize."""
+        ys_l2r, ys_r2l = self.recognize(padded_input)
+        meter.update(ys_l2r, ys_r2l, padded_target_l2r, padded_target_r2l, valid_rows=valid_rows)
+        return ys_l2r, ys_r2l
