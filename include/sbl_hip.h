@@ -13,8 +13,10 @@
  *     host read-back, so any sequence of calls can be captured into a hipGraph.
  *   - return 0 on success, otherwise a hipError_t value or SBL_ERR_INVALID (bad shape /
  *     alignment, checked on the host BEFORE any launch); text via sbl_last_error()
- *     (thread-local).  No global mutable state: safe from several host threads on distinct
- *     streams/devices (nn.DataParallel's threading model, SBL/train.py:115).
+ *     (thread-local).  Safe from several host threads on distinct streams/devices (nn.DataParallel's
+ *     threading model, SBL/train.py:115).  The only mutable state is a handful of process-wide settings, all
+ *     read when a launch is enqueued, so one thread's change reaches every thread's later launches: the
+ *     matrix-product precision, the two routing switches of sbl_set_tuning and the profile stamps.
  *   - activations of the visual trunk are NHWC ("channels last"): (image, h, w, c), image =
  *     n*T + t — the reference's transpose/contiguous/view (SBL/transformer/video_frontend.py:113-115)
  *     is folded into the layout.  Transformer tensors are row-major (B, L, 512).
@@ -63,26 +65,13 @@ int sbl_profile_last_kernel(void);
  * "exact split" holds for |x| >= 2^-110 or x == 0; residual planes of smaller magnitudes underflow bf16's range. */
 int sbl_set_matmul_precision(int terms);
 int sbl_get_matmul_precision(void);
-/* Measurement knobs (process-wide, read at enqueue time like the precision; results are the same either way).
- * knob 0: wave-group K split of the dense 64x64 split-bf16 tiles (512-thread workgroups), 1 = on (default), 0 = off;
- * knob 1: number of 64x64 output tiles from which a dense product takes 128x128 tiles (default 4096);
- * knob 2: largest tile count of a launch that takes the wave-group K split (default 320);
- * knob 3: stride-2 convolution weight gradients on 64x64 tiles (1, default) or by the general rule (0);
- * knob 4: workgroup target of their split-K (default 1536; 0 = the general rule);
- * knob 5: patch-resident 3x3 / stride-1 convolution kernel for the 22x22 and 11x11 trunk maps: 2 (default) swizzled 32-channel LDS rows,
- *         two workgroups per CU; 1 padded 64-channel rows, one workgroup per CU; 0 the per-tap gather kernels;
- * knob 6: cap on the workgroups of the grouped weight-gradient launch (0 = one per tile, default);
- * knob 7: position-major convolution weight gradients with Cout <= value on 64x64 tiles (default 512; 0 = 128x128 tiles);
- * knob 8: most images per tile of the patch-resident kernel (default 0 = as many as fit, i.e. two 11x11 maps; 1 = one,
- *         which leaves the 11x11 layer on the position-major kernels);
- * knob 9: patch-resident weight gradient of the 3x3 / stride-1 convolutions for maps of at least `value` pixels (default 30:
- *         the 22x22, 11x11 and 6x6 layers; 0 = the implicit-GEMM weight gradients everywhere);
- * knob 10 / 11: workgroup target (default 256) and largest split count (default 8) of the in-launch split-K of sbl_gemm2_f32;
- * knob 12: stem weight gradient with operands split once into LDS planes and transposed LDS reads (1, default: 635 us) or
- *          the split-per-use kernel (0: 801 us);
- * knob 13: phase ablation of that variant (measurement only: results are WRONG while it is non-zero);
- * knob 14: stem forward convolution with eight wavefronts (two tiles in flight) on one copy of the weight planes (1, default:
- *          434 us) or the four-wavefront kernel (0: 497 us). */
+/* Routing switches (process-wide, read at enqueue time like the precision).  Each chooses between two shipped kernel
+ * families for the 3x3 / stride-1 trunk convolutions in the split-bf16 modes; the suite uses them to run the second
+ * family on the large maps.  Any other knob, or a value a knob does not take, returns SBL_ERR_INVALID.
+ * knob 5: 2 (default) patch-resident forward / input-gradient kernel for the 22x22 and 11x11 trunk maps; 0 the per-tap
+ *         gather kernels;
+ * knob 9: patch-resident weight gradient for maps of at least `value` pixels (default 30: the 22x22, 11x11 and 6x6
+ *         layers; 0 = the implicit-GEMM weight gradients everywhere). */
 int sbl_set_tuning(int knob, int value);
 
 /* ---------------------------------------------------------------- dense GEMM / Linear

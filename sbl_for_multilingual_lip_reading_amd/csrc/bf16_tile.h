@@ -73,7 +73,7 @@ __device__ __forceinline__ bf16x8 bf_frag(const unsigned char* img, int rb, int 
     }
 }
 
-// SBL_ABL (tools/probes/tile_ablate.hip only; never set in the library build): bit 0 drops the MFMAs, bit 1 the LDS fragment
+// SBL_ABL (the tile-engine probe under tools/probes only; never set in the library build): bit 0 drops the MFMAs, bit 1 the LDS fragment
 // reads, bit 2 the split + LDS stores, bit 3 the global loads of the K loop - what each stage costs is the time that goes
 // away with it.
 #ifndef SBL_ABL

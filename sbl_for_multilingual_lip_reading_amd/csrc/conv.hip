@@ -7,15 +7,20 @@
 #include "conv_patch.h"
 #include "conv_patch_wgrad.h"
 
-int g_sbl_pm_wg64_maxm = 512;    // knob 7: position-major weight gradients with Cout <= this on 64x64 tiles (0 = always 128x128; same-box step
-                                 // A/B 0 / 128 / 256 / 512: 32.33 / 32.32 / 32.33 / 32.20 ms)
-int g_sbl_conv_patch = 2;        // sbl_set_tuning knob 5: patch-resident 3x3 / stride-1 kernel for the large maps (conv_patch.h): 0 off,
-                                 // 1 padded 64-channel rows (one workgroup per CU), 2 swizzled 32-channel rows (two per CU; default)
-int g_sbl_conv_patch_wgrad = 30;  // knob 9: patch-resident weight gradient (conv_patch_wgrad.h) for 3x3 / stride-1 maps of at least this many pixels (0 = off;
-                                 // same-box step A/B 0 / 100 / 30: 32.22 / 31.84 / 31.73 ms)
-int g_sbl_conv_patch_imgs = 0;   // knob 8: most images per tile of that kernel (0 = as many as fit: two 11x11 maps; 1 = single-image tiles only, i.e. layer 1 only)
-int g_sbl_wg_s2_small = 1;      // sbl_set_tuning knob 3: stride-2 weight gradients on 64x64 tiles (128 -> 256: 459 -> 335 us, 256 -> 512: 447 -> 400 us)
-int g_sbl_wg_target = 1536;     // knob 4: their workgroup target (0 = the default rule; same-box step A/B 32.44 / 32.34 / 32.29 ms for 128-tiles / 64-tiles / 64-tiles + 1536)
+SblRouting g_sbl_route = {2, 30};
+extern "C" int sbl_set_tuning(int knob, int value) {
+    SBL_REQUIRE(knob == 5 || knob == 9, "sbl_set_tuning: no knob %d; the two that remain are 5 (patch-resident 3x3 / stride-1 forward / input gradient: 2 on, "
+                "0 the per-tap gather kernels) and 9 (smallest map in pixels that takes the patch-resident weight gradient, 0 = never)", knob);
+    if (knob == 5) {
+        SBL_REQUIRE(value == 0 || value == 2, "sbl_set_tuning: knob 5 takes 2 (patch-resident kernels) or 0 (per-tap gather kernels), not %d", value);
+        g_sbl_route.conv_patch = value;
+    } else {
+        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
+        g_sbl_route.conv_patch_wgrad = value;
+    }
+    return 0;
+}
+
 static int check_conv(const char* who, int NIMG, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
     SBL_REQUIRE(NIMG > 0 && H > 0 && W > 0, "%s: bad image dims %d %d %d", who, NIMG, H, W);
     SBL_REQUIRE(Cin % 16 == 0 && Cout % 16 == 0 && Cin >= 16 && Cout >= 16, "%s: Cin=%d Cout=%d must be multiples of 16", who, Cin, Cout);
@@ -362,10 +367,8 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
     // otherwise, and 6 / 12 workgroups per CU so that the uneven last chunks and the atomic epilogues of one
     // workgroup hide behind the others (measured, tools/bench_conv.py: 465/477/511/515 us -> 411/355/437/453 us for
     // layers 1-4); chunks stay >= 256 pixels
-    constexpr int wg_tile = 0;
-    constexpr int wg_target_env = 0;
-    const bool big = wg_tile ? wg_tile == 128 : (M >= 128 && N >= 1152 && !(stride == 2 && g_sbl_wg_s2_small));
-    const int wg_target = wg_target_env ? wg_target_env : (g_sbl_wg_target > 0 && stride == 2 ? g_sbl_wg_target : (big ? 1536 : 3072));
+    const bool big = M >= 128 && N >= 1152 && !(stride == 2 && sbl_wg_s2_small);
+    const int wg_target = stride == 2 ? sbl_wg_s2_target : (big ? 1536 : 3072);
     SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_WGRAD)};
     if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && sbl_launch_conv_patch_wgrad(x, dy, dw, NIMG, H, W, Cin, Cout, sc.stamp, s)) {
         SBL_LAUNCH_CHECK("sbl_conv2d_wgrad(patch)");
@@ -382,7 +385,6 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
         EpiStore<2, false> e{dw, (long)N, nullptr, 0, nullptr, nullptr, 0};                                   \
         sbl_launch_gemm<DenseMC<BM, true>, ConvGatherMC<BN>, EpiStore<2, false>, BM, BN>(al, bl, e, M, N, K, splits, s, sc); \
     } while (0)
-    const int pm_wg_tile = (g_sbl_pm_wg64_maxm > 0 && M <= g_sbl_pm_wg64_maxm) ? 64 : 128;
     if (conv_pm_ok(Ho, Wo, KH, stride) && big && M >= 128 && Cin % 128 == 0) {
         // one tap per tile of the (tap, ci) axis: contract only over the pixels that tap can reach
 #define SBL_KPMW_(P) sbl_conv_pm_wgrad_kernel<DenseMCPM<T_>, ConvGatherMCPM<T_>, EpiStore<2, false>, T_, T_, P>
@@ -399,7 +401,7 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
         EpiStore<2, false> e{dw, (long)N, nullptr, 0, nullptr, nullptr, 0};                                   \
         SBL_PREC_LAUNCH(SBL_KPMW_, dim3(sbl_cdiv(M, T), sbl_cdiv(N, T), splits), s, al, bl, e, sc, M, N);     \
     } while (0)
-        if (pm_wg_tile == 64) SBL_CONV_WG_PM(64);
+        if (M <= sbl_pm_wg64_max_m) SBL_CONV_WG_PM(64);
         else SBL_CONV_WG_PM(128);
 #undef SBL_CONV_WG_PM
 #undef SBL_KPMW_

@@ -21,17 +21,14 @@
 #pragma once
 #include "mfma_gemm.h"
 
-// Two LDS layouts of a patch pixel / weight row (per plane):
-//   SW = false: 64 channels + 16 bytes of padding (144 B stride: conflict-free 16-byte reads); 162 KB at 11 x 22 pixels, ONE
-//               workgroup per CU.
-//   SW = true : 32 channels, no padding (64 B), the four 16-byte chunks of a row XOR-swizzled with bits 2-3 of the row index
-//               (consecutive rows then spread over all 64 banks): 72 KB, TWO workgroups per CU, so that one workgroup's patch
-//               staging and epilogue run under the other's MFMAs; twice the staging passes and barriers per 64 channels.
-#define SBL_CP_CKV(SW) ((SW) ? 32 : 64)
-#define SBL_CP_PIXBV(SW) ((SW) ? 64 : 144)
-template <bool SW>
+// LDS layout of a patch pixel / weight row (per plane): 32 channels, no padding (64 B), the four 16-byte chunks of a row
+// XOR-swizzled with bits 2-3 of the row index (consecutive rows then spread over all 64 banks): 72 KB at 11 x 22 pixels, TWO
+// workgroups per CU, so that one workgroup's patch staging and epilogue run under the other's MFMAs.  (Rows of 64 channels
+// + 16 bytes of padding - 162 KB, one workgroup per CU, half the staging passes and barriers - measured 228 against 190 us.)
+#define SBL_CP_CK 32         // channels per chunk
+#define SBL_CP_PIXB 64       // bytes of a patch pixel / weight row
 __device__ __forceinline__ int cp_addr(int row, int chunk) {      // byte offset of 16-byte chunk `chunk` of row `row` inside a plane
-    return SW ? row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4) : row * 144 + (chunk << 4);
+    return row * SBL_CP_PIXB + ((chunk ^ ((row >> 2) & 3)) << 4);
 }
 #define SBL_CP_EROW 68       // floats per pixel row of the epilogue's LDS image (64 channels + 4: conflict-free column writes)
 
@@ -56,13 +53,13 @@ struct PatchEpi {
     const float* bs_inv2;
 };
 
-template <int NT, bool DGRAD, int STATS, bool SW>
+template <int NT, bool DGRAD, int STATS>
 __global__ __launch_bounds__(256) void sbl_conv_patch_kernel(const float* __restrict__ src, const float* __restrict__ wk, PatchEpi epi,
                                                              int NIMG, int H, int W, int C, int Nout, int TR, int tpi, int ntiles, int G,
                                                              unsigned long long* stamp) {
     using Tm = BfTerms<NT>;
     constexpr int NPL = Tm::NPL;
-    constexpr int CK = SBL_CP_CKV(SW), PIXB = SBL_CP_PIXBV(SW), Q4 = CK / 4, WQ = CK / 16;      // chunk channels, row bytes, float4s per pixel, float4s of a weight row per thread
+    constexpr int CK = SBL_CP_CK, PIXB = SBL_CP_PIXB, Q4 = CK / 4, WQ = CK / 16;      // chunk channels, row bytes, float4s per pixel, float4s of a weight row per thread
     constexpr int WPLANE = 64 * PIXB;      // one plane of a tap's 64 x CK weight block, rows padded like patch pixels
     extern __shared__ __attribute__((aligned(16))) unsigned char cp_smem[];
     sbl_stamp_begin(stamp);
@@ -138,7 +135,7 @@ __global__ __launch_bounds__(256) void sbl_conv_patch_kernel(const float* __rest
                     if (q < nq) {
                         uint2 pl[NPL];
                         bf_split4<NPL>(v[u], pl);
-                        const int off = cp_addr<SW>(q / Q4, (q % Q4) >> 1) + ((q % Q4) & 1) * 8;
+                        const int off = cp_addr(q / Q4, (q % Q4) >> 1) + ((q % Q4) & 1) * 8;
 #pragma unroll
                         for (int t = 0; t < NPL; ++t) *reinterpret_cast<uint2*>(cp_smem + t * plane + off) = pl[t];
                     }
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(256) void sbl_conv_patch_kernel(const float* __rest
                     bf_split4<NPL>(wreg[u], pl);
 #pragma unroll
                     for (int t = 0; t < NPL; ++t)
-                        *reinterpret_cast<uint2*>(wsm + t * WPLANE + cp_addr<SW>(wrow, ((tid & 3) * WQ + u) >> 1) + (u & 1) * 8) = pl[t];
+                        *reinterpret_cast<uint2*>(wsm + t * WPLANE + cp_addr(wrow, ((tid & 3) * WQ + u) >> 1) + (u & 1) * 8) = pl[t];
                 }
                 __syncthreads();      // weight block (and, for tap 0, the patch) complete
                 if (tap < 8) {
@@ -168,12 +165,12 @@ __global__ __launch_bounds__(256) void sbl_conv_patch_kernel(const float* __rest
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
                         for (int t = 0; t < NPL; ++t)
-                            a[set][i][t] = *reinterpret_cast<const bf16x8*>(cp_smem + t * plane + cp_addr<SW>(arow[i] + trow, cs * 2 + half));
+                            a[set][i][t] = *reinterpret_cast<const bf16x8*>(cp_smem + t * plane + cp_addr(arow[i] + trow, cs * 2 + half));
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
 #pragma unroll
                         for (int t = 0; t < NPL; ++t)
-                            b[set][j][t] = *reinterpret_cast<const bf16x8*>(wsm + t * WPLANE + cp_addr<SW>(j * 32 + l31, cs * 2 + half));
+                            b[set][j][t] = *reinterpret_cast<const bf16x8*>(wsm + t * WPLANE + cp_addr(j * 32 + l31, cs * 2 + half));
                 };
                 frags(0, 0);
 #pragma unroll
@@ -262,15 +259,14 @@ __global__ __launch_bounds__(256) void sbl_conv_patch_kernel(const float* __rest
 // Tile of an H x W map: TR rows of one image (G = 1; the largest TR with TR * W <= 256 whose patch fits the LDS budget, split
 // evenly over the image), or - small maps, whole images only - G images of H rows (G * H * W <= 256).  Returns false when
 // the map does not take this path (fewer than 7 of the tile's 8 row blocks would be used, or nothing fits).
-static inline bool sbl_conv_patch_tile(int H, int W, int nplanes, bool sw, int max_imgs, int& TR, int& G) {
-    const long budget = (sw ? 80 : 160) * 1024;
-    const int pixb = SBL_CP_PIXBV(sw);
+static inline bool sbl_conv_patch_tile(int H, int W, int nplanes, int& TR, int& G) {
+    const long budget = 80 * 1024;
+    const int pixb = SBL_CP_PIXB;
     int best = 0;
     for (int tr = 1; tr <= H; ++tr)
         if (tr * W <= 256 && ((long)(tr + 2) * (W + 2) + 64) * pixb * nplanes <= budget) best = tr;
     if (best >= H) {      // a whole image fits: several per tile?
         int g = 256 / (H * W);
-        if (max_imgs > 0 && g > max_imgs) g = max_imgs;
         while (g > 1 && ((long)g * (H + 2) * (W + 2) + 64) * pixb * nplanes > budget) --g;
         TR = H;
         G = g < 1 ? 1 : g;
@@ -283,43 +279,35 @@ static inline bool sbl_conv_patch_tile(int H, int W, int nplanes, bool sw, int m
     return TR >= 4 && TR * W >= 160;
 }
 
-extern int g_sbl_conv_patch, g_sbl_conv_patch_imgs;      // sbl_set_tuning knobs 5 and 8
 template <bool DGRAD, int STATS>
 static inline bool sbl_launch_conv_patch(const float* src, const float* wk, const PatchEpi& epi, int NIMG, int H, int W, int C, int Nout,
                                          int kid, hipStream_t s) {
-    const bool sw = g_sbl_conv_patch == 2;      // knob 5: 1 = padded 64-channel rows (one workgroup per CU), 2 = swizzled 32-channel rows (two)
-    if (!g_sbl_conv_patch || g_sbl_prec == 0 || C % 64 != 0 || Nout % 64 != 0) return false;
+    if (!g_sbl_route.conv_patch || g_sbl_prec == 0 || C % 64 != 0 || Nout % 64 != 0) return false;
     const int npl = g_sbl_prec == 6 ? 3 : g_sbl_prec == 3 ? 2 : 1;
     int TR = 0, G = 1;
-    if (!sbl_conv_patch_tile(H, W, npl, sw, g_sbl_conv_patch_imgs, TR, G)) return false;      // small maps keep the position-major kernels
+    if (!sbl_conv_patch_tile(H, W, npl, TR, G)) return false;      // small maps keep the position-major kernels
     const int tpi = sbl_cdiv(H, TR), ntiles = G > 1 ? sbl_cdiv(NIMG, G) : NIMG * tpi;
-    size_t lds = (size_t)npl * ((size_t)G * (TR + 2) * (W + 2) + 64) * SBL_CP_PIXBV(sw);
+    size_t lds = (size_t)npl * ((size_t)G * (TR + 2) * (W + 2) + 64) * SBL_CP_PIXB;
     if (lds < (size_t)256 * SBL_CP_EROW * 4) lds = (size_t)256 * SBL_CP_EROW * 4;      // the epilogue's image of the tile
-    const int cap = sw ? 512 : 256;      // persistent: one (two) workgroup(s) per CU
+    const int cap = 512;      // persistent: two workgroups per CU
     const int gy = Nout / 64, capx = cap / gy > 0 ? cap / gy : 1;
     const int gx = ntiles < capx ? ntiles : capx;
     const dim3 grid(gx, gy);
     unsigned long long* stamp = sbl_next_stamp_slot(kid);
-#define SBL_CP_GO(P, S)                                                                                                        \
+#define SBL_CP_GO(P)                                                                                                           \
     do {                                                                                                                       \
-        static bool set_##P##S[64] = {false};                                                                                  \
+        static bool set_##P[64] = {false};                                                                                     \
         int dev = 0;                                                                                                           \
         if (hipGetDevice(&dev) != hipSuccess) return false;                                                                    \
-        if (!set_##P##S[dev & 63]) {                                                                                           \
-            if (hipFuncSetAttribute((const void*)sbl_conv_patch_kernel<P, DGRAD, STATS, S>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false; \
-            set_##P##S[dev & 63] = true;                                                                                       \
+        if (!set_##P[dev & 63]) {                                                                                              \
+            if (hipFuncSetAttribute((const void*)sbl_conv_patch_kernel<P, DGRAD, STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false; \
+            set_##P[dev & 63] = true;                                                                                          \
         }                                                                                                                      \
-        hipLaunchKernelGGL((sbl_conv_patch_kernel<P, DGRAD, STATS, S>), grid, dim3(256), lds, s, src, wk, epi, NIMG, H, W, C, Nout, TR, tpi, ntiles, G, stamp); \
+        hipLaunchKernelGGL((sbl_conv_patch_kernel<P, DGRAD, STATS>), grid, dim3(256), lds, s, src, wk, epi, NIMG, H, W, C, Nout, TR, tpi, ntiles, G, stamp); \
     } while (0)
-    if (sw) {
-        if (g_sbl_prec == 6) SBL_CP_GO(6, true);
-        else if (g_sbl_prec == 3) SBL_CP_GO(3, true);
-        else SBL_CP_GO(1, true);
-    } else {
-        if (g_sbl_prec == 6) SBL_CP_GO(6, false);
-        else if (g_sbl_prec == 3) SBL_CP_GO(3, false);
-        else SBL_CP_GO(1, false);
-    }
+    if (g_sbl_prec == 6) SBL_CP_GO(6);
+    else if (g_sbl_prec == 3) SBL_CP_GO(3);
+    else SBL_CP_GO(1);
 #undef SBL_CP_GO
     return true;
 }

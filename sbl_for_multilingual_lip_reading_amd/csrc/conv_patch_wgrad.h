@@ -223,18 +223,16 @@ static inline bool sbl_conv_patch_wgrad_geom(int NIMG, int H, int W, int Cin, in
     return true;
 }
 
-extern int g_sbl_conv_patch_wgrad;      // sbl_set_tuning knob 9
 // dw must be zeroed (or hold the sum to add to).  Returns false when nothing was launched.
 static inline bool sbl_launch_conv_patch_wgrad(const float* x, const float* dy, float* dw, int NIMG, int H, int W, int Cin, int Cout,
                                                unsigned long long* stamp, hipStream_t s) {
-    if (!g_sbl_conv_patch_wgrad || g_sbl_prec == 0 || Cin % 64 != 0 || Cout % 64 != 0 || H * W < g_sbl_conv_patch_wgrad) return false;
+    const int min_pixels = g_sbl_route.conv_patch_wgrad;
+    if (!min_pixels || g_sbl_prec == 0 || Cin % 64 != 0 || Cout % 64 != 0 || H * W < min_pixels) return false;
     const int npl = g_sbl_prec == 6 ? 3 : g_sbl_prec == 3 ? 2 : 1;
     PwgGeom gm;
     if (!sbl_conv_patch_wgrad_geom(NIMG, H, W, Cin, Cout, npl, gm)) return false;
     const int combos = (Cin / 64) * (Cout / 64);
-    extern int g_sbl_exp[8];
-    const int cus = g_sbl_exp[0] > 0 ? g_sbl_exp[0] : 256;      // (experiment knob 100: leave CUs to the other stream)
-    int gx = cus / combos;      // one workgroup per CU
+    int gx = sbl_patch_wgrad_cus / combos;      // one workgroup per CU
     if (gx < 1) gx = 1;
     if (gx > gm.ntiles) gx = gm.ntiles;
     const size_t lds = (size_t)npl * (gm.xrows + gm.dyrows) * 128 + (size_t)gm.dyrows * 4;      // images + pixel -> patch row table

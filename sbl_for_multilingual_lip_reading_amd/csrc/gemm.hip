@@ -54,72 +54,6 @@ extern "C" int sbl_set_matmul_precision(int terms) {
     return 0;
 }
 extern "C" int sbl_get_matmul_precision(void) { return g_sbl_prec; }
-int g_sbl_exp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-int g_sbl_gemm2_split_target = 256, g_sbl_gemm2_split_max = 8;      // knobs 10, 11: in-launch split-K of the two-direction decoder products
-int g_sbl_group_cap = 0;           // knob 6: cap on the workgroups of the grouped weight-gradient launch (0 = one per tile)
-int g_sbl_wave_ksplit = 1;
-int g_sbl_ksplit_tiles = 320;      // knob 2 (same-box A/B of the whole step: 0 -> 32.99, 320 -> 32.81, 768 -> 32.99 ms)
-int g_sbl_big_min = 4096;          // knob 1
-extern "C" int sbl_set_tuning(int knob, int value) {
-    extern int g_sbl_wg_s2_small, g_sbl_wg_target, g_sbl_conv_patch;
-    if (knob >= 100 && knob < 108) {      // scratch knobs for experiments (g_sbl_exp[knob - 100]); no shipped code path reads them unless DESIGN.md says so
-        g_sbl_exp[knob - 100] = value;
-        return 0;
-    }
-    if (knob == 14) {
-        extern int g_sbl_stem_fwd8;
-        g_sbl_stem_fwd8 = value != 0;
-        return 0;
-    }
-    if (knob == 13) {
-        extern int g_sbl_stem_ablate;
-        g_sbl_stem_ablate = value;
-        return 0;
-    }
-    if (knob == 12) {
-        extern int g_sbl_stem_wgrad_tr;
-        g_sbl_stem_wgrad_tr = value != 0;
-        return 0;
-    }
-    if (knob == 10 || knob == 11) {
-        SBL_REQUIRE(value >= 1, "sbl_set_tuning: value < 1");
-        (knob == 10 ? g_sbl_gemm2_split_target : g_sbl_gemm2_split_max) = value;
-        return 0;
-    }
-    if (knob == 9) {
-        extern int g_sbl_conv_patch_wgrad;
-        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
-        g_sbl_conv_patch_wgrad = value;
-        return 0;
-    }
-    if (knob == 8) {
-        extern int g_sbl_conv_patch_imgs;
-        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
-        g_sbl_conv_patch_imgs = value;
-        return 0;
-    }
-    if (knob == 7) {
-        extern int g_sbl_pm_wg64_maxm;
-        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
-        g_sbl_pm_wg64_maxm = value;
-        return 0;
-    }
-    if (knob == 6) {
-        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
-        g_sbl_group_cap = value;
-        return 0;
-    }
-    if (knob >= 3 && knob <= 5) {
-        SBL_REQUIRE(value >= 0, "sbl_set_tuning: negative value");
-        (knob == 3 ? g_sbl_wg_s2_small : knob == 4 ? g_sbl_wg_target : g_sbl_conv_patch) = value;
-        return 0;
-    }
-    SBL_REQUIRE(knob >= 0 && knob <= 2 && value >= 0, "sbl_set_tuning: unknown knob %d / value %d (0 = wave-group K split on/off, 1 = 64x64-tile count from which dense products take 128x128 tiles, 2 = largest tile count that takes the wave-group K split)", knob, value);
-    if (knob == 0) g_sbl_wave_ksplit = value != 0;
-    else if (knob == 1) g_sbl_big_min = value;
-    else g_sbl_ksplit_tiles = value;
-    return 0;
-}
 
 // ------------------------------------------------------------------ dispatch
 template <class AL, class BL, int BM, int BN, int KU>
@@ -183,8 +117,7 @@ extern "C" int sbl_gemm_f32(int transA, int transB, int M, int N, int K, const f
                 "sbl_gemm_f32: operand spans more than 2 GiB (buffer descriptor range)");
     const bool plain = !bias && !relu && !relu_mask;
     const long tiles64 = (long)sbl_cdiv(M, 64) * sbl_cdiv(N, 64);
-    const int big_min = g_sbl_big_min;   // tuning knob (4352x2048x512: 128x128 tiles 131 us, 64x64 115 us)
-    const bool big = (M >= 1024 && N >= 256 && tiles64 >= big_min);
+    const bool big = (M >= 1024 && N >= 256 && tiles64 >= sbl_big_min_tiles);
     // split K when the output has too few 64x64 tiles to fill 256 CUs: aim at ~256 workgroups, chunks of at
     // least one 64-deep macro step, at most 8 slices (the last-arriving workgroup reads every slab)
     int splits = 1;
@@ -236,19 +169,14 @@ extern "C" int sbl_gemm_f32(int transA, int transB, int M, int N, int K, const f
 #define SBL_GO(VEC, BM, BN, KU) \
     launch_trans<VEC, BM, BN, KU>(transA, transB, A, lda, B, ldb, C, ldc, bias, relu, relu_mask, ldm, mode, M, N, K, splits, sc, s)
     if (big) {
-        constexpr int big_ku = 1;
-        if (vec && big_ku == 2) SBL_GO(true, 128, 128, 2);
-        else if (vec) SBL_GO(true, 128, 128, 1);
+        if (vec) SBL_GO(true, 128, 128, 1);
         else SBL_GO(false, 128, 128, 1);
     } else {
         // KU = 4 (69 KB of LDS, 2 workgroups per CU) while every workgroup of the launch is resident at once; beyond
         // 512 workgroups KU = 2 (35 KB, 4 per CU) keeps them all resident instead of running a second, part-filled
         // round (measured 1440x2048x512: 36.6 vs 46.9 us)
-        constexpr int ku_env = 0;
-        const int ku = ku_env ? ku_env : (tiles64 * splits > 512 ? 2 : 4);
         if (!vec) SBL_GO(false, 64, 64, 1);
-        else if (ku == 1) SBL_GO(true, 64, 64, 1);
-        else if (ku == 2) SBL_GO(true, 64, 64, 2);
+        else if (tiles64 * splits > 512) SBL_GO(true, 64, 64, 2);
         else SBL_GO(true, 64, 64, 4);
     }
 #undef SBL_GO
@@ -271,8 +199,7 @@ extern "C" int sbl_gemm2_f32(int M, int N, int K, const float* A0, const float* 
     const bool vec = sbl_aligned16(A0) && sbl_aligned16(A1) && sbl_aligned16(B0) && sbl_aligned16(B1) && lda % 4 == 0 && ldb % 4 == 0 && K % 8 == 0;
     SBL_REQUIRE(sbl_fits_u32((long)M * lda) && sbl_fits_u32((long)N * ldb), "sbl_gemm2_f32: operand spans more than 2 GiB (buffer descriptor range)");
     const long tiles64 = (long)sbl_cdiv(M, 64) * sbl_cdiv(N, 64);
-    const int big_min = g_sbl_big_min;
-    const bool big = (M >= 1024 && N >= 256 && 2 * tiles64 >= big_min);
+    const bool big = (M >= 1024 && N >= 256 && 2 * tiles64 >= sbl_big_min_tiles);
     if (!vec || big) {      // shapes the decoder forward does not produce: two plain launches
         if (int e = sbl_gemm_f32(0, 1, M, N, K, A0, lda, B0, ldb, C0, ldc, bias0, relu, nullptr, 0, 0, nullptr, ws, ws_bytes, stream)) return e;
         return sbl_gemm_f32(0, 1, M, N, K, A1, lda, B1, ldb, C1, ldc, bias1, relu, nullptr, 0, 0, nullptr, ws, ws_bytes, stream);
@@ -292,12 +219,10 @@ extern "C" int sbl_gemm2_f32(int M, int N, int K, const float* A0, const float* 
         }
     }
     int splits = 1;
-    const int split_tiles = g_sbl_exp[1] > 0 ? g_sbl_exp[1] : 192;      // (experiment knob 101)
-    const int split_target = g_sbl_gemm2_split_target;
-    if (2 * tiles64 < split_tiles && K >= 128) {
-        splits = (int)((split_target + 2 * tiles64 - 1) / (2 * tiles64));
+    if (2 * tiles64 < sbl_gemm2_split_tiles && K >= 128) {
+        splits = (int)((sbl_gemm2_split_target + 2 * tiles64 - 1) / (2 * tiles64));
         if (splits > K / 64) splits = K / 64;
-        if (splits > g_sbl_gemm2_split_max) splits = g_sbl_gemm2_split_max;
+        if (splits > sbl_gemm2_split_max) splits = sbl_gemm2_split_max;
         if (splits < 1) splits = 1;
     }
     SplitCtl sc{nullptr, nullptr, nullptr, nullptr};
@@ -315,9 +240,7 @@ extern "C" int sbl_gemm2_f32(int M, int N, int K, const float* A0, const float* 
     DenseKC<64, true> bl{B0, ldb, N};
     EpiStore<0, false> e{C0, ldc, bias0, relu, nullptr, nullptr, 0};
     GemmDual du{A1, B1, C1, bias1};
-    constexpr int ku_env = 0;
-    const int ku = ku_env ? ku_env : (2 * tiles64 * splits > 512 ? 2 : 4);
-    if (ku == 2) sbl_launch_gemm2<DenseKC<64, true>, DenseKC<64, true>, EpiStore<0, false>, 64, 64, 2>(al, bl, e, du, M, N, K, splits, s, sc);
+    if (2 * tiles64 * splits > 512) sbl_launch_gemm2<DenseKC<64, true>, DenseKC<64, true>, EpiStore<0, false>, 64, 64, 2>(al, bl, e, du, M, N, K, splits, s, sc);
     else sbl_launch_gemm2<DenseKC<64, true>, DenseKC<64, true>, EpiStore<0, false>, 64, 64, 4>(al, bl, e, du, M, N, K, splits, s, sc);
     SBL_LAUNCH_CHECK("sbl_gemm2_f32");
     return 0;
@@ -332,7 +255,6 @@ extern "C" int sbl_wgrad_seg_f32(int nseg, const float* const* A_ptrs, long lda,
     hipStream_t s = (hipStream_t)stream;
     SBL_REQUIRE(nseg >= 1 && nseg <= SBL_MAX_KSEG && A_ptrs && B_ptrs && seg_rows && C, "sbl_wgrad_seg_f32: bad segment list (nseg=%d)", nseg);
     SBL_REQUIRE(M > 0 && N > 0 && lda >= M && ldb >= N && ldc >= N && lda % 4 == 0 && ldb % 4 == 0, "sbl_wgrad_seg_f32: bad dims M=%d N=%d lda=%ld ldb=%ld", M, N, lda, ldb);
-    constexpr int seg_tile_env = 0;
     constexpr int seg_ku = 2;
     constexpr int seg_target = 768;
     long K = 0;
@@ -369,7 +291,7 @@ extern "C" int sbl_wgrad_seg_f32(int nseg, const float* const* A_ptrs, long lda,
     using std::integral_constant;
     // 128x128 tiles (twice the flops per staged byte) once the weight has enough of them to split K over; measured at
     // K = 4352 rows: 2048x512 67 vs 52 TF, 1536x512 58 vs 50, 512x512 26 vs 34
-    const int seg_tile = seg_tile_env ? seg_tile_env : ((long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128) >= 48 ? 128 : 64);
+    const int seg_tile = ((long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128) >= 48 ? 128 : 64);
     if (!aligned) go(SegMC<64, false>{}, integral_constant<int, 64>{}, integral_constant<int, 2>{});
     else if (seg_tile == 128) go(SegMC<128, true>{}, integral_constant<int, 128>{}, integral_constant<int, 1>{});
     else if (seg_ku == 4) go(SegMC<64, true>{}, integral_constant<int, 64>{}, integral_constant<int, 4>{});
@@ -402,7 +324,7 @@ __global__ void group_write_kernel(GroupWrite w, GroupProb* table, int first, in
     if (i < count) table[first + i] = w.p[i];
 }
 struct GroupCommon {
-    int nprob, nseg, K, ntiles;
+    int nprob, nseg, K;
     int kcum[SBL_MAX_KSEG + 1];
 };
 // ONESEG: every problem's K rows are one contiguous block (the stage-batched decoder backward, the encoder): plain
@@ -411,10 +333,7 @@ struct GroupCommon {
 template <bool ONESEG, int PREC>
 __global__ __launch_bounds__(256) void sbl_wgrad_group_kernel(const GroupProb* __restrict__ table, GroupCommon gc,
                                                               unsigned long long* stamp) {
-    // (gridDim.x may be capped below the tile count - sbl_set_tuning knob 6: the workgroups then walk the tiles, so that the
-    // launch takes a bounded share of the CUs while a dependent chain of small kernels runs on the other stream)
-  for (int t = blockIdx.x; t < gc.ntiles; t += gridDim.x) {
-    if (t != (int)blockIdx.x) __syncthreads();      // the previous tile's LDS reads are done
+    const int t = blockIdx.x;      // one workgroup per tile
     // problem of this tile: binary search over tile0 (ascending), workgroup-uniform
     int lo = 0, hi = gc.nprob - 1;
     while (lo < hi) {
@@ -445,7 +364,6 @@ __global__ __launch_bounds__(256) void sbl_wgrad_group_kernel(const GroupProb* _
         sbl_gemm_tile<SegMC<128, true>, SegMC<128, true>, EpiStore<1, false>, 128, 128, 1, 2, PREC>(al, bl, e, sc, g.M, g.N, tx * 128,
                                                                                                   ty * 128, 0, gc.K, 0, 0, 1, ty == 0);
     }
-  }
 }
 
 extern "C" long sbl_wgrad_group_table_bytes(int nprob) { return (long)sizeof(GroupProb) * (nprob > 0 ? nprob : 0); }
@@ -500,8 +418,6 @@ extern "C" int sbl_wgrad_group_f32(int nprob, int nseg, const int* seg_rows, con
         hipLaunchKernelGGL(group_write_kernel, dim3(1), dim3(64), 0, s, w, tab, first, count);
     }
     SBL_REQUIRE(tiles < (1L << 30), "sbl_wgrad_group_f32: too many tiles");
-    gc.ntiles = (int)tiles;
-    if (g_sbl_group_cap > 0 && tiles > g_sbl_group_cap) tiles = g_sbl_group_cap;      // workgroups of the launch (they walk the tiles)
 #define SBL_KG1_(P) sbl_wgrad_group_kernel<true, P>
 #define SBL_KG0_(P) sbl_wgrad_group_kernel<false, P>
     if (nseg == 1)

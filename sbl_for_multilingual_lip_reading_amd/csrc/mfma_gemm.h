@@ -20,6 +20,7 @@
 #include "sbl_common.h"
 
 #include "tile_loaders.h"
+#include "tuning.h"
 
 // ------------------------------------------------------------------ epilogues
 // MODE 0: C = acc (+bias) (ReLU)   MODE 1: C += acc (non-atomic; one block per tile)
@@ -342,11 +343,7 @@ __device__ __forceinline__ void sbl_gemm_tile(const AL& al, const BL& bl, const 
         sbl_gemm_tile_bf<AL, BL, EPI, BM, BN, 1, WN, PREC, NH>(al, bl, epi, sc, M, N, m0, n0, kbeg, kend, tile, z, nz, colsum_tile);
 }
 
-// Matrix-product precision of the tile engine (sbl_set_matmul_precision): 0 = fp32 MFMA, 6 / 3 / 1 = bf16 MFMA terms.
-extern int g_sbl_prec;
-extern int g_sbl_wave_ksplit;      // A/B knobs (sbl_set_tuning): wave-group K split on / off,
-extern int g_sbl_ksplit_tiles;     // ... the largest tile count that takes it,
-extern int g_sbl_big_min;          // ... and the 64x64-tile count from which dense products take 128x128 tiles
+// Launch the instantiation of the current matrix-product precision (g_sbl_prec, tuning.h).
 #define SBL_PREC_LAUNCH(KERNEL_P, grid, s, ...)                                                         \
     do {                                                                                                \
         switch (g_sbl_prec) {                                                                           \
@@ -383,7 +380,7 @@ extern int g_sbl_big_min;          // ... and the 64x64-tile count from which de
 // two decoder directions' launches share the chip, and 48 KB / 512-thread workgroups co-reside worse); with 8.5 tiles per CU
 // (4352 x 2048 x 512) the large workgroups halve the resident tiles: 129 -> 206 us.  Whole-step A/B on one box: threshold
 // 0 / 320 / 768 tiles -> 32.99 / 32.81 / 32.99 ms.  Never with split-K over workgroups (the slab reduction has barriers).
-static inline bool sbl_wave_ksplit_pays(long tiles, int nz) { return nz == 1 && g_sbl_wave_ksplit && tiles <= g_sbl_ksplit_tiles; }
+static inline bool sbl_wave_ksplit_pays(long tiles, int nz) { return nz == 1 && tiles <= sbl_wave_ksplit_max_tiles; }
 
 // XCD-aware tile order (x_off < 0 selects it; the real offset is then -x_off - 1).  Workgroups go to the 8 XCDs
 // round-robin by linear id, each XCD with its own L2.  With the plain (x fastest) order the n-tiles that share one

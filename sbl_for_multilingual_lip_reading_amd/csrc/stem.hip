@@ -10,7 +10,7 @@
 // recomputed on the fly from conv_out, the pooled gradient and the argmax — dconv is never materialised.
 #include "sbl_common.h"
 #include "bf16_split.h"
-extern int g_sbl_prec;      // gemm.hip: 0 = fp32 MFMA, 6 / 3 / 1 = split-bf16 products (sbl_set_matmul_precision)
+#include "tuning.h"
 
 #define ST_TH 8
 #define ST_TW 16
@@ -132,8 +132,11 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restr
 //     reads, split in registers - the pixel operand never takes a second trip through LDS.  18 k-steps (K = 288, 245 live).
 //   Weights: split once per workgroup into LDS in B-fragment order ([k-step][channel half][plane][lane] x 16 bytes,
 //     108 KB for three planes), resident for the workgroup's lifetime: one ds_read_b128 per fragment, conflict free.
-//   One persistent workgroup per CU (108 KB + two 16.8 KB patch buffers); the next tile's patch is fetched into registers
-//     before the contraction and written to the idle buffer after it, so the global round trip hides under 216 MFMAs.
+//   One persistent workgroup per CU (108 KB + two 16.8 KB patch buffers) of EIGHT wavefronts on one copy of the weight planes:
+//     two groups of four wavefronts work on two tiles at a time (each group with its own patch buffer), so every SIMD has two
+//     wavefronts whose conversion / LDS work and MFMAs interleave (four wavefronts with two patch buffers of their own: 497
+//     against 434 us).  The next patch is fetched into registers before the contraction and written between two workgroup
+//     barriers after both groups are done with the current one, so the global round trip hides under 216 MFMAs.
 #define SB_KS 18
 __host__ __device__ constexpr int sb_rowoff(int r) { return ((r < 35 ? r : 34) / 7) * ST_PFS + ((r < 35 ? r : 34) % 7) * ST_PWS; }
 #define SB_PATCH (ST_PT * ST_PFS)                  // floats
@@ -163,8 +166,7 @@ __device__ __forceinline__ void sb_put_patch(float* patch, const float (&pre)[SB
         if (tid + u * 256 < SB_PATCH) patch[tid + u * 256] = pre[u];
 }
 
-// One tile of the contraction + epilogue for one wavefront (32 pixels x 64 channels): shared by the 4-wavefront kernel and the
-// 8-wavefront one below.
+// One tile of the contraction + epilogue for one wavefront (32 pixels x 64 channels).
 template <int NT>
 __device__ __forceinline__ void sb_tile_compute(const float* patch, const unsigned char* wsm, int abase, int lane, int half, int l31,
                                                 int wave, int ty, int tx, int img, int Ho, int Wo, float* __restrict__ out,
@@ -237,95 +239,6 @@ __device__ __forceinline__ void sb_tile_compute(const float* patch, const unsign
 }
 
 template <int NT>
-__global__ __launch_bounds__(256) void stem_conv_fwd_bf_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                               float* __restrict__ out, double* __restrict__ stats, int N,
-                                                               int T, int H, int W, int Ho, int Wo, int TY, int TX,
-                                                               int ntiles, unsigned long long* stamp) {
-    using Tm = BfTerms<NT>;
-    constexpr int NPL = Tm::NPL;
-    sbl_stamp_begin(stamp);
-    extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];
-    unsigned char* wsm = sb_smem;                                              // SB_KS * 2 * NPL fragments of 1 KB
-    float* patch0 = reinterpret_cast<float*>(sb_smem + SB_KS * 2 * NPL * 1024);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-
-    // weights -> bf16 planes in fragment order: lane ln of fragment (j, c) holds channel c*32 + (ln&31), taps (row 2j + (ln>>5), kw 0..7)
-    for (int u = tid; u < SB_KS * 2 * 64; u += 256) {
-        const int ln = u & 63, c = (u >> 6) & 1, j = u >> 7;
-        const int co = c * 32 + (ln & 31), r = 2 * j + (ln >> 5);
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (r < 35 && i < 7) ? w[co * ST_K + r * 7 + i] : 0.f;
-        uint2 lo[NPL], hi[NPL];
-        bf_split4<NPL>(make_float4(v[0], v[1], v[2], v[3]), lo);
-        bf_split4<NPL>(make_float4(v[4], v[5], v[6], v[7]), hi);
-#pragma unroll
-        for (int pl = 0; pl < NPL; ++pl)
-            *reinterpret_cast<uint4*>(wsm + (((j * 2 + c) * NPL + pl) * 64 + ln) * 16) = make_uint4(lo[pl].x, lo[pl].y, hi[pl].x, hi[pl].y);
-    }
-
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-    const int py = 2 * wave + (l31 >> 4), px = l31 & 15;      // this lane's A-operand pixel inside the tile
-    const int abase = py * 2 * ST_PWS + px * 2;
-    float pre[SB_PRE];
-    int cur = 0;
-    if ((int)blockIdx.x < ntiles) {
-        sb_fetch_patch(pre, x, blockIdx.x, TX, TY, T, H, W, tid);
-        sb_put_patch(patch0, pre, tid);
-    }
-    __syncthreads();
-
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = tile % TX;
-        const int ty = (tile / TX) % TY;
-        const int img = tile / (TX * TY);
-        const float* patch = patch0 + cur * SB_PATCH;
-        const int next = tile + (int)gridDim.x;
-        if (next < ntiles) sb_fetch_patch(pre, x, next, TX, TY, T, H, W, tid);
-
-        sb_tile_compute<NT>(patch, wsm, abase, lane, half, l31, wave, ty, tx, img, Ho, Wo, out, s1, s2);
-        if (next < ntiles) sb_put_patch(patch0 + (cur ^ 1) * SB_PATCH, pre, tid);
-        __syncthreads();       // next patch complete; every wave is done reading this one
-        cur ^= 1;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        s1[j] += __shfl_xor(s1[j], 32, 64);
-        s2[j] += __shfl_xor(s2[j], 32, 64);
-    }
-    float (*red)[128] = reinterpret_cast<float (*)[128]>(patch0);      // the loop's last barrier retired every patch read
-    if (half == 0) {
-        red[wave][l31] = s1[0];
-        red[wave][32 + l31] = s1[1];
-        red[wave][64 + l31] = s2[0];
-        red[wave][96 + l31] = s2[1];
-    }
-    __syncthreads();
-    if (tid < 128) atomicAdd(stats + tid, (double)(red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]));
-    sbl_stamp_end(stamp);
-}
-template <int NT>
-static int stem_launch_fwd_bf(const float* x, const float* w, float* conv_out, double* stats, int N, int T, int H, int W, int Ho,
-                              int Wo, int TY, int TX, int ntiles, hipStream_t s) {
-    constexpr int lds = SB_KS * 2 * BfTerms<NT>::NPL * 1024 + 2 * SB_PATCH * 4;
-    static bool set[64] = {false};
-    int dev = 0;
-    SBL_HIP(hipGetDevice(&dev));
-    if (!set[dev & 63]) {
-        SBL_HIP(hipFuncSetAttribute((const void*)stem_conv_fwd_bf_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        set[dev & 63] = true;
-    }
-    const int grid = ntiles < 256 ? ntiles : 256;          // persistent: one workgroup per CU
-    hipLaunchKernelGGL(stem_conv_fwd_bf_kernel<NT>, dim3(grid), dim3(256), lds, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX,
-                       ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
-    return 0;
-}
-
-// The same with EIGHT wavefronts on one copy of the weight planes: two groups of four wavefronts work on two tiles at a time
-// (each group with its own patch buffer), so every SIMD has two wavefronts whose conversion / LDS work and MFMAs interleave.
-// One patch buffer per group (two would not fit beside the 108 KB of weights): the next patch waits in registers and is
-// written between two workgroup barriers after both groups are done with the current one.
-template <int NT>
 __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                                 float* __restrict__ out, double* __restrict__ stats, int N,
                                                                 int T, int H, int W, int Ho, int Wo, int TY, int TX,
@@ -337,7 +250,8 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
     unsigned char* wsm = sb_smem;                                              // SB_KS * 2 * NPL fragments of 1 KB
     const int tid = threadIdx.x, grp = tid >> 8, gt = tid & 255, lane = tid & 63, wave = gt >> 6, half = lane >> 5, l31 = lane & 31;
     float* patch = reinterpret_cast<float*>(sb_smem + SB_KS * 2 * NPL * 1024) + grp * SB_PATCH;
-    for (int u = tid; u < SB_KS * 2 * 64; u += 512) {      // weights -> bf16 planes in fragment order (as above)
+    // weights -> bf16 planes in fragment order: lane ln of fragment (j, c) holds channel c*32 + (ln&31), taps (row 2j + (ln>>5), kw 0..7)
+    for (int u = tid; u < SB_KS * 2 * 64; u += 512) {
         const int ln = u & 63, c = (u >> 6) & 1, j = u >> 7;
         const int co = c * 32 + (ln & 31), r = 2 * j + (ln >> 5);
         float v[8];
@@ -396,7 +310,6 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
     }
     sbl_stamp_end(stamp);
 }
-int g_sbl_stem_fwd8 = 1;      // sbl_set_tuning knob 14: 1 = the 8-wavefront forward kernel, 0 = the 4-wavefront one
 template <int NT>
 static int stem_launch_fwd_bf2(const float* x, const float* w, float* conv_out, double* stats, int N, int T, int H, int W, int Ho,
                                int Wo, int TY, int TX, int ntiles, hipStream_t s) {
@@ -747,136 +660,12 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------ backward pass 2 on the bf16 MFMA pipe (split-bf16 modes)
-// Same tiles, dconv recomputation and atomics; the contraction over the tile's 128 pixels runs as 8 k-steps (one 16-pixel row
-// each) of v_mfma_f32_32x32x16_bf16.  dconv sits TRANSPOSED in LDS ([co][pixel], rows of 132 floats) so a lane's A operand
-// (channel l&31, pixels 8*(l>>5)..+7 of the row) is two aligned 16-byte reads; the B operand (tap l&31 of the wave's two
-// 32-tap tiles, the same 8 pixels) is eight stride-2 floats of the patch.  Both are split into bf16 planes in registers.
-#define SB_DT 132
-template <int NT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void stem_wgrad_bf_kernel(const float* __restrict__ x, const float* __restrict__ conv,
-                                                            const float* __restrict__ dpool, const uint8_t* __restrict__ argmax,
-                                                            const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            const double* __restrict__ sums, float* __restrict__ dw,
-                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int T,
-                                                            int H, int W, int Ho, int Wo, int Hp, int Wp, int TY, int TX,
-                                                            int ntiles, unsigned long long* stamp) {
-    using Tm = BfTerms<NT>;
-    constexpr int NPL = Tm::NPL;
-    sbl_stamp_begin(stamp);
-    __shared__ __attribute__((aligned(16))) float Dt[64 * SB_DT];
-    __shared__ float patch[ST_PT * ST_PFS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
-    const double cnt = (double)N * T * Ho * Wo;
-    if (blockIdx.x == 0 && tid < 64) {
-        dbeta[tid] = (float)sums[tid];
-        dgamma[tid] = (float)sums[64 + tid];
-    }
-    const int c4 = (tid & 15) * 4;
-    const float4 mu = *reinterpret_cast<const float4*>(mean + c4);
-    const float4 is = *reinterpret_cast<const float4*>(invstd + c4);
-    const float4 ga = *reinterpret_cast<const float4*>(gamma + c4);
-    const float4 be = *reinterpret_cast<const float4*>(beta + c4);
-    float mg[4], mgx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        mg[k] = (float)(sums[c4 + k] / cnt);
-        mgx[k] = (float)(sums[64 + c4 + k] / cnt);
-    }
-    const int k0 = (2 * wave) * 32 + l31, k1 = k0 + 32;   // this lane's two B-operand taps
-    const int boff0 = st_koff(k0) + 16 * half, boff1 = st_koff(k1) + 16 * half;      // + its 8 pixels' first column
-    const int aoff = l31 * SB_DT + 8 * half;
-
-    f32x16 acc[2][2];   // [co tile][k tile]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = tile % TX;
-        const int ty = (tile / TX) % TY;
-        const int img = tile / (TX * TY);
-        const int n = img / T, t = img - n * T;
-        __syncthreads();
-        st_load_patch(patch, x, n, t, ty, tx, T, H, W, tid);
-        // dconv tile -> Dt[co][pixel]; thread = (pixel group, channel quad), 8 passes of 16 pixels
-#pragma unroll 2
-        for (int ps = 0; ps < 8; ++ps) {
-            const int pix = ps * 16 + (tid >> 4);
-            const int oh = ty * ST_TH + (pix >> 4), ow = tx * ST_TW + (pix & 15);
-            float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (oh < Ho && ow < Wo) {
-                const float4 v = *reinterpret_cast<const float4*>(conv + (((long)img * Ho + oh) * Wo + ow) * 64 + c4);
-                float xh[4] = {(v.x - mu.x) * is.x, (v.y - mu.y) * is.y, (v.z - mu.z) * is.z, (v.w - mu.w) * is.w};
-                float y[4] = {xh[0] * ga.x + be.x, xh[1] * ga.y + be.y, xh[2] * ga.z + be.z, xh[3] * ga.w + be.w};
-                float g[4];
-                stem_gather_g(dpool, argmax, img, oh, ow, Hp, Wp, c4, y, g);
-                d.x = ga.x * is.x * (g[0] - mg[0] - xh[0] * mgx[0]);
-                d.y = ga.y * is.y * (g[1] - mg[1] - xh[1] * mgx[1]);
-                d.z = ga.z * is.z * (g[2] - mg[2] - xh[2] * mgx[2]);
-                d.w = ga.w * is.w * (g[3] - mg[3] - xh[3] * mgx[3]);
-            }
-            Dt[(c4 + 0) * SB_DT + pix] = d.x;
-            Dt[(c4 + 1) * SB_DT + pix] = d.y;
-            Dt[(c4 + 2) * SB_DT + pix] = d.z;
-            Dt[(c4 + 3) * SB_DT + pix] = d.w;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int sr = 0; sr < 8; ++sr) {          // k-step = pixel row sr of the tile
-            bf16x8 a[2][NPL], b[2][NPL];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float4* ap = reinterpret_cast<const float4*>(Dt + i * 32 * SB_DT + aoff + sr * 16);
-                uint2 lo[NPL], hi[NPL];
-                bf_split4<NPL>(ap[0], lo);
-                bf_split4<NPL>(ap[1], hi);
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) a[i][pl] = __builtin_bit_cast(bf16x8, make_uint4(lo[pl].x, lo[pl].y, hi[pl].x, hi[pl].y));
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const float* bp = patch + sr * 2 * ST_PWS + (j ? boff1 : boff0);
-                uint2 lo[NPL], hi[NPL];
-                bf_split4<NPL>(make_float4(bp[0], bp[2], bp[4], bp[6]), lo);
-                bf_split4<NPL>(make_float4(bp[8], bp[10], bp[12], bp[14]), hi);
-#pragma unroll
-                for (int pl = 0; pl < NPL; ++pl) b[j][pl] = __builtin_bit_cast(bf16x8, make_uint4(lo[pl].x, lo[pl].y, hi[pl].x, hi[pl].y));
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int tt = 0; tt < Tm::N; ++tt)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][Tm::pa(tt)], b[j][Tm::pb(tt)], acc[i][j], 0, 0, 0);
-        }
-    }
-    // D: col (lane&31) = tap within the k tile, row = co within the co tile
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int k = (2 * wave + j) * 32 + l31;
-            if (k < ST_K) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int co = i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                    atomicAdd(dw + co * ST_K + k, acc[i][j][r]);
-                }
-            }
-        }
-    sbl_stamp_end(stamp);
-}
-
-// ------------------------------------------------------------------ backward pass 2, split-bf16 modes, operands split ONCE
-// The kernel above splits every operand where it is used: each dconv value in all four wavefronts, each patch value once per
-// tap it feeds (~60 times), 216 conversion instructions per 24 MFMAs.  Here both operands are split into bf16 planes on the
-// way INTO LDS and every MFMA operand comes out of two transposed reads (ds_read_b64_tr_b16: per 16 lanes a block of
-// 4 K-rows x 16 columns; each lane supplies the 8-byte-aligned address of 4 consecutive columns of one row):
+// Same tiles, dconv recomputation and atomics as the fp32 kernel above; the contraction over the tile's 128 pixels runs as
+// 8 k-steps (one 16-pixel row each) of v_mfma_f32_32x32x16_bf16.  Both operands are split into bf16 planes ONCE, on the way
+// INTO LDS, and every MFMA operand comes out of two transposed reads (ds_read_b64_tr_b16: per 16 lanes a block of
+// 4 K-rows x 16 columns; each lane supplies the 8-byte-aligned address of 4 consecutive columns of one row).  (A first kernel
+// split every operand where it is used - each dconv value in all four wavefronts, each patch value once per tap it feeds,
+// ~60 times: 216 conversion instructions per 24 MFMAs.)
 //  * A = dconv: pixel-major planes [64 pixels][64 co] (half a tile at a time: 4 pixel rows = 4 k-steps), 128-byte rows with
 //    the two 64-byte halves swapped on rows with bit 1 set (conflict-free for 4 consecutive rows).
 //  * B = taps: the columns of a block are taps; the 7 kw taps (+ 1 pad) of a (kt, kh) pair at pixel px are the 8 CONSECUTIVE
@@ -886,7 +675,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // 4 wavefronts: wavefront w owns tap tiles w and w + 4 for both co tiles and every other k-step of one co tile of the ninth
 // tap tile; 27 MFMAs per 12 + 15 transposed reads at bf16x6 (average) and no conversion in the K loop.  77 KB of LDS and
 // 4-wavefront workgroups: two per CU.
-// MEASURED (tools/bench_stem.py, knobs 12 / 13): 642 us against 801 us for the kernel above.  Phase ablation: k-steps 240 us
+// MEASURED (tools/bench_stem.py): 642 us against 801 us for the split-per-use kernel.  With one phase removed at a time: k-steps 240 us
 // (MFMA-bound on the SIMDs of wavefronts 0 and 1: 30 MFMAs per k-step, 65 tiles per CU), dconv recompute 250 us (VALU: the
 // pool / ReLU / BatchNorm adjoint of 2048 (pixel, 4 channels) items per tile), patch staging 146 us - and the three still
 // ADD UP: a workgroup's phases are serial, and the second workgroup of the CU does not fill the other pipe (starting half of
@@ -911,7 +700,7 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                                                                   const double* __restrict__ sums, float* __restrict__ dw,
                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta, int N, int T,
                                                                   int H, int W, int Ho, int Wo, int Hp, int Wp, int TY, int TX,
-                                                                  int ntiles, unsigned long long* stamp, int ablate) {
+                                                                  int ntiles, unsigned long long* stamp) {
     using Tm = BfTerms<NT>;
     constexpr int NPL = Tm::NPL;
     typedef __attribute__((address_space(3))) bf16x4* lds_p;
@@ -1020,7 +809,7 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 }
             }
         }
-        if (tile + (int)gridDim.x < ntiles && !(ablate & 4)) fetch_patch(tile + gridDim.x);      // in flight under this tile's k-steps
+        if (tile + (int)gridDim.x < ntiles) fetch_patch(tile + gridDim.x);      // in flight under this tile's k-steps
 #pragma unroll 1
         for (int hf = 0; hf < 2; ++hf) {
             if (hf) __syncthreads();      // the first half's k-steps are done with the dconv planes
@@ -1029,76 +818,72 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             // once per half: the column's two pool-window candidates (index, validity, position inside the window), the channel
             // constants of the BatchNorm adjoint, the LDS slot.  The nine loads of an item (conv value, four pool candidates:
             // arg-max bytes + pooled gradient) are issued together.
-            if (!(ablate & 8)) {
-                const int pcol = tid >> 4;
-                const int ow = tx * ST_TW + pcol, owc = min(ow, Wo - 1);
-                const int pw0 = owc >> 1;
-                const int pwb[2] = {min(pw0, Wp - 1), min(pw0 + 1, Wp - 1)};
-                const bool vb[2] = {true, (owc & 1) && pw0 + 1 < Wp};
-                const int posb[2] = {owc - 2 * pwb[0] + 1, owc - 2 * pwb[1] + 1};
-                const float4 mu = *reinterpret_cast<const float4*>(kc + 0 * 64 + c4), is = *reinterpret_cast<const float4*>(kc + 1 * 64 + c4);
-                const float4 ga = *reinterpret_cast<const float4*>(kc + 2 * 64 + c4), be = *reinterpret_cast<const float4*>(kc + 3 * 64 + c4);
-                const float4 mg = *reinterpret_cast<const float4*>(kc + 4 * 64 + c4), mgx = *reinterpret_cast<const float4*>(kc + 5 * 64 + c4);
-                const float4 gi = make_float4(ga.x * is.x, ga.y * is.y, ga.z * is.z, ga.w * is.w);
+            const int pcol = tid >> 4;
+            const int ow = tx * ST_TW + pcol, owc = min(ow, Wo - 1);
+            const int pw0 = owc >> 1;
+            const int pwb[2] = {min(pw0, Wp - 1), min(pw0 + 1, Wp - 1)};
+            const bool vb[2] = {true, (owc & 1) && pw0 + 1 < Wp};
+            const int posb[2] = {owc - 2 * pwb[0] + 1, owc - 2 * pwb[1] + 1};
+            const float4 mu = *reinterpret_cast<const float4*>(kc + 0 * 64 + c4), is = *reinterpret_cast<const float4*>(kc + 1 * 64 + c4);
+            const float4 ga = *reinterpret_cast<const float4*>(kc + 2 * 64 + c4), be = *reinterpret_cast<const float4*>(kc + 3 * 64 + c4);
+            const float4 mg = *reinterpret_cast<const float4*>(kc + 4 * 64 + c4), mgx = *reinterpret_cast<const float4*>(kc + 5 * 64 + c4);
+            const float4 gi = make_float4(ga.x * is.x, ga.y * is.y, ga.z * is.z, ga.w * is.w);
 #pragma unroll 1
-                for (int u = 0; u < 4; ++u) {
-                    const int oh = ty * ST_TH + 4 * hf + u, ohc = min(oh, Ho - 1);
-                    const int ph0 = ohc >> 1;
-                    const int pha[2] = {min(ph0, Hp - 1), min(ph0 + 1, Hp - 1)};
-                    const bool va[2] = {true, (ohc & 1) && ph0 + 1 < Hp};
-                    float4 cv = make_float4(0.f, 0.f, 0.f, 0.f), dq[4];
-                    uint32_t am[4];
-                    if (!(ablate & 2)) {
-                        cv = *reinterpret_cast<const float4*>(conv + (((long)img * Ho + ohc) * Wo + owc) * 64 + c4);
+            for (int u = 0; u < 4; ++u) {
+                const int oh = ty * ST_TH + 4 * hf + u, ohc = min(oh, Ho - 1);
+                const int ph0 = ohc >> 1;
+                const int pha[2] = {min(ph0, Hp - 1), min(ph0 + 1, Hp - 1)};
+                const bool va[2] = {true, (ohc & 1) && ph0 + 1 < Hp};
+                const float4 cv = *reinterpret_cast<const float4*>(conv + (((long)img * Ho + ohc) * Wo + owc) * 64 + c4);
+                float4 dq[4];
+                uint32_t am[4];
 #pragma unroll
-                        for (int ca = 0; ca < 2; ++ca) {
-                            const long rowo = ((long)img * Hp + pha[ca]) * Wp;
+                for (int ca = 0; ca < 2; ++ca) {
+                    const long rowo = ((long)img * Hp + pha[ca]) * Wp;
 #pragma unroll
-                            for (int cb2 = 0; cb2 < 2; ++cb2) {
-                                const long o = (rowo + pwb[cb2]) * 64 + c4;
-                                am[ca * 2 + cb2] = *reinterpret_cast<const uint32_t*>(argmax + o);
-                                dq[ca * 2 + cb2] = *reinterpret_cast<const float4*>(dpool + o);
-                            }
-                        }
+                    for (int cb2 = 0; cb2 < 2; ++cb2) {
+                        const long o = (rowo + pwb[cb2]) * 64 + c4;
+                        am[ca * 2 + cb2] = *reinterpret_cast<const uint32_t*>(argmax + o);
+                        dq[ca * 2 + cb2] = *reinterpret_cast<const float4*>(dpool + o);
                     }
-                    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (oh < Ho && ow < Wo) {
-                        const float xh[4] = {(cv.x - mu.x) * is.x, (cv.y - mu.y) * is.y, (cv.z - mu.z) * is.z, (cv.w - mu.w) * is.w};
-                        const float y[4] = {xh[0] * ga.x + be.x, xh[1] * ga.y + be.y, xh[2] * ga.z + be.z, xh[3] * ga.w + be.w};
-                        // max-pool adjoint routed by the recorded arg-max (stem_gather_g's rule) times the ReLU mask
-                        float g[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int ca = 0; ca < 2; ++ca)
-#pragma unroll
-                            for (int cb2 = 0; cb2 < 2; ++cb2) {
-                                // position of the pixel inside the candidate window, or 15 (no arg-max byte has that value) when the
-                                // candidate is not a window of this pixel
-                                const int pos = (va[ca] && vb[cb2]) ? (oh - 2 * pha[ca] + 1) * 3 + posb[cb2] : 15;
-                                const uint32_t m = am[ca * 2 + cb2];
-                                const float4 dd = dq[ca * 2 + cb2];
-                                if ((int)(m & 255) == pos) g[0] += dd.x;
-                                if ((int)((m >> 8) & 255) == pos) g[1] += dd.y;
-                                if ((int)((m >> 16) & 255) == pos) g[2] += dd.z;
-                                if ((int)(m >> 24) == pos) g[3] += dd.w;
-                            }
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (!(y[k] > 0.f)) g[k] = 0.f;
-                        d.x = gi.x * (g[0] - mg.x - xh[0] * mgx.x);
-                        d.y = gi.y * (g[1] - mg.y - xh[1] * mgx.y);
-                        d.z = gi.z * (g[2] - mg.z - xh[2] * mgx.z);
-                        d.w = gi.w * (g[3] - mg.w - xh[3] * mgx.w);
-                    }
-                    uint2 pl[NPL];
-                    bf_split4<NPL>(d, pl);
-                    const int off = sw_off(16 * u + pcol, tid & 15);
-#pragma unroll
-                    for (int pq = 0; pq < NPL; ++pq) *reinterpret_cast<uint2*>(dp + pq * SW_DPLANE + off) = pl[pq];
                 }
+                float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (oh < Ho && ow < Wo) {
+                    const float xh[4] = {(cv.x - mu.x) * is.x, (cv.y - mu.y) * is.y, (cv.z - mu.z) * is.z, (cv.w - mu.w) * is.w};
+                    const float y[4] = {xh[0] * ga.x + be.x, xh[1] * ga.y + be.y, xh[2] * ga.z + be.z, xh[3] * ga.w + be.w};
+                    // max-pool adjoint routed by the recorded arg-max (stem_gather_g's rule) times the ReLU mask
+                    float g[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ca = 0; ca < 2; ++ca)
+#pragma unroll
+                        for (int cb2 = 0; cb2 < 2; ++cb2) {
+                            // position of the pixel inside the candidate window, or 15 (no arg-max byte has that value) when the
+                            // candidate is not a window of this pixel
+                            const int pos = (va[ca] && vb[cb2]) ? (oh - 2 * pha[ca] + 1) * 3 + posb[cb2] : 15;
+                            const uint32_t m = am[ca * 2 + cb2];
+                            const float4 dd = dq[ca * 2 + cb2];
+                            if ((int)(m & 255) == pos) g[0] += dd.x;
+                            if ((int)((m >> 8) & 255) == pos) g[1] += dd.y;
+                            if ((int)((m >> 16) & 255) == pos) g[2] += dd.z;
+                            if ((int)(m >> 24) == pos) g[3] += dd.w;
+                        }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (!(y[k] > 0.f)) g[k] = 0.f;
+                    d.x = gi.x * (g[0] - mg.x - xh[0] * mgx.x);
+                    d.y = gi.y * (g[1] - mg.y - xh[1] * mgx.y);
+                    d.z = gi.z * (g[2] - mg.z - xh[2] * mgx.z);
+                    d.w = gi.w * (g[3] - mg.w - xh[3] * mgx.w);
+                }
+                uint2 pl[NPL];
+                bf_split4<NPL>(d, pl);
+                const int off = sw_off(16 * u + pcol, tid & 15);
+#pragma unroll
+                for (int pq = 0; pq < NPL; ++pq) *reinterpret_cast<uint2*>(dp + pq * SW_DPLANE + off) = pl[pq];
             }
             __syncthreads();
 #pragma unroll 1
-            for (int sr = (ablate & 1) ? 4 : 0; sr < 4; ++sr) {          // k-step = pixel row 4 hf + sr of the tile
+            for (int sr = 0; sr < 4; ++sr) {          // k-step = pixel row 4 hf + sr of the tile
                 bf16x8 a[2][NPL];
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -1158,8 +943,6 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     flush(accx, 8, wave & 1);      // (two wavefronts per co tile: partial sums over alternate k-steps)
     sbl_stamp_end(stamp);
 }
-int g_sbl_stem_ablate = 0;        // knob 13 (measurement only, WRONG RESULTS): stem_wgrad_tr_kernel without 1 the k-steps, 2 the dconv loads, 4 the patch loads, 8 the dconv phase
-int g_sbl_stem_wgrad_tr = 1;      // sbl_set_tuning knob 12: 1 = the kernel above (default), 0 = stem_wgrad_bf_kernel
 
 // ------------------------------------------------------------------ host entry points
 static int stem_dims(const char* who, int N, int T, int H, int W) {
@@ -1178,15 +961,9 @@ extern "C" int sbl_stem_conv_fwd(const float* x, const float* w, float* conv_out
     SBL_REQUIRE(ntiles < (1L << 31), "sbl_stem_conv_fwd: too many tiles");
     SBL_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 128, s));
     if (g_sbl_prec) {
-        int e;
-        if (g_sbl_stem_fwd8)
-            e = g_sbl_prec == 6 ? stem_launch_fwd_bf2<6>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-              : g_sbl_prec == 3 ? stem_launch_fwd_bf2<3>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-                                : stem_launch_fwd_bf2<1>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
-        else
-            e = g_sbl_prec == 6 ? stem_launch_fwd_bf<6>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-              : g_sbl_prec == 3 ? stem_launch_fwd_bf<3>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-                                : stem_launch_fwd_bf<1>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
+        const int e = g_sbl_prec == 6 ? stem_launch_fwd_bf2<6>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
+                    : g_sbl_prec == 3 ? stem_launch_fwd_bf2<3>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
+                                      : stem_launch_fwd_bf2<1>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
         if (e) return e;
         SBL_LAUNCH_CHECK("sbl_stem_conv_fwd(bf16)");
         return 0;
@@ -1258,8 +1035,7 @@ extern "C" int sbl_stem_wgrad(const float* x, const float* conv_out, const float
     const long ntiles = (long)N * T * TY * TX;
     SBL_REQUIRE(ntiles < (1L << 31), "sbl_stem_wgrad: too many tiles");
     SBL_HIP(hipMemsetAsync(dw, 0, sizeof(float) * 64 * ST_K, s));
-    const int grid = (int)(ntiles < 768 ? ntiles : 768);   // 3 workgroups per CU (52 KB LDS each)
-    if (g_sbl_prec && g_sbl_stem_wgrad_tr) {
+    if (g_sbl_prec) {
         const int grid2 = (int)(ntiles < 512 ? ntiles : 512);   // 2 workgroups per CU (77 KB LDS each)
 #define SBL_SWT_(NT)                                                                                                           \
     do {                                                                                                                       \
@@ -1272,25 +1048,16 @@ extern "C" int sbl_stem_wgrad(const float* x, const float* conv_out, const float
             set_[dev & 63] = true;                                                                                             \
         }                                                                                                                      \
         hipLaunchKernelGGL(stem_wgrad_tr_kernel<NT>, dim3(grid2), dim3(SW_THREADS), lds, s, x, conv_out, dpooled, argmax, mean, invstd, gamma, \
-                           beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM), g_sbl_stem_ablate); \
+                           beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM)); \
     } while (0)
         if (g_sbl_prec == 6) SBL_SWT_(6);
         else if (g_sbl_prec == 3) SBL_SWT_(3);
         else SBL_SWT_(1);
 #undef SBL_SWT_
-        SBL_LAUNCH_CHECK("sbl_stem_wgrad(bf16, transposed reads)");
-        return 0;
-    }
-    if (g_sbl_prec) {
-#define SBL_SWG_(NT) hipLaunchKernelGGL(stem_wgrad_bf_kernel<NT>, dim3(grid), dim3(256), 0, s, x, conv_out, dpooled, argmax, mean, invstd, gamma, \
-                       beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM))
-        if (g_sbl_prec == 6) SBL_SWG_(6);
-        else if (g_sbl_prec == 3) SBL_SWG_(3);
-        else SBL_SWG_(1);
-#undef SBL_SWG_
         SBL_LAUNCH_CHECK("sbl_stem_wgrad(bf16)");
         return 0;
     }
+    const int grid = (int)(ntiles < 768 ? ntiles : 768);   // 3 workgroups per CU (52 KB LDS each)
     hipLaunchKernelGGL(stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, x, conv_out, dpooled, argmax, mean, invstd, gamma,
                        beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
     SBL_LAUNCH_CHECK("sbl_stem_wgrad");

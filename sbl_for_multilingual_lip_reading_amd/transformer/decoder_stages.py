@@ -342,7 +342,7 @@ class DecoderStagesFn(torch.autograd.Function):
         # 928-row products that cannot fill the chip.  (Issuing it after backward has passed the encoder measured slower for the
         # whole step, 31.95 against 31.46 ms in a same-box A/B: the encoder's own launches get 2-3x faster without 2688 tiles
         # beside them, but the chip idles under them and the grouped launch then competes with the throughput-bound frontend
-        # backward.  Capping its grid to 128 / 192 workgroups, sbl_set_tuning knob 6: 33.69 / 32.01 ms.)
+        # backward.  Capping its grid to 128 / 192 workgroups, 33.69 / 32.01 ms.)
         run = side if side is not None else main
         if run is not main:
             run.wait_stream(main)
