@@ -61,6 +61,8 @@ int sbl_profile_last_kernel(void);
  *   3  two planes, three products (~2^-17 per product);   1  plain bf16 inputs with fp32 accumulation — BASELINE
  *      config 5 "mixed bf16" (fp32 master weights, fp32 accumulate).
  * Inputs and outputs stay fp32 in memory in every mode.  Returns SBL_ERR_INVALID for any other value.
+ * Dense products small enough for the register-only skinny kernel (skinny_gemm.h; sbl_profile_last_kernel() == 1) are
+ * multiplied in exact fp32 in EVERY mode: the setting reaches the tiled kernels only.
  * The value is read at enqueue time and baked into captured hipGraphs (re-capture after changing it).  Mode 6's
  * "exact split" holds for |x| >= 2^-110 or x == 0; residual planes of smaller magnitudes underflow bf16's range. */
 int sbl_set_matmul_precision(int terms);
@@ -68,8 +70,10 @@ int sbl_get_matmul_precision(void);
 /* Routing switches (process-wide, read at enqueue time like the precision).  Each chooses between two shipped kernel
  * families for the 3x3 / stride-1 trunk convolutions in the split-bf16 modes; the suite uses them to run the second
  * family on the large maps.  Any other knob, or a value a knob does not take, returns SBL_ERR_INVALID.
- * knob 5: 2 (default) patch-resident forward / input-gradient kernel for the 22x22 and 11x11 trunk maps; 0 the per-tap
- *         gather kernels;
+ * knob 5: 2 (default) patch-resident forward / input-gradient kernel on every map whose tile sbl_conv_patch_tile accepts; 0
+ *         the per-tap gather / position-major kernels.  The tile comes from an LDS budget per bf16 plane, so the maps depend
+ *         on the mode: 22x22 and 28x28 (rows of one image) and 11x11 (2 images per tile) in bf16x6, bf16x3 and bf16; 6x6 (7
+ *         images), 7x7 (5), 4x4 (16) and 4x5 / 5x4 (12) in bf16x3 and bf16 only; 3x3 (28 images) in bf16 only;
  * knob 9: patch-resident weight gradient for maps of at least `value` pixels (default 30: the 22x22, 11x11 and 6x6
  *         layers; 0 = the implicit-GEMM weight gradients everywhere). */
 int sbl_set_tuning(int knob, int value);

@@ -74,7 +74,8 @@ extern "C" int sbl_conv2d_fwd(const float* x, const float* w, float* y, double* 
         }                                                                                                      \
     } while (0)
     if (KH == 3 && stride == 1) {
-        // layers 1 and 2: the input patch of a tile staged once in LDS for all nine taps (conv_patch.h)
+        // every map sbl_conv_patch_tile accepts in the current mode (layers 1 and 2 in all split-bf16 modes, layers 3 and 4 too
+        // at two planes / one plane): the input patch of a tile staged once in LDS for all nine taps (conv_patch.h)
         bool done;
         const PatchEpi pe{y, stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         if (stats) done = sbl_launch_conv_patch<false, 1>(x, w, pe, NIMG, H, W, Cin, Cout, SBL_KID_CONV_FWD, s);
@@ -247,7 +248,7 @@ static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NI
     const long t128 = (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128);
     SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * SBL_CONV_WS_COUNTERS), "sbl_conv2d_dgrad: workspace unaligned or < 16 KiB");
     if (KH == 3 && stride == 1) {
-        // large maps: patch-resident kernel with mirrored taps (conv_patch.h); same epilogue functors
+        // the maps sbl_conv_patch_tile accepts (see sbl_conv2d_fwd): patch-resident kernel with mirrored taps (conv_patch.h)
         bool done;
         const PatchEpi pe{dx, f.sums, f.addend, f.y, f.x, f.mean, f.inv, f.x2, f.mean2, f.inv2};
         if (f.sums) done = sbl_launch_conv_patch<true, 2>(dy, wt, pe, NIMG, H, W, Cout, Cin, SBL_KID_CONV_DGRAD, s);

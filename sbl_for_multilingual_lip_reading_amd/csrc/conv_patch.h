@@ -1,5 +1,8 @@
 // Patch-resident 3x3 / stride-1 convolution for the large trunk maps (ResNet layer 1: 22x22 x 64 channels, tiles of 11 rows;
-// layer 2: 11x11 x 128 channels, tiles of two whole images), split-bf16 modes.
+// layer 2: 11x11 x 128 channels, tiles of two whole images), split-bf16 modes.  sbl_conv_patch_tile sizes the tile from an LDS
+// budget PER PLANE, so with two planes (bf16x3) and one (bf16) the small maps of layers 3 and 4 fit as well and take this
+// kernel with many whole images per tile: 6x6 -> 7 images, 7x7 -> 5, 4x4 -> 16, 4x5 / 5x4 -> 12 (bf16x3 and bf16), 3x3 -> 28
+// (bf16 only); at three planes (bf16x6) those maps stay with the position-major kernels.
 //
 // The implicit-GEMM kernels of mfma_gemm.h treat every tap as its own K range: each of the nine taps re-gathers its operand
 // from global memory and re-splits it into bf16 planes (9x the loads and conversions; 0.6-0.9 GB fetched per launch for
