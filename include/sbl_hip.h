@@ -141,6 +141,25 @@ int sbl_stem_wgrad(const float* x, const float* conv_out, const float* dpooled, 
                    const float* mean, const float* invstd, const float* gamma, const float* beta, const double* sums,
                    float* dw, float* dgamma, float* dbeta, int N, int T, int H, int W, sbl_stream_t stream);
 
+/* The same two kernels fed by the loader's uint8 frames: the device input pipeline of sbl_preprocess_clips (below) folded
+ * into the stem's patch staging, so the fp32 clip (N,Tout,Hc,Wc) never exists - not in HBM, not saved for backward.  The
+ * staged value of clip coordinate (n, tt, ih, iw) is lut256[in[n, src_frame[n,tt], y1[n]+ih, x1[n] + (flip[n] ? Wc-1-iw : iw)]]
+ * (the table entry itself: no arithmetic on the byte), and 0 where src_frame[n,tt] < 0, in the convolution's padding, and
+ * wherever the resolved coordinate leaves the (Tin,Hin,Win) frames - a bad crop origin or frame index reads as zero, never
+ * out of bounds.  in, lut256, y1, x1, flip, src_frame: exactly sbl_preprocess_clips' arguments; (Tout,Hc,Wc) take the place
+ * of sbl_stem_conv_fwd's (T,H,W) and obey its rules (Hc, Wc multiples of 4, >= 8), Hc <= Hin, Wc <= Win, N*Tin*Hin*Win < 2^31.
+ * conv_out / dw are bit-identical to sbl_preprocess_clips + sbl_stem_conv_fwd / sbl_stem_wgrad up to the order of the float
+ * atomics (stats, dw), in every sbl_set_matmul_precision mode.  Replaces SBL/data_gen.py:104-108,122-125,276-296 and
+ * cvtransforms.py:7-48 (the loader's float pipeline) in front of SBL/transformer/video_frontend.py:99-104. */
+int sbl_stem_conv_fwd_u8(const uint8_t* in, const float* lut256, const int* y1, const int* x1, const int* flip,
+                         const int* src_frame, const float* w /*[64][245]*/, float* conv_out, double* stats, int N, int Tin,
+                         int Hin, int Win, int Tout, int Hc, int Wc, sbl_stream_t stream);
+int sbl_stem_wgrad_u8(const uint8_t* in, const float* lut256, const int* y1, const int* x1, const int* flip,
+                      const int* src_frame, const float* conv_out, const float* dpooled, const uint8_t* argmax,
+                      const float* mean, const float* invstd, const float* gamma, const float* beta, const double* sums,
+                      float* dw, float* dgamma, float* dbeta, int N, int Tin, int Hin, int Win, int Tout, int Hc, int Wc,
+                      sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- BatchNorm (train / eval)
  * nn.BatchNorm{2,3}d defaults: SBL/transformer/video_frontend.py:21,24,71,101. */
 int sbl_bn_finalize(const double* stats /*[2C]*/, long count, float* running_mean, float* running_var,

@@ -19,6 +19,8 @@ SIGNATURES = {
     "sbl_stem_bn_relu_pool_fwd": [P, P, P, P, P, P, P, I, I, I, P],
     "sbl_stem_bwd_reduce": [P, P, P, P, P, P, P, P, I, I, I, P],
     "sbl_stem_wgrad": [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, P],
+    "sbl_stem_conv_fwd_u8": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "sbl_stem_wgrad_u8": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_bn_finalize": [P, L, P, P, F, F, P, P, I, P, P],
     "sbl_bn_eval_stats": [P, P, F, P, P, I, P],
     "sbl_bn_apply_fwd": [P, P, P, P, P, P, P, L, I, I, P],

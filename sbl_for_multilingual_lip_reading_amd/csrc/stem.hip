@@ -11,6 +11,8 @@
 #include "sbl_common.h"
 #include "bf16_split.h"
 #include "tuning.h"
+#include <type_traits>
+#include <utility>
 
 #define ST_TH 8
 #define ST_TW 16
@@ -47,8 +49,123 @@ __device__ __forceinline__ void st_load_patch(float* patch, const float* __restr
     }
 }
 
+// ------------------------------------------------------------------ patch sources
+// Every kernel that stages an input patch is a template over where the patch comes from.  `const float*` is the fp32 clip
+// (N,T,H,W): those instantiations are the code above / below unchanged (the kernel argument stays a __restrict__ pointer:
+// StemKArg).  StemSrcU8 is the loader's uint8 frames
+// (N,Tin,Hin,Win) plus the per-clip crop origin, flip flag and source-frame map of sbl_preprocess_clips (misc.hip), and the
+// 256-entry normalisation table: the value staged for clip coordinate (n, tt, ih, iw) is
+//     lut[in[n, src_frame[n,tt], y1[n] + ih, x1[n] + (flip[n] ? W-1-iw : iw)]]
+// - the table entry itself, so the floats that reach the MFMAs are bit for bit those of the fp32 clip that
+// sbl_preprocess_clips would have written - and 0 for a zero frame (src_frame < 0), for the convolution's padding, and for
+// any resolved coordinate outside (Tin,Hin,Win): a bad index from a loader reads as zero, never out of bounds.
+//   * The table lives in LDS with a 257th entry 0.0f; a staged element travels as an INDEX 0..256 (256 = "zero"), so the
+//     global phase of a loader is byte loads only (what the prefetching kernels keep in flight under their MFMAs) and the
+//     table lookup happens when the registers are written to LDS.  1028 bytes per workgroup: 80,760 -> 81,788 of the 81,920
+//     that let two fp32-forward workgroups share a CU, 77.5 KB for the transposed weight gradient (two per CU).
+//   * The eight per-clip integers of a tile (five source frames, y1, x1, flip) are workgroup-uniform.  They are loaded one
+//     tile AHEAD of the byte loads that depend on them (StemRawIdx: nothing is derived from the loaded registers before
+//     st_raw_resolve), so no loader waits on a load -> load chain.  The five frame offsets stay in scalar registers: item u
+//     of a thread lies in one of two patch frames known at compile time (st_fo_item), so nothing indexes them at run time
+//     (a per-element select over an array of five put the array into scratch, and a scratch load in front of every byte load).
+struct StemSrcU8 {
+    const uint8_t* __restrict__ in;
+    const float* __restrict__ lut;
+    const int* __restrict__ y1;
+    const int* __restrict__ x1;
+    const int* __restrict__ flip;
+    const int* __restrict__ src_frame;
+    int Tin, Hin, Win;
+};
+template <class Src> struct StemKArg { typedef Src type; };
+template <> struct StemKArg<const float*> { typedef const float* __restrict__ type; };
+template <class Src> constexpr bool st_is_raw = std::is_same<Src, StemSrcU8>::value;
+#define ST_LUT 257                                   // table entries in LDS: 256 byte values + the zero entry
+#define ST_PRE ((ST_PT * ST_PFS + 255) / 256)        // patch elements per thread of a 256-thread loader (17)
+struct StemRawIdx {      // as loaded
+    int sf[ST_PT], y1, x1, flip;
+};
+struct StemRawTile {     // resolved: element offset of each source frame (-1 = zero frame), sx = xb + xm * iw
+    int fo0, fo1, fo2, fo3, fo4;      // (named scalars, read through st_fo<K>: an array indexed per element ends up in scratch)
+    unsigned y1, xb;
+    int xm;
+};
+template <int K> __device__ __forceinline__ int st_fo(const StemRawTile& rt) {      // patch frame K >= ST_PT: past the patch, zero
+    if constexpr (K == 0) return rt.fo0;
+    else if constexpr (K == 1) return rt.fo1;
+    else if constexpr (K == 2) return rt.fo2;
+    else if constexpr (K == 3) return rt.fo3;
+    else if constexpr (K == 4) return rt.fo4;
+    else return -1;
+}
+// Thread tid's item U of a loader is element i = min(tid + 256 U, LAST) of EPF-element frames: one of two frames known at
+// compile time
+template <int U, int EPF, int LAST> __device__ __forceinline__ int st_fo_item(const StemRawTile& rt, int i) {
+    constexpr int F0 = (U * 256) / EPF;
+    static_assert((U * 256 + 255 < LAST ? U * 256 + 255 : LAST) / EPF <= F0 + 1, "an item spans two frames at most");
+    return i < (F0 + 1) * EPF ? st_fo<F0>(rt) : st_fo<F0 + 1>(rt);
+}
+template <int... U, class F> __device__ __forceinline__ void st_static_for(std::integer_sequence<int, U...>, F&& f) {
+    (f(std::integral_constant<int, U>{}), ...);
+}
+__device__ __forceinline__ void st_lut_fill(float* s_lut, const StemSrcU8& s, int tid, int nthreads) {
+    for (int i = tid; i < ST_LUT; i += nthreads) s_lut[i] = i < 256 ? s.lut[i] : 0.f;
+}
+__device__ __forceinline__ void st_raw_idx_load(StemRawIdx& q, const StemSrcU8& s, int n, int t, int T) {
+#pragma unroll
+    for (int f = 0; f < ST_PT; ++f) q.sf[f] = s.src_frame[n * T + min(max(t + f - 2, 0), T - 1)];
+    q.y1 = s.y1[n];
+    q.x1 = s.x1[n];
+    q.flip = s.flip[n];
+}
+__device__ __forceinline__ StemRawTile st_raw_resolve(const StemRawIdx& q, const StemSrcU8& s, int n, int t, int T, int W) {
+    StemRawTile r;
+    auto frame = [&](int f) {
+        const int sf = __builtin_amdgcn_readfirstlane(q.sf[f]);
+        const bool ok = (unsigned)(t + f - 2) < (unsigned)T && (unsigned)sf < (unsigned)s.Tin;
+        return ok ? (n * s.Tin + sf) * (s.Hin * s.Win) : -1;      // (the host checks N*Tin*Hin*Win < 2^31)
+    };
+    r.fo0 = frame(0), r.fo1 = frame(1), r.fo2 = frame(2), r.fo3 = frame(3), r.fo4 = frame(4);
+    const unsigned x1 = (unsigned)__builtin_amdgcn_readfirstlane(q.x1);
+    const bool fl = __builtin_amdgcn_readfirstlane(q.flip) != 0;
+    r.y1 = (unsigned)__builtin_amdgcn_readfirstlane(q.y1);
+    r.xb = fl ? x1 + (unsigned)(W - 1) : x1;
+    r.xm = fl ? -1 : 1;
+    return r;
+}
+// Element offset into `in` of clip coordinate (ih, iw) of the frame at offset fo, or -1 where the staged value is zero.
+// Unsigned (wrapping) sums: whatever y1 / x1 hold, an offset >= 0 lies inside the frame.
+__device__ __forceinline__ int st_raw_off(const StemRawTile& rt, const StemSrcU8& s, int fo, int ih, int iw, int H, int W) {
+    const unsigned sy = rt.y1 + (unsigned)ih, sx = rt.xb + (unsigned)(rt.xm * iw);
+    const bool ok = fo >= 0 && (unsigned)ih < (unsigned)H && (unsigned)iw < (unsigned)W &&
+                    sy < (unsigned)s.Hin && sx < (unsigned)s.Win;
+    return ok ? fo + (int)sy * s.Win + (int)sx : -1;
+}
+__device__ __forceinline__ int st_raw_ld(const StemSrcU8& s, int off) {      // table index of an element: no branch around the load
+    const int b = s.in[max(off, 0)];
+    return off >= 0 ? b : 256;
+}
+// The 5 x 21 x 40 patch of tile (ty, tx) as table indices, element i = tid + 256 u (the layout of st_load_patch), all loads
+// of a thread issued together; then indices -> LDS through the table.
+__device__ __forceinline__ void st_raw_fetch(int (&pre)[ST_PRE], const StemSrcU8& s, const StemRawTile& rt, int ty, int tx, int H,
+                                             int W, int tid) {
+    const int ih0 = 2 * ty * ST_TH - 3, iw0 = 2 * tx * ST_TW - 3;
+    st_static_for(std::make_integer_sequence<int, ST_PRE>{}, [&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        const int i = tid + u * 256;
+        const int c = i % ST_PWS, r = (i / ST_PWS) % ST_PH;
+        pre[u] = st_raw_ld(s, c < ST_PW ? st_raw_off(rt, s, st_fo_item<u, ST_PFS, ST_PRE * 256>(rt, i), ih0 + r, iw0 + c, H, W) : -1);
+    });
+}
+__device__ __forceinline__ void st_raw_put(float* patch, const float* s_lut, const int (&pre)[ST_PRE], int tid) {
+#pragma unroll
+    for (int u = 0; u < ST_PRE; ++u)
+        if (tid + u * 256 < ST_PT * ST_PFS) patch[tid + u * 256] = s_lut[pre[u]];
+}
+
 // ------------------------------------------------------------------ pass 1: conv + statistics
-__global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+template <class Src>
+__global__ __launch_bounds__(256) void stem_conv_fwd_kernel(Src src, const float* __restrict__ w,
                                                             float* __restrict__ out, double* __restrict__ stats, int N,
                                                             int T, int H, int W, int Ho, int Wo, int TY, int TX,
                                                             int ntiles, unsigned long long* stamp) {
@@ -57,6 +174,17 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restr
     __shared__ float patch[ST_PT * ST_PFS];
     float (*red)[128] = reinterpret_cast<float (*)[128]>(patch);   // reused after the tile loop: 80.8 KB total => 2 WG/CU
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const float* x = nullptr;
+    float* s_lut = nullptr;
+    StemRawIdx qi;
+    if constexpr (st_is_raw<Src>) {
+        __shared__ float lut_s[ST_LUT];      // (81.8 KB with it: still 2 WG/CU)
+        s_lut = lut_s;
+        st_lut_fill(s_lut, src, tid, 256);
+        if ((int)blockIdx.x < ntiles) st_raw_idx_load(qi, src, (int)blockIdx.x / (TX * TY) / T, (int)blockIdx.x / (TX * TY) % T, T);
+    } else {
+        x = src;
+    }
 
     for (int i = tid; i < 64 * ST_K; i += 256) {   // w[co][k] -> Ws[k][co]
         const int co = i / ST_K, k = i - co * ST_K;
@@ -75,7 +203,16 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restr
         const int img = tile / (TX * TY);
         const int n = img / T, t = img - n * T;
         __syncthreads();   // previous tile's patch reads done (also orders the Ws fill on the first trip)
-        st_load_patch(patch, x, n, t, ty, tx, T, H, W, tid);
+        if constexpr (st_is_raw<Src>) {
+            const StemRawTile rt = st_raw_resolve(qi, src, n, t, T, W);
+            const int nx = tile + (int)gridDim.x;      // the next tile's clip integers: in flight under this tile
+            if (nx < ntiles) st_raw_idx_load(qi, src, nx / (TX * TY) / T, nx / (TX * TY) % T, T);
+            int pre[ST_PRE];
+            st_raw_fetch(pre, src, rt, ty, tx, H, W, tid);
+            st_raw_put(patch, s_lut, pre, tid);
+        } else {
+            st_load_patch(patch, x, n, t, ty, tx, T, H, W, tid);
+        }
         __syncthreads();
 
         f32x16 acc0, acc1;
@@ -238,8 +375,8 @@ __device__ __forceinline__ void sb_tile_compute(const float* patch, const unsign
     }
 }
 
-template <int NT>
-__global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __restrict__ x, const float* __restrict__ w,
+template <int NT, class Src>
+__global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(Src src, const float* __restrict__ w,
                                                                 float* __restrict__ out, double* __restrict__ stats, int N,
                                                                 int T, int H, int W, int Ho, int Wo, int TY, int TX,
                                                                 int ntiles, unsigned long long* stamp) {
@@ -250,6 +387,10 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
     unsigned char* wsm = sb_smem;                                              // SB_KS * 2 * NPL fragments of 1 KB
     const int tid = threadIdx.x, grp = tid >> 8, gt = tid & 255, lane = tid & 63, wave = gt >> 6, half = lane >> 5, l31 = lane & 31;
     float* patch = reinterpret_cast<float*>(sb_smem + SB_KS * 2 * NPL * 1024) + grp * SB_PATCH;
+    const float* x = nullptr;
+    float* s_lut = reinterpret_cast<float*>(sb_smem + SB_KS * 2 * NPL * 1024) + 2 * SB_PATCH;      // raw source only: ST_LUT floats more
+    if constexpr (st_is_raw<Src>) st_lut_fill(s_lut, src, tid, 512);
+    else x = src;
     // weights -> bf16 planes in fragment order: lane ln of fragment (j, c) holds channel c*32 + (ln&31), taps (row 2j + (ln>>5), kw 0..7)
     for (int u = tid; u < SB_KS * 2 * 64; u += 512) {
         const int ln = u & 63, c = (u >> 6) & 1, j = u >> 7;
@@ -267,18 +408,46 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
     float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
     const int py = 2 * wave + (l31 >> 4), px = l31 & 15;      // this lane's A-operand pixel inside the tile
     const int abase = py * 2 * ST_PWS + px * 2;
-    float pre[SB_PRE];
+    typename std::conditional<st_is_raw<Src>, int, float>::type pre[SB_PRE];      // raw source: table indices (looked up by put)
     const int npairs = (ntiles + 1) >> 1;      // pair p = tiles 2p (group 0) and 2p + 1 (group 1); trip counts are workgroup-uniform
+    StemRawIdx qi;
+    // fetch(tl): the patch of tile tl into registers.  Raw source: with the clip integers loaded one fetch earlier, and the
+    // next fetch's (tile tl + 2 gridDim of the same group) requested behind the byte loads.
+    auto fetch_raw = [&](int tl) {
+        if constexpr (st_is_raw<Src>) {
+            const int img = tl / (TX * TY);
+            const StemRawTile rt = st_raw_resolve(qi, src, img / T, img % T, T, W);
+            st_raw_fetch(pre, src, rt, (tl / TX) % TY, tl % TX, H, W, gt);
+            const int nx = tl + 2 * (int)gridDim.x;
+            if (nx < ntiles) st_raw_idx_load(qi, src, nx / (TX * TY) / T, nx / (TX * TY) % T, T);
+        }
+    };
+    if constexpr (st_is_raw<Src>) {
+        if ((int)blockIdx.x * 2 + grp < ntiles) {
+            const int img = ((int)blockIdx.x * 2 + grp) / (TX * TY);
+            st_raw_idx_load(qi, src, img / T, img % T, T);
+        }
+        __syncthreads();      // the table is complete before the first put
+    }
     if ((int)blockIdx.x < npairs && (int)blockIdx.x * 2 + grp < ntiles) {
-        sb_fetch_patch(pre, x, blockIdx.x * 2 + grp, TX, TY, T, H, W, gt);
-        sb_put_patch(patch, pre, gt);
+        if constexpr (st_is_raw<Src>) {
+            fetch_raw(blockIdx.x * 2 + grp);
+            st_raw_put(patch, s_lut, pre, gt);
+        } else {
+            sb_fetch_patch(pre, x, blockIdx.x * 2 + grp, TX, TY, T, H, W, gt);
+            sb_put_patch(patch, pre, gt);
+        }
     }
     __syncthreads();
     for (int pt = blockIdx.x; pt < npairs; pt += gridDim.x) {
         const int tile = pt * 2 + grp;
         const int npt = pt + (int)gridDim.x;
         const bool nvalid = npt < npairs && npt * 2 + grp < ntiles;
-        if (nvalid) sb_fetch_patch(pre, x, npt * 2 + grp, TX, TY, T, H, W, gt);
+        if constexpr (st_is_raw<Src>) {
+            if (nvalid) fetch_raw(npt * 2 + grp);
+        } else {
+            if (nvalid) sb_fetch_patch(pre, x, npt * 2 + grp, TX, TY, T, H, W, gt);
+        }
         if (tile < ntiles) {      // (uniform per group of four wavefronts)
             const int tx = tile % TX;
             const int ty = (tile / TX) % TY;
@@ -286,7 +455,11 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
             sb_tile_compute<NT>(patch, wsm, abase, lane, half, l31, wave, ty, tx, img, Ho, Wo, out, s1, s2);
         }
         __syncthreads();       // both groups are done reading their patches
-        if (nvalid) sb_put_patch(patch, pre, gt);
+        if constexpr (st_is_raw<Src>) {
+            if (nvalid) st_raw_put(patch, s_lut, pre, gt);
+        } else {
+            if (nvalid) sb_put_patch(patch, pre, gt);
+        }
         __syncthreads();       // next patches complete
     }
 #pragma unroll
@@ -310,20 +483,20 @@ __global__ __launch_bounds__(512) void stem_conv_fwd_bf2_kernel(const float* __r
     }
     sbl_stamp_end(stamp);
 }
-template <int NT>
-static int stem_launch_fwd_bf2(const float* x, const float* w, float* conv_out, double* stats, int N, int T, int H, int W, int Ho,
+template <int NT, class Src>
+static int stem_launch_fwd_bf2(const Src& x, const float* w, float* conv_out, double* stats, int N, int T, int H, int W, int Ho,
                                int Wo, int TY, int TX, int ntiles, hipStream_t s) {
-    constexpr int lds = SB_KS * 2 * BfTerms<NT>::NPL * 1024 + 2 * SB_PATCH * 4;
+    constexpr int lds = SB_KS * 2 * BfTerms<NT>::NPL * 1024 + 2 * SB_PATCH * 4 + (st_is_raw<Src> ? ST_LUT * 4 : 0);
     static bool set[64] = {false};
     int dev = 0;
     SBL_HIP(hipGetDevice(&dev));
     if (!set[dev & 63]) {
-        SBL_HIP(hipFuncSetAttribute((const void*)stem_conv_fwd_bf2_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        SBL_HIP(hipFuncSetAttribute((const void*)stem_conv_fwd_bf2_kernel<NT, typename StemKArg<Src>::type>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         set[dev & 63] = true;
     }
     const int npairs = (ntiles + 1) / 2;
     const int grid = npairs < 256 ? npairs : 256;          // persistent: one workgroup per CU
-    hipLaunchKernelGGL(stem_conv_fwd_bf2_kernel<NT>, dim3(grid), dim3(512), lds, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX,
+    hipLaunchKernelGGL((stem_conv_fwd_bf2_kernel<NT, typename StemKArg<Src>::type>), dim3(grid), dim3(512), lds, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX,
                        ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
     return 0;
 }
@@ -562,7 +735,8 @@ __global__ __launch_bounds__(256) void stem_bwd_reduce_kernel(const float* __res
 // dw[co][k] = sum_pixels dconv[pixel][co] * patch(pixel, k),  dconv = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)).
 // MFMA: rows = co (2 tiles), cols = k (8 tiles of 32, 245 valid), contraction over the tile's 128 pixels.
 // Wave w owns k-tiles {2w, 2w+1}; accumulators persist across the workgroup's tiles, float atomics at the end.
-__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ conv,
+template <class Src>
+__global__ __launch_bounds__(256) void stem_wgrad_kernel(Src src, const float* __restrict__ conv,
                                                          const float* __restrict__ dpool, const uint8_t* __restrict__ argmax,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -574,6 +748,17 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
     __shared__ __attribute__((aligned(16))) float Ds[128 * ST_DS];
     __shared__ float patch[ST_PT * ST_PFS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l31 = lane & 31;
+    const float* x = nullptr;
+    float* s_lut = nullptr;
+    StemRawIdx qi;
+    if constexpr (st_is_raw<Src>) {
+        __shared__ float lut_s[ST_LUT];      // (52.6 KB with it: still 3 WG/CU)
+        s_lut = lut_s;
+        st_lut_fill(s_lut, src, tid, 256);
+        if ((int)blockIdx.x < ntiles) st_raw_idx_load(qi, src, (int)blockIdx.x / (TX * TY) / T, (int)blockIdx.x / (TX * TY) % T, T);
+    } else {
+        x = src;
+    }
     const double cnt = (double)N * T * Ho * Wo;
     if (blockIdx.x == 0 && tid < 64) {
         dbeta[tid] = (float)sums[tid];
@@ -607,7 +792,16 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
         const int img = tile / (TX * TY);
         const int n = img / T, t = img - n * T;
         __syncthreads();
-        st_load_patch(patch, x, n, t, ty, tx, T, H, W, tid);
+        if constexpr (st_is_raw<Src>) {
+            const StemRawTile rt = st_raw_resolve(qi, src, n, t, T, W);
+            const int nx = tile + (int)gridDim.x;      // the next tile's clip integers: in flight under this tile
+            if (nx < ntiles) st_raw_idx_load(qi, src, nx / (TX * TY) / T, nx / (TX * TY) % T, T);
+            int pre[ST_PRE];
+            st_raw_fetch(pre, src, rt, ty, tx, H, W, tid);
+            st_raw_put(patch, s_lut, pre, tid);
+        } else {
+            st_load_patch(patch, x, n, t, ty, tx, T, H, W, tid);
+        }
         // dconv tile -> Ds[pixel][co]; thread = (pixel group, channel quad), 8 passes of 16 pixels
 #pragma unroll 2
         for (int ps = 0; ps < 8; ++ps) {
@@ -692,8 +886,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
 __device__ __forceinline__ int sw_off(int row, int f) {      // 8-byte slot of channels 4f .. 4f + 3 of dconv row `row`
     return row * 128 + ((((f >> 1) ^ (((row >> 1) & 1) << 2))) << 4) + ((f & 1) << 3);
 }
-template <int NT>
-__global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_wgrad_tr_kernel(const float* __restrict__ x, const float* __restrict__ conv,
+template <int NT, class Src>
+__global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void stem_wgrad_tr_kernel(Src src, const float* __restrict__ conv,
                                                                   const float* __restrict__ dpool, const uint8_t* __restrict__ argmax,
                                                                   const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                   const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -719,6 +913,15 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     // per-channel constants of the BatchNorm adjoint in LDS:
     // [0] mean [1] invstd [2] gamma [3] beta [4] mean(g) [5] mean(g * xhat)
     float* kc = reinterpret_cast<float*>(sw_smem + 2 * NPL * SW_PLANE + NPL * SW_DPLANE);
+    const float* x = nullptr;
+    float* s_lut = kc + 6 * 64;      // raw source only: ST_LUT floats more
+    StemRawIdx qi;
+    if constexpr (st_is_raw<Src>) {
+        st_lut_fill(s_lut, src, tid, SW_THREADS);
+        if ((int)blockIdx.x < ntiles) st_raw_idx_load(qi, src, (int)blockIdx.x / (TX * TY) / T, (int)blockIdx.x / (TX * TY) % T, T);
+    } else {
+        x = src;
+    }
     if (tid < 64) {
         kc[0 * 64 + tid] = mean[tid];
         kc[1 * 64 + tid] = invstd[tid];
@@ -759,13 +962,31 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 
     // the tile's input patch as quads of 4 consecutive columns, all loads of a thread issued together (clamped addresses, the
     // out-of-range values replaced by zeros afterwards: no branch around a load)
+    // (raw source: the quads travel as table indices - four byte loads where the fp32 source has four dword loads, columns that
+    // run backwards under a flip included - and go through the table on their way into the planes)
     float4 pv[SW_PQ];
+    int pvi[st_is_raw<Src> ? SW_PQ : 1][4];
     auto fetch_patch = [&](int tile) {
         const int tx = tile % TX;
         const int ty = (tile / TX) % TY;
         const int img = tile / (TX * TY);
         const int n = img / T, t = img - n * T;
         const int ih0 = 2 * ty * ST_TH - 3, iw0 = 2 * tx * ST_TW - 3;
+        if constexpr (st_is_raw<Src>) {
+            const StemRawTile rt = st_raw_resolve(qi, src, n, t, T, W);
+            static_assert(SW_THREADS == 256, "st_fo_item counts items of 256 threads");
+            st_static_for(std::make_integer_sequence<int, SW_PQ>{}, [&](auto uc) {
+                constexpr int u = decltype(uc)::value;
+                const int i = min(tid + u * SW_THREADS, ST_PT * ST_PH * (SW_RS / 4) - 1);
+                const int j = i % (SW_RS / 4);
+                const int r = (i / (SW_RS / 4)) % ST_PH;
+                const int fo = st_fo_item<u, ST_PH * (SW_RS / 4), ST_PT * ST_PH * (SW_RS / 4) - 1>(rt, i);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) pvi[u][k] = st_raw_ld(src, st_raw_off(rt, src, fo, ih0 + r, iw0 + 4 * j + k, H, W));
+            });
+            const int nx = tile + (int)gridDim.x;      // the next fetch's clip integers, requested behind the byte loads
+            if (nx < ntiles) st_raw_idx_load(qi, src, nx / (TX * TY) / T, nx / (TX * TY) % T, T);
+        } else {
 #pragma unroll
         for (int u = 0; u < SW_PQ; ++u) {
             const int i = min(tid + u * SW_THREADS, ST_PT * ST_PH * (SW_RS / 4) - 1);
@@ -782,6 +1003,7 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
             pv[u].z = rok && (unsigned)(iw + 2) < (unsigned)W ? a2 : 0.f;
             pv[u].w = rok && (unsigned)(iw + 3) < (unsigned)W ? a3 : 0.f;
         }
+        }
     };
     if ((int)blockIdx.x < ntiles) fetch_patch(blockIdx.x);
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -796,6 +1018,7 @@ __global__ __launch_bounds__(SW_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
                 if (i < ST_PT * ST_PH * (SW_RS / 4)) {
                     const int j = i % (SW_RS / 4);
                     uint2 pl[NPL];
+                    if constexpr (st_is_raw<Src>) pv[u] = make_float4(s_lut[pvi[u][0]], s_lut[pvi[u][1]], s_lut[pvi[u][2]], s_lut[pvi[u][3]]);
                     bf_split4<NPL>(pv[u], pl);
                     const int eo = ((i / (SW_RS / 4)) * SW_RS + 4 * j) * 2;
 #pragma unroll
@@ -951,28 +1174,54 @@ static int stem_dims(const char* who, int N, int T, int H, int W) {
     return 0;
 }
 
-extern "C" int sbl_stem_conv_fwd(const float* x, const float* w, float* conv_out, double* stats, int N, int T, int H,
-                                 int W, sbl_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = stem_dims("sbl_stem_conv_fwd", N, T, H, W)) return e;
-    SBL_REQUIRE(x && w && conv_out && stats, "sbl_stem_conv_fwd: null pointer");
+template <class Src>
+static int stem_conv_fwd_any(const char* who, const Src& x, const float* w, float* conv_out, double* stats, int N, int T, int H, int W,
+                             hipStream_t s) {
     const int Ho = H / 2, Wo = W / 2, TY = sbl_cdiv(Ho, ST_TH), TX = sbl_cdiv(Wo, ST_TW);
     const long ntiles = (long)N * T * TY * TX;
-    SBL_REQUIRE(ntiles < (1L << 31), "sbl_stem_conv_fwd: too many tiles");
+    SBL_REQUIRE(ntiles < (1L << 31), "%s: too many tiles", who);
     SBL_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 128, s));
     if (g_sbl_prec) {
         const int e = g_sbl_prec == 6 ? stem_launch_fwd_bf2<6>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
                     : g_sbl_prec == 3 ? stem_launch_fwd_bf2<3>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
                                       : stem_launch_fwd_bf2<1>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
         if (e) return e;
-        SBL_LAUNCH_CHECK("sbl_stem_conv_fwd(bf16)");
+        SBL_LAUNCH_CHECK(st_is_raw<Src> ? "sbl_stem_conv_fwd_u8(bf16)" : "sbl_stem_conv_fwd(bf16)");
         return 0;
     }
     const int grid = (int)(ntiles < 512 ? ntiles : 512);   // persistent: 2 workgroups per CU (LDS-bound)
-    hipLaunchKernelGGL(stem_conv_fwd_kernel, dim3(grid), dim3(256), 0, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY,
+    hipLaunchKernelGGL(stem_conv_fwd_kernel<typename StemKArg<Src>::type>, dim3(grid), dim3(256), 0, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY,
                        TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
-    SBL_LAUNCH_CHECK("sbl_stem_conv_fwd");
+    SBL_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int sbl_stem_conv_fwd(const float* x, const float* w, float* conv_out, double* stats, int N, int T, int H,
+                                 int W, sbl_stream_t stream) {
+    if (int e = stem_dims("sbl_stem_conv_fwd", N, T, H, W)) return e;
+    SBL_REQUIRE(x && w && conv_out && stats, "sbl_stem_conv_fwd: null pointer");
+    return stem_conv_fwd_any("sbl_stem_conv_fwd", x, w, conv_out, stats, N, T, H, W, (hipStream_t)stream);
+}
+
+// The raw source's host checks: sbl_preprocess_clips' (misc.hip) plus the stem's own on the logical clip (Tout, Hc, Wc).
+static int stem_raw_src(const char* who, StemSrcU8& src, const uint8_t* in, const float* lut256, const int* y1, const int* x1,
+                        const int* flip, const int* src_frame, int N, int Tin, int Hin, int Win, int Tout, int Hc, int Wc) {
+    SBL_REQUIRE(in && lut256 && y1 && x1 && flip && src_frame, "%s: null pointer", who);
+    SBL_REQUIRE(N > 0 && Tin > 0 && Tout > 0 && Hc > 0 && Wc > 0 && Hc <= Hin && Wc <= Win,
+                "%s: bad dims N=%d Tin=%d Hin=%d Win=%d Tout=%d Hc=%d Wc=%d", who, N, Tin, Hin, Win, Tout, Hc, Wc);
+    if (int e = stem_dims(who, N, Tout, Hc, Wc)) return e;
+    SBL_REQUIRE((long)N * Tin * Hin * Win < (1L << 31), "%s: frames too large (N*Tin*Hin*Win must stay below 2^31)", who);
+    src = StemSrcU8{in, lut256, y1, x1, flip, src_frame, Tin, Hin, Win};
+    return 0;
+}
+
+extern "C" int sbl_stem_conv_fwd_u8(const uint8_t* in, const float* lut256, const int* y1, const int* x1, const int* flip,
+                                    const int* src_frame, const float* w, float* conv_out, double* stats, int N, int Tin, int Hin,
+                                    int Win, int Tout, int Hc, int Wc, sbl_stream_t stream) {
+    StemSrcU8 src;
+    if (int e = stem_raw_src("sbl_stem_conv_fwd_u8", src, in, lut256, y1, x1, flip, src_frame, N, Tin, Hin, Win, Tout, Hc, Wc)) return e;
+    SBL_REQUIRE(w && conv_out && stats, "sbl_stem_conv_fwd_u8: null pointer");
+    return stem_conv_fwd_any("sbl_stem_conv_fwd_u8", src, w, conv_out, stats, N, Tout, Hc, Wc, (hipStream_t)stream);
 }
 
 extern "C" int sbl_bn_finalize(const double* stats, long count, float* running_mean, float* running_var, float momentum,
@@ -1023,43 +1272,62 @@ extern "C" int sbl_stem_bwd_reduce(const float* conv_out, const float* dpooled, 
     return 0;
 }
 
-extern "C" int sbl_stem_wgrad(const float* x, const float* conv_out, const float* dpooled, const uint8_t* argmax,
-                              const float* mean, const float* invstd, const float* gamma, const float* beta,
-                              const double* sums, float* dw, float* dgamma, float* dbeta, int N, int T, int H, int W,
-                              sbl_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = stem_dims("sbl_stem_wgrad", N, T, H, W)) return e;
-    SBL_REQUIRE(x && conv_out && dpooled && argmax && mean && invstd && gamma && beta && sums && dw && dgamma && dbeta,
-                "sbl_stem_wgrad: null pointer");
+template <class Src>
+static int stem_wgrad_any(const char* who, const Src& x, const float* conv_out, const float* dpooled, const uint8_t* argmax,
+                          const float* mean, const float* invstd, const float* gamma, const float* beta, const double* sums, float* dw,
+                          float* dgamma, float* dbeta, int N, int T, int H, int W, hipStream_t s) {
+    SBL_REQUIRE(conv_out && dpooled && argmax && mean && invstd && gamma && beta && sums && dw && dgamma && dbeta, "%s: null pointer", who);
     const int Ho = H / 2, Wo = W / 2, TY = sbl_cdiv(Ho, ST_TH), TX = sbl_cdiv(Wo, ST_TW);
     const long ntiles = (long)N * T * TY * TX;
-    SBL_REQUIRE(ntiles < (1L << 31), "sbl_stem_wgrad: too many tiles");
+    SBL_REQUIRE(ntiles < (1L << 31), "%s: too many tiles", who);
     SBL_HIP(hipMemsetAsync(dw, 0, sizeof(float) * 64 * ST_K, s));
     if (g_sbl_prec) {
         const int grid2 = (int)(ntiles < 512 ? ntiles : 512);   // 2 workgroups per CU (77 KB LDS each)
 #define SBL_SWT_(NT)                                                                                                           \
     do {                                                                                                                       \
-        const size_t lds = 2 * BfTerms<NT>::NPL * SW_PLANE + BfTerms<NT>::NPL * SW_DPLANE + 6 * 64 * sizeof(float);                                   \
+        const size_t lds = 2 * BfTerms<NT>::NPL * SW_PLANE + BfTerms<NT>::NPL * SW_DPLANE + 6 * 64 * sizeof(float) +           \
+                           (st_is_raw<Src> ? ST_LUT * sizeof(float) : 0);                                                            \
         static bool set_[64] = {false};                                                                                        \
         int dev = 0;                                                                                                           \
         SBL_HIP(hipGetDevice(&dev));                                                                                           \
         if (!set_[dev & 63]) {                                                                                                 \
-            SBL_HIP(hipFuncSetAttribute((const void*)stem_wgrad_tr_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); \
+            SBL_HIP(hipFuncSetAttribute((const void*)stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); \
             set_[dev & 63] = true;                                                                                             \
         }                                                                                                                      \
-        hipLaunchKernelGGL(stem_wgrad_tr_kernel<NT>, dim3(grid2), dim3(SW_THREADS), lds, s, x, conv_out, dpooled, argmax, mean, invstd, gamma, \
+        hipLaunchKernelGGL((stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>), dim3(grid2), dim3(SW_THREADS), lds, s, x, conv_out, dpooled, argmax, mean, invstd, gamma, \
                            beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM)); \
     } while (0)
         if (g_sbl_prec == 6) SBL_SWT_(6);
         else if (g_sbl_prec == 3) SBL_SWT_(3);
         else SBL_SWT_(1);
 #undef SBL_SWT_
-        SBL_LAUNCH_CHECK("sbl_stem_wgrad(bf16)");
+        SBL_LAUNCH_CHECK(st_is_raw<Src> ? "sbl_stem_wgrad_u8(bf16)" : "sbl_stem_wgrad(bf16)");
         return 0;
     }
     const int grid = (int)(ntiles < 768 ? ntiles : 768);   // 3 workgroups per CU (52 KB LDS each)
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3(grid), dim3(256), 0, s, x, conv_out, dpooled, argmax, mean, invstd, gamma,
+    hipLaunchKernelGGL(stem_wgrad_kernel<typename StemKArg<Src>::type>, dim3(grid), dim3(256), 0, s, x, conv_out, dpooled, argmax, mean, invstd, gamma,
                        beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
-    SBL_LAUNCH_CHECK("sbl_stem_wgrad");
+    SBL_LAUNCH_CHECK(who);
     return 0;
+}
+
+extern "C" int sbl_stem_wgrad(const float* x, const float* conv_out, const float* dpooled, const uint8_t* argmax,
+                              const float* mean, const float* invstd, const float* gamma, const float* beta,
+                              const double* sums, float* dw, float* dgamma, float* dbeta, int N, int T, int H, int W,
+                              sbl_stream_t stream) {
+    if (int e = stem_dims("sbl_stem_wgrad", N, T, H, W)) return e;
+    SBL_REQUIRE(x, "sbl_stem_wgrad: null pointer");
+    return stem_wgrad_any("sbl_stem_wgrad", x, conv_out, dpooled, argmax, mean, invstd, gamma, beta, sums, dw, dgamma, dbeta,
+                          N, T, H, W, (hipStream_t)stream);
+}
+
+extern "C" int sbl_stem_wgrad_u8(const uint8_t* in, const float* lut256, const int* y1, const int* x1, const int* flip,
+                                 const int* src_frame, const float* conv_out, const float* dpooled, const uint8_t* argmax,
+                                 const float* mean, const float* invstd, const float* gamma, const float* beta, const double* sums,
+                                 float* dw, float* dgamma, float* dbeta, int N, int Tin, int Hin, int Win, int Tout, int Hc, int Wc,
+                                 sbl_stream_t stream) {
+    StemSrcU8 src;
+    if (int e = stem_raw_src("sbl_stem_wgrad_u8", src, in, lut256, y1, x1, flip, src_frame, N, Tin, Hin, Win, Tout, Hc, Wc)) return e;
+    return stem_wgrad_any("sbl_stem_wgrad_u8", src, conv_out, dpooled, argmax, mean, invstd, gamma, beta, sums, dw, dgamma, dbeta,
+                          N, Tout, Hc, Wc, (hipStream_t)stream);
 }

@@ -1212,22 +1212,30 @@ def refresh_packed_weights():
 
 
 class StemFn(torch.autograd.Function):
-    """frontend3D (video_frontend.py:99-104) on (N,T,H,W) clips -> pooled NHWC (N*T, H/4, W/4, 64)."""
+    """frontend3D (video_frontend.py:99-104) on (N,T,H,W) clips -> pooled NHWC (N*T, H/4, W/4, 64).  x: the fp32 clips, or a
+    RawClips - the loader's uint8 frames go straight into the convolution's patch staging (sbl_stem_conv_fwd_u8 /
+    sbl_stem_wgrad_u8), no fp32 clip is allocated and backward keeps the bytes instead."""
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, training, momentum, eps, nbt=None):
         """nbt: the BatchNorm's num_batches_tracked (int64 scalar) or None; incremented by the finalize kernel."""
-        _need_cuda(x, w, gamma, beta)
-        x = x.contiguous()
-        N, T, H, W = x.shape
-        dev = x.device
+        raw = x if isinstance(x, RawClips) else None
+        if raw is None:
+            _need_cuda(x, w, gamma, beta)
+            x = x.contiguous()
+            src, dims = (x,), tuple(x.shape)
+        else:
+            _need_cuda(*raw.tensors(), w, gamma, beta)
+            src, dims = raw.tensors(), raw.src_dims()
+        N, T, H, W = dims[0], dims[-3], dims[-2], dims[-1]
+        dev = src[0].device
         if training and any(ctx.needs_input_grad):
             zero_pool_reset(dev)          # the step starts here: one memset for every zero-initialised buffer of its backward
         Ho, Wo = H // 2, W // 2
         w2 = w.contiguous().view(64, 245)
         conv = torch.empty(N * T, Ho, Wo, 64, device=dev, dtype=torch.float32)
         stats = torch.empty(128, device=dev, dtype=torch.float64)
-        call("sbl_stem_conv_fwd", _p(x), _p(w2), _p(conv), _p(stats), N, T, H, W, _s())
+        call("sbl_stem_conv_fwd" if raw is None else "sbl_stem_conv_fwd_u8", *[_p(t) for t in src], _p(w2), _p(conv), _p(stats), *dims, _s())
         mean = torch.empty(64, device=dev, dtype=torch.float32)
         invstd = torch.empty(64, device=dev, dtype=torch.float32)
         if training:
@@ -1239,18 +1247,19 @@ class StemFn(torch.autograd.Function):
         argmax = torch.empty(N * T, Ho // 2, Wo // 2, 64, device=dev, dtype=torch.uint8)
         call("sbl_stem_bn_relu_pool_fwd", _p(conv), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(pooled), _p(argmax),
              N * T, Ho, Wo, _s())
-        ctx.save_for_backward(x, conv, argmax, mean, invstd, gamma, beta)
-        ctx.training = training
+        ctx.save_for_backward(conv, argmax, mean, invstd, gamma, beta, *src)
+        ctx.training, ctx.raw, ctx.dims = training, raw is not None, dims
         return pooled
 
     @staticmethod
     @_bw
     def backward(ctx, dpooled):
-        x, conv, argmax, mean, invstd, gamma, beta = ctx.saved_tensors
+        conv, argmax, mean, invstd, gamma, beta, *src = ctx.saved_tensors
         if not ctx.training:
             raise _lib.SblHipError("stem backward is implemented for training-mode BatchNorm (batch statistics) only")
-        N, T, H, W = x.shape
-        dev = x.device
+        dims = ctx.dims
+        N, T, H, W = dims[0], dims[-3], dims[-2], dims[-1]
+        dev = conv.device
         dpooled = dpooled.contiguous()
         sums = torch.empty(128, device=dev, dtype=torch.float64)
         call("sbl_stem_bwd_reduce", _p(conv), _p(dpooled), _p(argmax), _p(mean), _p(invstd), _p(gamma), _p(beta),
@@ -1258,8 +1267,8 @@ class StemFn(torch.autograd.Function):
         dw = torch.empty(64, 245, device=dev, dtype=torch.float32)
         dgamma = torch.empty(64, device=dev, dtype=torch.float32)
         dbeta = torch.empty(64, device=dev, dtype=torch.float32)
-        call("sbl_stem_wgrad", _p(x), _p(conv), _p(dpooled), _p(argmax), _p(mean), _p(invstd), _p(gamma), _p(beta),
-             _p(sums), _p(dw), _p(dgamma), _p(dbeta), N, T, H, W, _s())
+        call("sbl_stem_wgrad_u8" if ctx.raw else "sbl_stem_wgrad", *[_p(t) for t in src], _p(conv), _p(dpooled), _p(argmax), _p(mean),
+             _p(invstd), _p(gamma), _p(beta), _p(sums), _p(dw), _p(dgamma), _p(dbeta), *dims, _s())
         return None, dw.view(64, 1, 5, 7, 7), dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -1479,6 +1488,97 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
 _LUT = {}
 
 
+def _lut(dev, mean, std):
+    """The 256-entry normalisation table of a device, cached: float32((v/255. - mean)/std) in double, exactly the reference's
+    numpy arithmetic.  Its first use on a device copies from the host, so it must not fall inside a graph capture."""
+    key = (dev.index, mean, std)
+    lut = _LUT.get(key)
+    if lut is None:
+        lut = _LUT[key] = torch.from_numpy(((_np.arange(256, dtype=_np.float64) / 255. - mean) / std).astype(_np.float32)).to(dev)
+    return lut
+
+
+class RawClips:
+    """A batch of clips as the loader holds it: uint8 frames plus what SBL/data_gen.py:276-296 and cvtransforms.py:7-48 would do
+    to them - the arguments of preprocess_clips, kept together.  StemFn and the models (Lipreading / Transformer.forward /
+    recognize / validate, ClassifierTransformer.forward) take one wherever they take the (N,T,H,W) float clips; the stem then
+    reads the bytes directly and the float clips are never built.  Immutable; the tensors may be overwritten in place (the
+    static inputs of a captured graph).
+
+    frames_u8 (N,Tin,Hin,Win) uint8; y1, x1, flip int32 (N,): crop origin and horizontal-flip flag per clip; src_frame int32
+    (N,Tout): the source frame of every output frame, -1 = an all-zero frame (frame removal, padding to 30 frames, the CLS
+    loader's 31st frame); crop = (Hc,Wc); mean / std of ColorNormalize.  All contiguous, all on one device.  While the index
+    tensors are on the host their ranges are checked (0 <= y1, y1 + Hc <= Hin, likewise x, src_frame < Tin); device tensors
+    are not read back - an index that leaves the frames reads as zero in the kernels."""
+    __slots__ = ("frames_u8", "y1", "x1", "flip", "src_frame", "crop", "mean", "std", "_lut")
+
+    def __init__(self, frames_u8, y1, x1, flip, src_frame, crop=(88, 88), mean=0.413621, std=0.1700239):
+        def want(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise TypeError("RawClips: %s must be a %s tensor (got %s)" % (name, dtype, getattr(t, "dtype", type(t).__name__)))
+            if t.dim() != len(shape) or any(d is not None and t.size(i) != d for i, d in enumerate(shape)):
+                raise ValueError("RawClips: %s must have shape (%s), got %s" % (name, ", ".join("*" if d is None else str(d) for d in shape), tuple(t.shape)))
+            if not t.is_contiguous():
+                raise ValueError("RawClips: %s must be contiguous" % name)
+            if t.device != frames_u8.device:
+                raise ValueError("RawClips: %s is on %s, the frames on %s" % (name, t.device, frames_u8.device))
+        want("frames_u8", frames_u8, torch.uint8, (None, None, None, None))
+        N, Tin, Hin, Win = frames_u8.shape
+        for name, t in (("y1", y1), ("x1", x1), ("flip", flip)):
+            want(name, t, torch.int32, (N,))
+        want("src_frame", src_frame, torch.int32, (N, None))
+        Hc, Wc = int(crop[0]), int(crop[1])
+        if not (0 < Hc <= Hin and 0 < Wc <= Win and src_frame.size(1) > 0):
+            raise ValueError("RawClips: crop %dx%d of %dx%d frames, %d output frames" % (Hc, Wc, Hin, Win, src_frame.size(1)))
+        if not frames_u8.is_cuda:      # host tensors: a range check costs nothing (on the device it would be a sync)
+            if N and (int(y1.min()) < 0 or int(y1.max()) + Hc > Hin):
+                raise ValueError("RawClips: y1 outside [0, %d]" % (Hin - Hc))
+            if N and (int(x1.min()) < 0 or int(x1.max()) + Wc > Win):
+                raise ValueError("RawClips: x1 outside [0, %d]" % (Win - Wc))
+            if N and int(src_frame.max()) >= Tin:
+                raise ValueError("RawClips: src_frame >= Tin = %d" % Tin)
+        for k, v in (("frames_u8", frames_u8), ("y1", y1), ("x1", x1), ("flip", flip), ("src_frame", src_frame), ("crop", (Hc, Wc)),
+                     ("mean", float(mean)), ("std", float(std)),
+                     ("_lut", _lut(frames_u8.device, float(mean), float(std)) if frames_u8.is_cuda else None)):
+            object.__setattr__(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("RawClips is immutable")
+
+    @property
+    def shape(self):
+        """The logical clip shape (N,Tout,Hc,Wc)."""
+        return torch.Size((self.frames_u8.size(0), self.src_frame.size(1)) + self.crop)
+
+    @property
+    def device(self):
+        return self.frames_u8.device
+
+    def dim(self):
+        return 4
+
+    def size(self, i=None):
+        return self.shape if i is None else self.shape[i]
+
+    def to(self, device):
+        return RawClips(*(t.to(device) for t in (self.frames_u8, self.y1, self.x1, self.flip, self.src_frame)), crop=self.crop,
+                        mean=self.mean, std=self.std)
+
+    def tensors(self):
+        """The six source arguments of sbl_stem_conv_fwd_u8 / sbl_stem_wgrad_u8, in order."""
+        _need_cuda(self.frames_u8)
+        return (self.frames_u8, self._lut, self.y1, self.x1, self.flip, self.src_frame)
+
+    def src_dims(self):
+        """(N, Tin, Hin, Win, Tout, Hc, Wc)"""
+        return tuple(self.frames_u8.shape) + (self.src_frame.size(1),) + self.crop
+
+    def materialize(self):
+        """The fp32 clips (N,Tout,Hc,Wc) that preprocess_clips builds from the same arguments."""
+        return preprocess_clips(self.frames_u8, self.y1, self.x1, self.flip, self.src_frame, Tout=self.src_frame.size(1),
+                                crop=self.crop, mean=self.mean, std=self.std)
+
+
 def preprocess_clips(frames_u8, y1, x1, flip, src_frame, Tout=30, crop=(88, 88), mean=0.413621, std=0.1700239):
     """Device input pipeline (SBL/data_gen.py:276-296 + cvtransforms.py): uint8 (N,Tin,Hin,Win) grayscale frames ->
     normalised, cropped, flipped, frame-mapped, zero-padded fp32 clips (N,Tout,Hc,Wc) in one kernel.  y1/x1/flip:
@@ -1486,10 +1586,7 @@ def preprocess_clips(frames_u8, y1, x1, flip, src_frame, Tout=30, crop=(88, 88),
     _need_cuda(frames_u8, y1, x1, flip, src_frame)
     assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous()
     N, Tin, Hin, Win = frames_u8.shape
-    key = (frames_u8.device.index, mean, std)
-    lut = _LUT.get(key)
-    if lut is None:   # float32((v/255. - mean)/std) in double, exactly the reference's numpy arithmetic
-        lut = _LUT[key] = torch.from_numpy(((_np.arange(256, dtype=_np.float64) / 255. - mean) / std).astype(_np.float32)).to(frames_u8.device)
+    lut = _lut(frames_u8.device, mean, std)
     out = torch.empty(N, Tout, crop[0], crop[1], device=frames_u8.device, dtype=torch.float32)
     call("sbl_preprocess_clips", _p(frames_u8), _p(out), _p(lut), _p(y1.contiguous()), _p(x1.contiguous()), _p(flip.contiguous()),
          _p(src_frame.contiguous()), N, Tin, Hin, Win, Tout, crop[0], crop[1], _s())

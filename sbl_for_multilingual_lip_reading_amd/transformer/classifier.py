@@ -28,14 +28,17 @@ class ClassifierTransformer(nn.Module):
         self.fc_2 = nn.Linear(512, 2)
 
     def forward(self, padded_input_visual):
-        """padded_input_visual (N, T, H, W) -> (v_t (N, 1500) word logits, v_t_languages (N, 2) language logits).
+        """padded_input_visual (N, T, H, W), or an ops.RawClips of that logical shape (the 31st all-zero frame of the CLS loader
+        is then a src_frame column of -1) -> (v_t (N, 1500) word logits, v_t_languages (N, 2) language logits).
 
         The shipped forward cannot run: it averages over the feature axis (`mean(dim=2, keepdim=True)`) and then feeds the
         resulting (N, T, 1) tensor to a 512-input Linear, which raises.  This restates its evident intent, the
         same restatement as oracle.sbl_oracle.cls_forward: the word head reads the encoder output averaged over time, the
         language head reads its last frame (the reference hard-codes row 30 of its 31-frame clips).  No frame is padded
         here: the reference's loader already delivers its 31 frames.  Every clip uses its full length."""
-        feats = self.visual_frontend(padded_input_visual.unsqueeze(1))        # (N, T, 512)
+        if not isinstance(padded_input_visual, ops.RawClips):
+            padded_input_visual = padded_input_visual.unsqueeze(1)
+        feats = self.visual_frontend(padded_input_visual)        # (N, T, 512)
         lengths = [feats.size(1)] * feats.size(0)
         enc, *_ = self.encoder_v(feats, lengths)
         return ops.ClsHeadFn.apply(enc, self.fc_1500.weight, self.fc_1500.bias, self.fc_2.weight, self.fc_2.bias,

@@ -2,6 +2,7 @@
 bidirectional decoder."""
 import torch.nn as nn
 
+from ._env import ops
 from .video_frontend import visual_frontend
 
 
@@ -18,21 +19,24 @@ class Transformer(nn.Module):
             nn.init.xavier_uniform_(w)
 
     def _encode(self, frames):
-        """frames (N, T, H, W) grayscale -> (encoder output (N, T, 512), lengths): every clip uses all its frames
-        (the reference passes full lengths too)."""
-        feats = self.visual_frontend(frames.unsqueeze(1))       # (N, 1, T, H, W): one input channel
+        """frames (N, T, H, W) grayscale, or an ops.RawClips of that logical shape (the loader's uint8 frames: no float clip is
+        built) -> (encoder output (N, T, 512), lengths): every clip uses all its frames (the reference passes full lengths
+        too)."""
+        if not isinstance(frames, ops.RawClips):
+            frames = frames.unsqueeze(1)                        # (N, 1, T, H, W): one input channel
+        feats = self.visual_frontend(frames)
         lengths = [feats.size(1)] * feats.size(0)
         enc, *_ = self.encoder(feats, lengths)
         return enc, lengths
 
     def forward(self, padded_input, padded_target_l2r, padded_target_r2l):
-        """padded_input (N, T, H, W); targets (N, To), IGNORE_ID padded.
+        """padded_input (N, T, H, W) or ops.RawClips; targets (N, To), IGNORE_ID padded.
         Returns (pred_l2r (N, 16, 58), gold_l2r (N, 16), pred_r2l, gold_r2l)."""
         enc, lengths = self._encode(padded_input)
         return self.decoder(padded_target_l2r, padded_target_r2l, enc, lengths)
 
     def recognize(self, input):
-        """Greedy bidirectional decode of (N, T, H, W) crops: (ys_l2r, ys_r2l), int64 (N, 17)."""
+        """Greedy bidirectional decode of (N, T, H, W) crops (or ops.RawClips): (ys_l2r, ys_r2l), int64 (N, 17)."""
         enc, _ = self._encode(input)
         return self.decoder.recognize_beam(enc)
 

@@ -121,7 +121,8 @@ class Lipreading(nn.Module):
         _he_init(self.modules())      # again over the trunk too: its draws are overwritten but advance the RNG
 
     def _frontend_forward(self, x):
-        """x: (N, 1, T, H, W) or (N, T, H, W) -> (N*T, 512)"""
+        """x: (N, 1, T, H, W) or (N, T, H, W) float clips, or an ops.RawClips (uint8 frames, fed to the stem as they are)
+        -> (N*T, 512)"""
         if x.dim() == 5:
             x = x[:, 0]
         conv, bn = self.frontend3D[0], self.frontend3D[1]
