@@ -398,6 +398,38 @@ int sbl_smoothed_ce_bwd(const float* pred, const int64_t* gold, const float* out
 int sbl_seq_score(const int64_t* ys_l2r, const int64_t* ys_r2l, int Ly, const int64_t* gold_l2r, const int64_t* gold_r2l,
                   int To, int N, int64_t sos, int64_t eos, int64_t ignore, const uint64_t* names, int n_names,
                   const int32_t* valid_rows, int32_t* per_sample, uint64_t* acc, sbl_stream_t stream);
+/* The same scoring for ONE direction: the single-direction seq2seq model, LRW/train.py:245-260 (predictions cut at
+ * len(gold) + 1 and stripped of sos / eos / -1, :247-249).  ys (N, Ly) is the row of Seq2SeqTransformer.recognize, acc uint64
+ * (SBL_SCORE_COUNTERS), per_sample NULL or int32 (3, N).  Same definition, deviations and counters as sbl_seq_score. */
+int sbl_seq_score1(const int64_t* ys, int Ly, const int64_t* gold, int To, int N, int64_t sos, int64_t eos, int64_t ignore,
+                   const uint64_t* names, int n_names, const int32_t* valid_rows, int32_t* per_sample, uint64_t* acc,
+                   sbl_stream_t stream);
+
+/* ---------------------------------------------------------------- single-direction seq2seq decoder (LRW/transformer/decoder.py)
+ * out[b,l,:] = emb[tok[b*ldt + pos0 + l]] * scale + pe[pos0 + l], l < L: decoder.py:111-112 (teacher-forced, pos0 = 0, L = 14)
+ * and :154-156 (greedy).  scale is x_logit_scale: d_model^-0.5 when the embedding is tied to the output projection, else 1. */
+int sbl_embed_scale_pe_fwd(const int64_t* tok, long ldt, const float* emb, const float* pe, float* out, int B, int L, int D,
+                           int V, float scale, int pos0, sbl_stream_t stream);
+/* demb[tok[b*ldt + l]] += scale * dy[b,l,:] (float atomics; demb is accumulated into) */
+int sbl_embed_scale_bwd(const int64_t* tok, long ldt, const float* dy, float* demb, int B, int L, int D, int V, float scale,
+                        sbl_stream_t stream);
+/* One greedy step of attention with a K/V cache: replaces the prefix recompute of decoder.py:146-164 (every step there runs
+ * attention.py:32-60 over the whole prefix; the decoder is causal, so row i needs only the new query and the keys 0..i).
+ * One wavefront per (clip, head), d = 64.  q (B, H*64) rows of stride ldq: the step's query.  k_cache / v_cache:
+ * (B, Lcap, H*64) with row stride ldc and batch stride Lcap*ldc (independent of the current length), Lcap <= 64.
+ * append = 1 (self-attention): the step's new rows k_new / v_new (B, H*64), stride ldn, are stored at cache row n_prev and the
+ * query attends to rows 0..n_prev.  append = 0 (cross-attention over the hoisted encoder K/V): rows 0..n_prev-1, nothing is
+ * written.  n_prev is the step index, a launch argument.  o (B, H*64), stride ldo = softmax(q K^T * scale) V, fp32. */
+int sbl_decode_attn_step(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                         float* v_cache, long ldc, int Lcap, float* o, long ldo, int B, int H, int n_prev, int append,
+                         float scale, sbl_stream_t stream);
+/* Tail of a greedy step in one launch (decoder.py:166-171, then :154-156 of the next step): logits = y w^T (bias-free
+ * Linear(512, V), V <= 64; plain fp32 FMA in every sbl_set_matmul_precision mode), ys[b, step+1] = arg-max (lowest index on
+ * ties), and - x_next != NULL - x_next[b,:] = emb[that token] * emb_scale + pe[step+1], the next step's input row.  logits:
+ * NULL or (B, V) with row stride ldl.  D must be 512; pe has pe_rows rows. */
+int sbl_decode_tail(const float* y, long ldy, const float* w, float* logits, long ldl, int64_t* ys, long ldys, int step,
+                    const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next, int B, int V, int D,
+                    sbl_stream_t stream);
 
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)

@@ -66,6 +66,11 @@ SIGNATURES = {
     "sbl_argmax_select": [P, L, P, L, P, L, I, I, P, I, I, P],
     "sbl_decoder_preprocess": [P, P, P, P, P, P, I, I, I, L, L, L, P],
     "sbl_seq_score": [P, P, I, P, P, I, I, L, L, L, P, I, P, P, P, P],
+    "sbl_seq_score1": [P, I, P, I, I, L, L, L, P, I, P, P, P, P],
+    "sbl_embed_scale_pe_fwd": [P, L, P, P, P, I, I, I, I, F, I, P],
+    "sbl_embed_scale_bwd": [P, L, P, P, I, I, I, I, F, P],
+    "sbl_decode_attn_step": [P, L, P, P, L, P, P, L, I, P, L, I, I, I, I, F, P],
+    "sbl_decode_tail": [P, L, P, P, L, P, L, I, P, P, I, F, P, I, I, I, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
     "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],

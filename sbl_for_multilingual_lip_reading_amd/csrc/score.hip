@@ -170,3 +170,21 @@ extern "C" int sbl_seq_score(const int64_t* ys_l2r, const int64_t* ys_r2l, int L
     SBL_LAUNCH_CHECK("sbl_seq_score");
     return 0;
 }
+
+// One direction (the single-direction seq2seq model, LRW/train.py:245-260): the same kernel with a grid of one direction;
+// acc is one row of SBL_SCORE_COUNTERS counters, per_sample int32 (3, N).
+extern "C" int sbl_seq_score1(const int64_t* ys, int Ly, const int64_t* gold, int To, int N, int64_t sos, int64_t eos,
+                              int64_t ignore, const uint64_t* names, int n_names, const int32_t* valid_rows, int32_t* per_sample,
+                              uint64_t* acc, sbl_stream_t stream) {
+    SBL_REQUIRE(N >= 0, "sbl_seq_score1: N=%d", N);
+    SBL_REQUIRE(To >= 1 && To <= SCORE_MAX_TO, "sbl_seq_score1: target width To=%d outside 1..%d", To, SCORE_MAX_TO);
+    SBL_REQUIRE(Ly >= 1, "sbl_seq_score1: prediction width Ly=%d", Ly);
+    SBL_REQUIRE((names != nullptr) == (n_names > 0), "sbl_seq_score1: name table and n_names=%d disagree", n_names);
+    SBL_REQUIRE(acc, "sbl_seq_score1: null accumulator");
+    if (N == 0) return 0;
+    SBL_REQUIRE(ys && gold, "sbl_seq_score1: null token tensor");
+    hipLaunchKernelGGL(seq_score_kernel, dim3(sbl_cdiv(N, 64), 1), dim3(64), 0, (hipStream_t)stream, ys, ys, Ly, gold, gold, To, N,
+                       sos, eos, ignore, names, n_names, valid_rows, per_sample, (unsigned long long*)acc);
+    SBL_LAUNCH_CHECK("sbl_seq_score1");
+    return 0;
+}

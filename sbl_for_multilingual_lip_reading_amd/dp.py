@@ -25,7 +25,9 @@ def _ordered_params(model):
     fused = []
     cross = []
     dec = getattr(model, "decoder", None)
-    if dec is not None and hasattr(dec, "_layers"):
+    if dec is not None and hasattr(dec, "cross_attention_modules"):
+        cross = list(dec.cross_attention_modules())      # the single-direction decoder (seq2seq.py): layers 0.. of one stack
+    elif dec is not None and hasattr(dec, "_layers"):
         cross = [lay.enc_attn for d in (0, 1) for lay in dec._layers(d)]
     cross_ids = {id(m) for m in cross}
     if cross:
@@ -215,11 +217,13 @@ class GradientExchange:
 
         for name, seg in feeds:
             self._hooks.append(getattr(model, name).register_forward_hook(on_output(seg)))
-        res = getattr(model.visual_frontend, "resnet18", None)
+        # the frontend submodule is `visual_frontend`, or what the model class names as FLAT_FRONTEND (seq2seq: `lipreading`)
+        front = getattr(model, "FLAT_FRONTEND", "visual_frontend")
+        res = getattr(getattr(model, front), "resnet18", None)
         if res is not None:
             for k in (4, 3, 2):
                 self._hooks.append(getattr(res, "layer%d" % k).register_forward_pre_hook(
-                    stage_pre_hook("visual_frontend.resnet18.layer%d." % k)))
+                    stage_pre_hook("%s.resnet18.layer%d." % (front, k))))
 
     def close(self):
         """Remove the forward hooks (the exchange then only runs when launch() / finish() are called explicitly)."""

@@ -1694,16 +1694,107 @@ def seq_score(ys_l2r, ys_r2l, gold_l2r, gold_r2l, acc, sos_id, eos_id, ignore_id
         raise ValueError("seq_score: target width To=%d outside 1..%d" % (To, SCORE_MAX_TO))
     live = torch.arange(N) < (N if valid_rows is None else min(max(int(valid_rows[0]), 0), N))
     for d, (ys, gold) in enumerate(((ys_l2r, gold_l2r), (ys_r2l, gold_r2l))):
-        dist, c, werr = _seq_score_cpu(ys, gold, sos_id, eos_id, ignore_id, names)
-        if per_sample is not None:
-            per_sample[d] = torch.where(live, torch.stack((dist, c, werr)), torch.full((), -1, dtype=torch.int64)).to(torch.int32)
-        scored = live & (c > 0)
-        a = acc[d]
-        a[SCORE_N_SCORED] += scored.sum()
-        a[SCORE_N_EMPTY] += (live & (c == 0)).sum()
-        a[SCORE_N_WORD_ERR] += werr[scored].sum()
-        a[SCORE_SUM_DIST] += dist[scored].sum()
-        a[SCORE_SUM_LEN] += c[scored].sum()
-        a[SCORE_DIST_BY_LEN:SCORE_DIST_BY_LEN + 16].index_add_(0, c[scored], dist[scored])
-        a[SCORE_COUNT_BY_LEN:SCORE_COUNT_BY_LEN + 16].index_add_(0, c[scored], torch.ones_like(c[scored]))
+        _score_accumulate_cpu(acc[d], None if per_sample is None else per_sample[d], live,
+                              *_seq_score_cpu(ys, gold, sos_id, eos_id, ignore_id, names))
     return acc
+
+
+def _score_accumulate_cpu(a, per, live, dist, c, werr):
+    """Add one direction's per-sample (dist, c, word_err) to its counter row `a` (and write them to `per`, int32 (3, N))."""
+    if per is not None:
+        per.copy_(torch.where(live, torch.stack((dist, c, werr)), torch.full((), -1, dtype=torch.int64)).to(torch.int32))
+    scored = live & (c > 0)
+    a[SCORE_N_SCORED] += scored.sum()
+    a[SCORE_N_EMPTY] += (live & (c == 0)).sum()
+    a[SCORE_N_WORD_ERR] += werr[scored].sum()
+    a[SCORE_SUM_DIST] += dist[scored].sum()
+    a[SCORE_SUM_LEN] += c[scored].sum()
+    a[SCORE_DIST_BY_LEN:SCORE_DIST_BY_LEN + 16].index_add_(0, c[scored], dist[scored])
+    a[SCORE_COUNT_BY_LEN:SCORE_COUNT_BY_LEN + 16].index_add_(0, c[scored], torch.ones_like(c[scored]))
+
+
+def seq_score1(ys, gold, acc, sos_id, eos_id, ignore_id, names=None, valid_rows=None, per_sample=None):
+    """seq_score for ONE direction (include/sbl_hip.h, sbl_seq_score1; the single-direction model, LRW/train.py:245-260).
+    ys int64 (N, Ly), gold int64 (N, To <= 15), acc int64 (SCORE_COUNTERS,), per_sample None or int32 (3, N).  On the GPU one
+    launch, no sync, no allocation; CPU tensors take the same definition in vectorised torch.  Returns acc."""
+    N, Ly = ys.shape
+    To = gold.size(1)
+    if gold.shape != (N, To) or not all(t.dtype == torch.int64 and t.is_contiguous() for t in (ys, gold)):
+        raise ValueError("seq_score1: ys / gold must be contiguous int64 (N, Ly) / (N, To), got %s %s" % (tuple(ys.shape), tuple(gold.shape)))
+    if acc.shape != (SCORE_COUNTERS,) or acc.dtype != torch.int64 or not acc.is_contiguous():
+        raise ValueError("seq_score1: acc must be a contiguous int64 (%d,) tensor" % SCORE_COUNTERS)
+    if names is not None and (names.dtype != torch.int64 or names.dim() != 1 or names.numel() < 1 or not names.is_contiguous()):
+        raise ValueError("seq_score1: names must be the int64 table of pack_names")
+    if valid_rows is not None and (valid_rows.dtype != torch.int32 or valid_rows.numel() != 1):
+        raise ValueError("seq_score1: valid_rows must be an int32[1] tensor")
+    if per_sample is not None and (per_sample.shape != (3, N) or per_sample.dtype != torch.int32 or not per_sample.is_contiguous()):
+        raise ValueError("seq_score1: per_sample must be a contiguous int32 (3, %d) tensor" % N)
+    every = (ys, gold, acc) + tuple(t for t in (names, valid_rows, per_sample) if t is not None)
+    if any(t.device != acc.device for t in every):
+        raise ValueError("seq_score1: tensors on different devices")
+    if acc.is_cuda:
+        call("sbl_seq_score1", _p(ys), Ly, _p(gold), To, N, sos_id, eos_id, ignore_id, _p(names),
+             0 if names is None else names.numel(), _p(valid_rows), _p(per_sample), _p(acc), _s())
+        return acc
+    if not 1 <= To <= SCORE_MAX_TO:
+        raise ValueError("seq_score1: target width To=%d outside 1..%d" % (To, SCORE_MAX_TO))
+    live = torch.arange(N) < (N if valid_rows is None else min(max(int(valid_rows[0]), 0), N))
+    _score_accumulate_cpu(acc, per_sample, live, *_seq_score_cpu(ys, gold, sos_id, eos_id, ignore_id, names))
+    return acc
+
+
+# --------------------------------------------------------------------------- #
+# single-direction seq2seq decoder (LRW/transformer/decoder.py): scaled embedding, KV-cached greedy step
+# --------------------------------------------------------------------------- #
+class EmbedScalePEFn(torch.autograd.Function):
+    """emb[tok] * scale + pe[:L]; LRW/transformer/decoder.py:111-112.  tok: int64 (B, L) (any row stride).  The gradient of
+    `emb` is the scatter-add of scale * dy; when `emb` is also the output projection's weight (tgt_emb_prj_weight_sharing)
+    autograd - or the shared flat gradient slice both kernels accumulate into - sums it with the projection's."""
+
+    @staticmethod
+    def forward(ctx, tok, emb, pe, scale):
+        _need_cuda(tok, emb, pe)
+        B, L = tok.shape
+        V, D = emb.shape
+        assert tok.dtype == torch.int64 and tok.stride(1) == 1 and pe.size(0) >= L and pe.is_contiguous() and emb.is_contiguous()
+        out = torch.empty(B, L, D, device=emb.device, dtype=torch.float32)
+        call("sbl_embed_scale_pe_fwd", _p(tok), tok.stride(0), _p(emb), _p(pe), _p(out), B, L, D, V, scale, 0, _s())
+        ctx.tok, ctx.cfg = tok, (B, L, V, D, scale)
+        ctx.gb = _gbuf(emb)
+        return out
+
+    @staticmethod
+    @_bw
+    def backward(ctx, dy):
+        B, L, V, D, scale = ctx.cfg
+        dy = dy.contiguous()
+        demb, _, demb_ret = _target(ctx.gb, (V, D), dy.device, zero=True)
+        call("sbl_embed_scale_bwd", _p(ctx.tok), ctx.tok.stride(0), _p(dy), _p(demb), B, L, D, V, scale, _s())
+        return None, demb_ret, None, None
+
+
+def decode_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append, scale=0.125):
+    """One (clip, head) wavefront each: the single new query row attends to the cache (include/sbl_hip.h,
+    sbl_decode_attn_step).  q / k_new / v_new / out: (B, H*64) row views (column slices of wider buffers are fine);
+    k_cache / v_cache: views whose first element is row 0 of clip 0, row stride .stride(-2), batch stride Lcap rows."""
+    B = q.size(0)
+    ldc = k_cache.stride(-2)
+    assert v_cache.stride(-2) == ldc and k_cache.stride(-1) == 1 and q.stride(1) == 1 and out.stride(1) == 1
+    assert k_cache.dim() == 3 and k_cache.size(0) == B and k_cache.size(1) == Lcap and k_cache.stride(0) == Lcap * ldc
+    assert v_cache.shape == k_cache.shape and v_cache.stride(0) == Lcap * ldc
+    if append:
+        assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
+    call("sbl_decode_attn_step", _p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache),
+         _p(v_cache), ldc, Lcap, _p(out), out.stride(0), B, H, int(n_prev), int(bool(append)), scale, _s())
+    return out
+
+
+def decode_tail(y, w, ys, step, emb, pe, emb_scale, x_next=None, logits=None):
+    """Greedy step tail in one launch (sbl_decode_tail): ys[:, step+1] = argmax(y w^T); x_next = emb[token] * emb_scale +
+    pe[step+1] (the next step's input row) when given; logits (B, V) are written when given."""
+    B, D = y.shape
+    V = w.size(0)
+    assert y.stride(1) == 1 and w.is_contiguous() and ys.dtype == torch.int64 and ys.stride(1) == 1
+    assert x_next is None or (x_next.is_contiguous() and x_next.shape == (B, D) and pe.is_contiguous() and emb.is_contiguous())
+    call("sbl_decode_tail", _p(y), y.stride(0), _p(w), _p(logits), 0 if logits is None else logits.stride(0), _p(ys), ys.stride(0),
+         int(step), _p(emb), _p(pe), pe.size(0), emb_scale, _p(x_next), B, V, D, _s())

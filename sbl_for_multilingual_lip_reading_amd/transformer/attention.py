@@ -45,6 +45,9 @@ class MultiHeadAttention(nn.Module):
         nn.init.normal_(self.fc.weight, std=math.sqrt(2.0 / (n_head * d_v + d_model)))
 
         self.dropout = nn.Dropout(dropout)
+        # True when an owner keeps this module's (w_ks, w_vs) inside a block it lays out itself (the seq2seq decoder's
+        # all-layers cross-attention K/V block): _fuse then leaves the parameters where they are
+        self.kv_in_block = False
 
     def _fuse(self):
         """Re-point w_qs/w_ks/w_vs parameters at adjacent rows of one buffer (idempotent, cheap pointer check).
@@ -53,7 +56,7 @@ class MultiHeadAttention(nn.Module):
         bs = (self.w_qs.bias, self.w_ks.bias, self.w_vs.bias)
         if ops._adjacent(*ws) and ops._adjacent(*bs):
             return
-        if getattr(ws[0], "_sbl_flat", None) is not None:
+        if getattr(ws[0], "_sbl_flat", None) is not None or self.kv_in_block:
             # parameters of a dp.FlatModel are never re-allocated here.  Its layout keeps self-attention triples adjacent;
             # the decoder's cross-attention modules have (w_ks, w_vs) adjacent inside the all-layers K/V block instead,
             # which is all the cross-attention path (KVProjectFn / decoder_stages) needs

@@ -34,12 +34,20 @@ class ErrorRateMeter:
         self.sos_id, self.eos_id, self.ignore_id = int(sos_id), int(eos_id), int(ignore_id)
         self.names = None if names is None else ops.pack_names(names).to(self.device)
         self.acc = torch.zeros(2, ops.SCORE_COUNTERS, dtype=torch.int64, device=self.device)
+        self.single = False          # set by update_single: result() then also reports the un-prefixed single-direction keys
 
     def update(self, ys_l2r, ys_r2l, gold_l2r, gold_r2l, valid_rows=None):
         """Score one batch and add it: one launch on the current stream, no sync, no allocation (capturable).
         valid_rows: None or a device int32[1]; rows at or beyond it are ignored."""
         ops.seq_score(ys_l2r, ys_r2l, gold_l2r, gold_r2l, self.acc, self.sos_id, self.eos_id, self.ignore_id,
                       names=self.names, valid_rows=valid_rows)
+
+    def update_single(self, ys, gold, valid_rows=None):
+        """Score one batch of a single-direction model (seq2seq.Seq2SeqTransformer; LRW/train.py:245-260: predictions cut at
+        len(gold) + 1 and stripped of sos / eos / IGNORE_ID) and add it to the first counter row: one launch of
+        sbl_seq_score1, no sync, no allocation.  The second row stays zero."""
+        self.single = True
+        ops.seq_score1(ys, gold, self.acc[0], self.sos_id, self.eos_id, self.ignore_id, names=self.names, valid_rows=valid_rows)
 
     def all_reduce(self, group=None):
         """Sum the counters over the ranks of a torch.distributed group (RCCL on the GPU, gloo on CPU tensors): every
@@ -65,6 +73,8 @@ class ErrorRateMeter:
             out[tag + "_per_corpus"] = a[d][ops.SCORE_SUM_DIST] / a[d][ops.SCORE_SUM_LEN] if n else nan
             out["n" if d == 0 else "r2l_n"] = n
             out["n_empty" if d == 0 else "r2l_n_empty"] = a[d][ops.SCORE_N_EMPTY]
+        if self.single:      # a single-direction model: "wer", "per", "per_corpus" (with "n", "n_empty") are its result
+            out.update(wer=out["l2r_wer"], per=out["l2r_per"], per_corpus=out["l2r_per_corpus"])
         return out
 
 

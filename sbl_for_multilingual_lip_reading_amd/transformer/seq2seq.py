@@ -1,0 +1,295 @@
+"""The single-direction phoneme seq2seq model: the reference's VSR_seq2seq_Transformer_with_phonemes_LRW/ ("LRW/" below; the
+LRW1000 directory has the same classes with a 48-token vocabulary), the baseline the SBL model is measured against.
+
+Seq2SeqDecoder / Seq2SeqTransformer keep the constructor and forward signatures and the state-dict keys of
+LRW/transformer/decoder.py:Decoder and LRW/transformer/transformer.py:Transformer.  The teacher-forced pass is built from the
+entry points the SBL model uses; the greedy decode keeps a K/V cache per layer and processes one new row per clip and step
+(csrc/decode_step.hip) instead of re-running the whole prefix at every step as LRW/transformer/decoder.py:146-164 does: every
+layer of this decoder is causal, so row i of every sub-layer depends on rows <= i only."""
+import torch
+import torch.nn as nn
+
+from ._env import _lib, config, ops
+from .decoder import DecoderLayer
+from .module import PositionalEncoding
+from .utils import get_attn_pad_mask
+from .video_frontend import Lipreading
+
+IGNORE_ID = config.IGNORE_ID
+MAX_TGT_LEN = 14          # pad_list's fixed max_len (LRW/transformer/utils.py:5): <sos> + at most 13 tokens
+MAX_KEYS = 64             # one key per lane in the decode-step attention; the teacher-forced kernels share the bound
+
+
+class Seq2SeqDecoder(nn.Module):
+    """n_layers causal decoder layers over one target direction (LRW/transformer/decoder.py:19-176).
+
+    With tgt_emb_prj_weight_sharing the output projection and the embedding are ONE parameter and the embedding is scaled
+    by x_logit_scale = d_model ** -0.5 (decoder.py:57-62); otherwise they are separate and the scale is 1."""
+
+    def __init__(
+            self, sos_id, eos_id,
+            n_tgt_vocab, d_word_vec,
+            n_layers, n_head, d_k, d_v,
+            d_model, d_inner, dropout=0.1,
+            tgt_emb_prj_weight_sharing=True,
+            pe_maxlen=5000):
+        super(Seq2SeqDecoder, self).__init__()
+        if d_model != 512 or d_word_vec != d_model or d_k != 64 or d_v != 64:
+            raise _lib.SblHipError("Seq2SeqDecoder: the HIP kernels are built for d_model = d_word_vec = 512 and d_k = d_v = 64 "
+                                   "(got %d, %d, %d, %d)" % (d_model, d_word_vec, d_k, d_v))
+        if not 1 <= n_tgt_vocab <= 64:
+            raise _lib.SblHipError("Seq2SeqDecoder: n_tgt_vocab = %d outside 1..64 (the decode tail keeps one class per lane)"
+                                   % n_tgt_vocab)
+        self.sos_id = sos_id
+        self.eos_id = eos_id
+        self.n_tgt_vocab = n_tgt_vocab
+        self.d_word_vec = d_word_vec
+        self.n_layers = n_layers
+        self.n_head = n_head
+        self.d_k = d_k
+        self.d_v = d_v
+        self.d_model = d_model
+        self.d_inner = d_inner
+        self.tgt_emb_prj_weight_sharing = tgt_emb_prj_weight_sharing
+        self.pe_maxlen = pe_maxlen
+
+        self.tgt_word_emb = nn.Embedding(n_tgt_vocab, d_word_vec)
+        self.positional_encoding = PositionalEncoding(d_model, max_len=pe_maxlen)
+        self.dropout = nn.Dropout(dropout)
+        self.layer_stack = nn.ModuleList(DecoderLayer(d_model, d_inner, n_head, d_k, d_v, dropout=dropout)
+                                         for _ in range(n_layers))
+        self.tgt_word_prj = nn.Linear(d_model, n_tgt_vocab, bias=False)
+        nn.init.xavier_normal_(self.tgt_word_prj.weight)
+        if tgt_emb_prj_weight_sharing:
+            self.tgt_word_prj.weight = self.tgt_word_emb.weight
+            self.x_logit_scale = d_model ** -0.5
+        else:
+            self.x_logit_scale = 1.
+
+    # ------------------------------------------------------------------ parameter layout
+    def cross_attention_modules(self):
+        """The layers' cross-attention modules, in layer order.  Their [w_ks; w_vs] rows (and biases) form one block
+        [K_0; V_0; K_1; ...] so that the encoder output's K / V for ALL layers are one GEMM in recognize_beam;
+        dp.FlatModel lays the block out itself, otherwise _fuse() does."""
+        return [lay.enc_attn for lay in self.layer_stack]
+
+    def _fuse(self):
+        """Idempotent (pointer checks): q/k/v of every self-attention adjacent, the cross-attention K/V block adjacent."""
+        for lay in self.layer_stack:
+            lay.slf_attn._fuse()
+        mods = self.cross_attention_modules()
+        ws = [w for m in mods for w in (m.w_ks.weight, m.w_vs.weight)]
+        bs = [b for m in mods for b in (m.w_ks.bias, m.w_vs.bias)]
+        for m in mods:
+            m.kv_in_block = True
+        if ops._adjacent(*ws) and ops._adjacent(*bs):
+            return
+        if getattr(ws[0], "_sbl_flat", None) is not None:
+            raise _lib.SblHipError("Seq2SeqDecoder: the flat model's cross-attention K/V block is not contiguous")
+        with torch.no_grad():
+            fw = torch.cat([w.data for w in ws], 0).contiguous()
+            fb = torch.cat([b.data for b in bs], 0).contiguous()
+            if fw.is_cuda:      # one-time set-up: the old storages are released below, so the copies must have run
+                torch.cuda.current_stream(fw.device).synchronize()
+            r = 0
+            for w, b in zip(ws, bs):
+                n = w.size(0)
+                w.data = fw[r:r + n]
+                b.data = fb[r:r + n]
+                r += n
+
+    # ------------------------------------------------------------------ teacher-forced pass
+    def preprocess(self, padded_input):
+        """decoder.py:64-79: strip IGNORE_ID; ys_in = <sos> + y padded with eos, ys_out = y + <eos> padded with IGNORE_ID,
+        both (N, 14).  Vectorised on the input's device: no per-row loop, no host sync."""
+        N, To = padded_input.shape
+        if To > MAX_TGT_LEN - 1:
+            raise _lib.SblHipError("Seq2SeqDecoder: targets of width %d; at most %d tokens fit the fixed length %d "
+                                   "(LRW/transformer/utils.py:5)" % (To, MAX_TGT_LEN - 1, MAX_TGT_LEN))
+        y = padded_input.long()
+        valid = y.ne(IGNORE_ID)
+        order = torch.argsort((~valid).to(torch.int8), dim=1, stable=True)      # stable compaction of the valid ids to the left
+        comp = torch.gather(y, 1, order)
+        n_valid = valid.sum(1, keepdim=True)
+        inside = torch.arange(To, device=y.device).unsqueeze(0) < n_valid
+        ys_in = y.new_full((N, MAX_TGT_LEN), self.eos_id)
+        ys_in[:, 0] = self.sos_id
+        ys_in[:, 1:1 + To] = torch.where(inside, comp, torch.full_like(comp, self.eos_id))
+        ys_out = y.new_full((N, MAX_TGT_LEN), IGNORE_ID)
+        ys_out[:, :To] = torch.where(inside, comp, torch.full_like(comp, IGNORE_ID))
+        ys_out.scatter_(1, n_valid, self.eos_id)
+        return ys_in, ys_out
+
+    def _check_encoder(self, enc):
+        if enc.dim() != 3 or enc.size(-1) != self.d_model:
+            raise _lib.SblHipError("Seq2SeqDecoder: encoder output of shape %s, expected (N, T, %d)" % (tuple(enc.shape), self.d_model))
+        if enc.size(1) > MAX_KEYS:
+            raise _lib.SblHipError("Seq2SeqDecoder: %d encoder frames; the attention kernels hold at most %d keys" % (enc.size(1), MAX_KEYS))
+        if not enc.is_cuda:
+            raise _lib.SblHipError("Seq2SeqDecoder needs CUDA/HIP tensors (got a %s tensor); there is no CPU path" % enc.device)
+
+    def forward(self, padded_input, encoder_padded_outputs, encoder_input_lengths, return_attns=False):
+        """padded_input (N, To <= 13) IGNORE_ID-padded targets, encoder_padded_outputs (N, Ti, 512).  The one-shot
+        teacher-forced pass of decoder.py:81-136.  Returns (pred (N, 14, V), gold (N, 14)) [+ the attention lists]."""
+        enc = encoder_padded_outputs
+        self._check_encoder(enc)
+        self._fuse()
+        N, Ti, _ = enc.shape
+        ys_in, ys_out = self.preprocess(padded_input.to(enc.device))
+        L = ys_in.size(1)
+        # the K / V projections of the encoder output come first: the backward of every other decoder node then outranks
+        # theirs in autograd's ready queue, so the decoder's gradients are complete when the encoder-output gradient is
+        # (dp.GradientExchange launches the decoder segment there)
+        kv = [lay.enc_attn.project_kv(enc) for lay in self.layer_stack]
+        pad = ys_in.eq(self.eos_id)
+        non_pad_mask = (~pad).float().unsqueeze(-1)
+        future = torch.ones((L, L), dtype=torch.bool, device=enc.device).triu(1)
+        slf_attn_mask = pad.unsqueeze(1) | future.unsqueeze(0)                   # key-pad OR causal, (N, L, L)
+        if all(int(n) >= Ti for n in encoder_input_lengths):
+            dec_enc_attn_mask = None                                              # full lengths: the mask is a no-op
+        else:
+            dec_enc_attn_mask = get_attn_pad_mask(enc, encoder_input_lengths, L)
+        x = ops.EmbedScalePEFn.apply(ys_in, self.tgt_word_emb.weight, self.positional_encoding.pe[0], float(self.x_logit_scale))
+        x = ops.dropout(x, self.dropout.p, self.training)
+        slf_list, enc_list = [], []
+        for lay, kv_l in zip(self.layer_stack, kv):
+            x, slf, cross = lay(x, enc, non_pad_mask=non_pad_mask, slf_attn_mask=slf_attn_mask,
+                                dec_enc_attn_mask=dec_enc_attn_mask, enc_kv=kv_l)
+            if return_attns:
+                slf_list.append(slf)
+                enc_list.append(cross)
+        pred = ops.linear(x, self.tgt_word_prj.weight)
+        if return_attns:
+            return pred, ys_out, slf_list, enc_list
+        return pred, ys_out
+
+    # ------------------------------------------------------------------ greedy decode
+    def recognize_beam(self, encoder_outputs, char_list=None, args=None, cached=True):
+        """Greedy decode of maxlen = Ti steps (decoder.py:138-176; char_list / args are accepted and unused, as there).
+        Returns ys int64 (N, Ti + 1), column 0 is <sos>.  cached=True: one new row per clip and step against per-layer K/V
+        caches; cached=False: the reference's loop, the whole prefix re-run at every step through the teacher-forced building
+        blocks (the statement the cached path is tested against).  No host sync either way."""
+        self._check_encoder(encoder_outputs)
+        self._fuse()
+        with torch.no_grad():
+            return self._greedy_cached(encoder_outputs) if cached else self._greedy_recompute(encoder_outputs)
+
+    def _new_ys(self, enc):
+        return torch.full((enc.size(0), enc.size(1) + 1), self.sos_id, dtype=torch.long, device=enc.device)
+
+    def _greedy_recompute(self, enc):
+        N, T, _ = enc.shape
+        kv = [lay.enc_attn.project_kv(enc) for lay in self.layer_stack]       # step-invariant
+        ys = self._new_ys(enc)
+        emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
+        for i in range(T):
+            x = ops.EmbedScalePEFn.apply(ys[:, :i + 1], emb, pe, float(self.x_logit_scale))
+            x = ops.dropout(x, self.dropout.p, self.training)
+            for lay, kv_l in zip(self.layer_stack, kv):
+                x, _, _ = lay(x, enc, non_pad_mask=None, slf_attn_mask='causal', dec_enc_attn_mask=None, enc_kv=kv_l)
+            ops.argmax_select(ops.linear(x[:, -1], w), None, ys, i, 1)
+        return ys
+
+    def _greedy_cached(self, enc):
+        if self.training and self.dropout.p > 0:
+            raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+        N, T, D = enc.shape
+        dev = enc.device
+        layers = list(self.layer_stack)
+        nl, H = len(layers), self.n_head
+        HD, F_ = H * 64, self.d_inner
+        call, gemm, _p, _s = ops.call, ops.gemm, ops._p, ops._s
+        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+
+        # the K / V of the encoder output for all layers: one GEMM against the [K_0; V_0; K_1; ...] block
+        cross = self.cross_attention_modules()
+        enc2 = enc.contiguous().view(N * T, D)
+        kv = new(N * T, nl * 2 * HD)
+        gemm(0, 1, N * T, nl * 2 * HD, D, enc2, D, cross[0].w_ks.weight, D, kv, nl * 2 * HD, bias=cross[0].w_ks.bias)
+        kv3 = kv.view(N, T, nl * 2 * HD)
+        cache = new(nl, 2, N, T, HD)          # self-attention K / V rows of every layer; row i is written at step i
+        ys = self._new_ys(enc)
+        emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
+        V, scale = emb.size(0), float(self.x_logit_scale)
+        x = new(N, D)
+        call("sbl_embed_scale_pe_fwd", _p(ys), ys.stride(0), _p(emb), _p(pe), _p(x), N, 1, D, V, scale, 0, _s())
+        qkv, q, att, o, h = new(N, 3 * HD), new(N, HD), new(N, HD), new(N, D), new(N, F_)
+        ya, yb, yc = new(N, D), new(N, D), new(N, D)
+        mean, rstd = new(N), new(N)
+
+        def add_ln(x_, res, ln, out):
+            call("sbl_add_layernorm_fwd", _p(x_), _p(res), _p(ln.weight), _p(ln.bias), _p(out), _p(mean), _p(rstd), N, D, ln.eps,
+                 0.0, None, 0, _s())
+
+        for i in range(T):
+            cur = x
+            for l, lay in enumerate(layers):
+                sa, ca, ff = lay.slf_attn, lay.enc_attn, lay.pos_ffn
+                gemm(0, 1, N, 3 * HD, D, cur, D, sa.w_qs.weight, D, qkv, 3 * HD, bias=sa.w_qs.bias)
+                ops.decode_attn_step(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], T, att, H, i, True)
+                gemm(0, 1, N, D, HD, att, HD, sa.fc.weight, HD, o, D, bias=sa.fc.bias)
+                add_ln(o, cur, sa.layer_norm, ya)
+                gemm(0, 1, N, HD, D, ya, D, ca.w_qs.weight, D, q, HD, bias=ca.w_qs.bias)
+                c0 = l * 2 * HD
+                ops.decode_attn_step(q, None, None, kv3[:, :, c0:c0 + HD], kv3[:, :, c0 + HD:c0 + 2 * HD], T, att, H, T, False)
+                gemm(0, 1, N, D, HD, att, HD, ca.fc.weight, HD, o, D, bias=ca.fc.bias)
+                add_ln(o, ya, ca.layer_norm, yb)
+                gemm(0, 1, N, F_, D, yb, D, ff.w_1.weight, D, h, F_, bias=ff.w_1.bias, relu=1)
+                gemm(0, 1, N, D, F_, h, F_, ff.w_2.weight, F_, o, D, bias=ff.w_2.bias)
+                add_ln(o, yb, ff.layer_norm, yc)
+                cur = yc
+            ops.decode_tail(cur, w, ys, i, emb, pe, scale, x_next=x if i + 1 < T else None)
+        return ys
+
+
+class Seq2SeqTransformer(nn.Module):
+    """Lip crops -> visual frontend -> encoder -> single-direction decoder (LRW/transformer/transformer.py:4-75).  Submodule
+    names `encoder`, `decoder`, `lipreading` and their registration order are the reference's, so its state-dict keys load
+    and the construction-time Xavier re-draw of every parameter of rank >= 2 (the tied weight once) consumes the RNG as it
+    does there."""
+
+    # dp.FlatModel layout (see classifier.ClassifierTransformer)
+    FLAT_SEGMENTS = ("decoder.", "encoder.", "lipreading.resnet18.layer4.", "lipreading.resnet18.layer3.",
+                     "lipreading.resnet18.layer2.", "lipreading.")
+    FLAT_FEEDS = (("encoder", "decoder."), ("lipreading", "encoder."))
+    FLAT_FRONTEND = "lipreading"
+
+    def __init__(self, encoder, decoder):
+        super(Seq2SeqTransformer, self).__init__()
+        self.encoder = encoder
+        self.decoder = decoder
+        self.lipreading = Lipreading(hiddenDim=512, embedSize=256)
+        for w in [p for p in self.parameters() if p.dim() > 1]:
+            nn.init.xavier_uniform_(w)
+
+    def _encode(self, frames):
+        """frames (N, T, H, W) grayscale or an ops.RawClips -> (encoder output (N, T, 512), full lengths)."""
+        if not isinstance(frames, ops.RawClips):
+            frames = frames.unsqueeze(1)
+        feats = self.lipreading(frames)
+        lengths = [feats.size(1)] * feats.size(0)
+        enc, *_ = self.encoder(feats, lengths)
+        return enc, lengths
+
+    def forward(self, padded_input, padded_target):
+        """padded_input (N, T, H, W) or ops.RawClips; padded_target (N, To <= 13), IGNORE_ID padded.
+        Returns (pred (N, 14, V), gold (N, 14))."""
+        enc, lengths = self._encode(padded_input)
+        pred, gold, *_ = self.decoder(padded_target, enc, lengths)
+        return pred, gold
+
+    def recognize(self, input, char_list=None, args=None, cached=True):
+        """Greedy decode of (N, T, H, W) crops (or ops.RawClips): ys int64 (N, T + 1).  In eval() under torch.no_grad() the
+        whole call is capturable as one hipGraph (no host sync, no host read of device data)."""
+        enc, _ = self._encode(input)
+        return self.decoder.recognize_beam(enc, char_list, args, cached=cached)
+
+    def validate(self, padded_input, padded_target, meter, valid_rows=None):
+        """One validation batch (the body of LRW/train.py:229-254): greedy decode, then score ys against the (N, To)
+        IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device; capturable like recognize.  Returns ys."""
+        ys = self.recognize(padded_input)
+        meter.update_single(ys, padded_target, valid_rows=valid_rows)
+        return ys
+
+
+__all__ = ["Seq2SeqDecoder", "Seq2SeqTransformer", "MAX_TGT_LEN"]
