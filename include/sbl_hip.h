@@ -338,17 +338,7 @@ int sbl_gather_last_fwd(const float* x, float* out, int B, const int* seg_L, int
 int sbl_gather_last_bwd(const float* dy, float* dx, int B, const int* seg_L, int nseg, int D, sbl_stream_t stream);
 
 /* ---------------------------------------------------------------- SBL decoder pieces
- * out[b,l,:] = emb[tok[b*ldt + l]] + pe[l]: decoder.py:116-120 */
-int sbl_embed_pe_fwd(const int64_t* tok, long ldt, const float* emb, const float* pe, float* out, int B, int L, int D,
-                     int V, sbl_stream_t stream);
-/* demb[tok] += dy (float atomics) */
-int sbl_embed_bwd(const int64_t* tok, long ldt, const float* dy, float* demb, int B, int L, int D, int V,
-                  sbl_stream_t stream);
-/* A' = A + flip_t(B), B' = 2B + flip_t(A): closed form of the aliased loops decoder.py:132-143,160-164 */
-int sbl_fusion_fwd(const float* a, const float* b, float* a2, float* b2, int B, int L, int D, sbl_stream_t stream);
-int sbl_fusion_bwd(const float* da2, const float* db2, float* da, float* db, int B, int L, int D,
-                   sbl_stream_t stream);
-/* Decoder.preprocess (decoder.py:62-77): strip IGNORE_ID, <sos> + ids (input form) / ids (label form), both padded with <eos>
+ * Decoder.preprocess (decoder.py:62-77): strip IGNORE_ID, <sos> + ids (input form) / ids (label form), both padded with <eos>
    to maxlen; int64 (N,To) -> two int64 (N,maxlen).  padded1 != NULL: a second target set (the r2l direction) in the same launch. */
 int sbl_decoder_preprocess(const int64_t* padded0, const int64_t* padded1, int64_t* ys_in0, int64_t* ys_out0, int64_t* ys_in1,
                            int64_t* ys_out1, int N, int To, int maxlen, int64_t sos, int64_t eos, int64_t ignore,

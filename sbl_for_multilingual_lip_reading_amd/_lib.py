@@ -59,10 +59,6 @@ SIGNATURES = {
     "sbl_fusion_seg_bwd": [P, P, P, P, I, P, I, I, P],
     "sbl_gather_last_fwd": [P, P, I, P, I, I, P],
     "sbl_gather_last_bwd": [P, P, I, P, I, I, P],
-    "sbl_embed_pe_fwd": [P, L, P, P, P, I, I, I, I, P],
-    "sbl_embed_bwd": [P, L, P, P, I, I, I, I, P],
-    "sbl_fusion_fwd": [P, P, P, P, I, I, I, P],
-    "sbl_fusion_bwd": [P, P, P, P, I, I, I, P],
     "sbl_argmax_select": [P, L, P, L, P, L, I, I, P, I, I, P],
     "sbl_decoder_preprocess": [P, P, P, P, P, P, I, I, I, L, L, L, P],
     "sbl_seq_score": [P, P, I, P, P, I, I, L, L, L, P, I, P, P, P, P],

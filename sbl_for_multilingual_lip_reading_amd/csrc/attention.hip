@@ -653,8 +653,7 @@ static SegDesc at_qtile_desc(int L, int Lk) {      // L query rows (two tiles), 
     return t;
 }
 static bool at_small_ok(const SegDesc& d, int Lk_fixed, int mask_kind) {
-    constexpr int enabled = 1;
-    if (!enabled || mask_kind == 2 || Lk_fixed > 32) return false;
+    if (mask_kind == 2 || Lk_fixed > 32) return false;
     for (int s = 0; s < d.nseg; ++s)
         if (d.L[s] > 16) return false;
     return true;
@@ -775,25 +774,19 @@ extern "C" int sbl_attention_seg_bwd(const float* dout, long lddo, const float* 
     if (at_small_ok(d, Lk_fixed, 0) && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && sbl_aligned16(dq) && sbl_aligned16(dk) &&
         sbl_aligned16(dv)) {
         const int nprob = nseg * B * H;
-        constexpr int shared_kv = 1;
-        if (Lk_fixed > 0 && nseg > 1 && !shared_kv) {      // atomics path accumulates: start from zero
-            SBL_HIP(hipMemset2DAsync(dk, lddk * sizeof(float), 0, (size_t)H * 64 * sizeof(float), (size_t)B * Lk_fixed, (hipStream_t)stream));
-            SBL_HIP(hipMemset2DAsync(dv, lddv * sizeof(float), 0, (size_t)H * 64 * sizeof(float), (size_t)B * Lk_fixed, (hipStream_t)stream));
-        }
         const int nwv = nseg < 8 ? nseg : 8;      // 8 wavefronts = 2 per SIMD at this kernel's register use; beyond 8 segments each
                                                    // wavefront takes several (sbl_make_segs caps nseg at SBL_MAX_SEG = 16)
-        if (shared_kv && Lk_fixed > 0 && nseg > 1) {
+        if (Lk_fixed > 0 && nseg > 1) {      // shared keys: one workgroup per (batch, head) sums the segments' dK / dV in LDS
             static bool attr_set2[64] = {false};
             if (int e = at_attr((const void*)attention_small_bwd_kernel<true>, 8 * 16384, attr_set2)) return e;
-        }
-        if (shared_kv && Lk_fixed > 0 && nseg > 1)
             hipLaunchKernelGGL(attention_small_bwd_kernel<true>, dim3(B * H), dim3(64 * nwv), (size_t)nwv * 16384, (hipStream_t)stream, dout, lddo, q,
                                ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, d, Lk_fixed, scale,
                                drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, nprob, (unsigned long long*)nullptr);
-        else
+        } else {
             hipLaunchKernelGGL(attention_small_bwd_kernel<false>, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, dout,
                                lddo, q, ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, d, Lk_fixed, scale,
                                drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, nprob, (unsigned long long*)nullptr);
+        }
         SBL_LAUNCH_CHECK("sbl_attention_bwd(small)");
         return 0;
     }

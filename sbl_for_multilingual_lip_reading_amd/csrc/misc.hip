@@ -68,14 +68,6 @@ extern "C" int sbl_embed_seg_bwd(const int64_t* tok, long ldt, const float* dy, 
     SBL_LAUNCH_CHECK("sbl_embed_bwd");
     return 0;
 }
-extern "C" int sbl_embed_pe_fwd(const int64_t* tok, long ldt, const float* emb, const float* pe, float* out, int B, int L,
-                                int D, int V, sbl_stream_t stream) {
-    return sbl_embed_pe_seg_fwd(tok, ldt, emb, pe, out, B, &L, 1, D, V, stream);
-}
-extern "C" int sbl_embed_bwd(const int64_t* tok, long ldt, const float* dy, float* demb, int B, int L, int D, int V,
-                             sbl_stream_t stream) {
-    return sbl_embed_seg_bwd(tok, ldt, dy, demb, B, &L, 1, D, V, stream);
-}
 
 // ------------------------------------------------------------------ SBL fusion: decoder.py:132-143,160-164
 // fwd: A' = A + flip(B), B' = 2B + flip(A).  bwd (adjoint): dA = dA' + flip(dB'), dB = flip(dA') + 2 dB'.
@@ -127,12 +119,6 @@ extern "C" int sbl_fusion_seg_fwd(const float* a, const float* b, float* a2, flo
 extern "C" int sbl_fusion_seg_bwd(const float* da2, const float* db2, float* da, float* db, int B, const int* seg_L, int nseg,
                                   int D, sbl_stream_t stream) {
     return fusion_common("sbl_fusion_bwd", da2, db2, da, db, B, seg_L, nseg, D, true, stream);
-}
-extern "C" int sbl_fusion_fwd(const float* a, const float* b, float* a2, float* b2, int B, int L, int D, sbl_stream_t stream) {
-    return fusion_common("sbl_fusion_fwd", a, b, a2, b2, B, &L, 1, D, false, stream);
-}
-extern "C" int sbl_fusion_bwd(const float* da2, const float* db2, float* da, float* db, int B, int L, int D, sbl_stream_t stream) {
-    return fusion_common("sbl_fusion_bwd", da2, db2, da, db, B, &L, 1, D, true, stream);
 }
 
 // ------------------------------------------------------------------ last position of every sequence: decoder.py:166-167

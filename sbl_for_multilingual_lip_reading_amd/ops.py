@@ -9,9 +9,11 @@ non-zero status raises.
 All Functions are hipGraph-capturable: no host sync, no host read of device data;
 dropout seeds and teacher-forcing coins live in device memory.
 """
+import copy as _copy
 import ctypes as _ct
 import functools as _functools
 import threading as _threading
+import types as _types
 import weakref as _weakref
 
 import numpy as _np
@@ -574,21 +576,15 @@ class AddLayerNormFn(torch.autograd.Function):
              0, _s())
         ctx.save_for_backward(x2, r2, gamma, mean, rstd)
         ctx.shape = x.shape
-        ctx.gb = (_gbuf(gamma), _gbuf(beta))
+        ctx.ln = (gamma, beta, _gbuf(gamma), _gbuf(beta), eps)
         return y.view(x.shape)
 
     @staticmethod
     @_bw
     def backward(ctx, dy):
         x2, r2, gamma, mean, rstd = ctx.saved_tensors
-        D = x2.size(1)
-        M = x2.size(0)
-        dy2 = dy.contiguous().view(-1, D)
-        dz = torch.empty_like(dy2)
-        dg, _, dg_ret = _target(ctx.gb[0], (D,), dy.device, zero=True)
-        db, _, db_ret = _target(ctx.gb[1], (D,), dy.device, zero=True)
-        call("sbl_add_layernorm_bwd", _p(dy2), _p(x2), _p(r2), _p(gamma), _p(mean), _p(rstd), _p(dz), None, _p(dg), _p(db),
-             M, D, 0.0, None, 0, _s())
+        ln, (dg_ret, db_ret) = _ln_targets(ctx.ln, dy.device)
+        dz, _ = ln_bwd(dy.contiguous().view(x2.shape), x2, r2, ln, mean, rstd, 0.0, None, 0, False)
         dz = dz.view(ctx.shape)
         return dz, (dz if r2 is not None else None), dg_ret, db_ret, None
 
@@ -682,8 +678,15 @@ class SDPAFn(torch.autograd.Function):
 
 
 # --------------------------------------------------------------------------- #
-# fused multi-head attention sub-layer
+# the post-norm transformer sub-layer: its launch sequences, stated once
 # --------------------------------------------------------------------------- #
+# y = LayerNorm(dropout(core(x W_in^T + b_in) W_out^T + b_out) + x), core = attention or ReLU, as plain functions over
+# explicit tensors: no autograd, no streams; they write into the buffers they are given and allocate the others.  Callers:
+# the tape nodes below, the stage-batched decoder backward (transformer/decoder_stages.py), the KV-cached greedy decode
+# (transformer/seq2seq.py).  The attention core draws its dropout mask at offset `off_a`, the output dropout (fused into the
+# LayerNorm kernels) at `off_o` / `off`; backward passes the forward's offsets and the kernels regenerate the masks.  Every
+# weight gradient goes to the caller's `sink(lin, dY, X)` (dW += dY^T X, the bias gradient riding on it) BEFORE the input
+# gradient is accumulated in place onto the residual gradient.
 def _adjacent(*ts):
     """True if the tensors are contiguous and laid out back to back in memory (rows of one fused matrix)."""
     p = ts[0].data_ptr()
@@ -694,6 +697,211 @@ def _adjacent(*ts):
     return True
 
 
+def fuse_rows(ws, bs):
+    """Move the parameters `ws` (and their biases `bs`) to adjacent row ranges of one new buffer each."""
+    with torch.no_grad():
+        fw = torch.cat([w.data for w in ws], 0).contiguous()
+        fb = torch.cat([b.data for b in bs], 0).contiguous()
+        if fw.is_cuda:      # one-time set-up: the old storages are released below, so the copies must have run
+            torch.cuda.current_stream(fw.device).synchronize()
+        r = 0
+        for w, b in zip(ws, bs):
+            n = w.size(0)
+            w.data = fw[r:r + n]
+            b.data = fb[r:r + n]
+            r += n
+
+
+class Lin:
+    """Handle of y = x W^T + b with W (N, K) = the weights `ws` stacked, which must be adjacent rows of one matrix (fused
+    q/k/v or k/v; a single weight is its own stack), `bs` likewise.  gw / gb: the persistent gradient buffers of the
+    stacked W / b when every part has one and they are adjacent too, else both None (backward then hands fresh gradients
+    to autograd)."""
+
+    def __init__(self, ws, bs):
+        assert _adjacent(*ws) and _adjacent(*bs)
+        self.w, self.b = ws[0], bs[0]
+        self.N, self.K = sum(w.size(0) for w in ws), ws[0].size(1)
+        gw, gb = [_gbuf(t) for t in ws], [_gbuf(t) for t in bs]
+        ok = all(g is not None for g in gw + gb) and _adjacent(*gw) and _adjacent(*gb)
+        self.gw, self.gb = (gw[0], gb[0]) if ok else (None, None)
+
+
+def _sublayer(inp, out, gamma, beta, eps, drop_p, H=0):
+    """Parameter handle of one sub-layer.  inp: the Lin in front of the core, out: the one behind it, ln: (gamma, beta, where
+    backward accumulates dgamma, dbeta - persistent buffers or None -, eps), H heads (attention)."""
+    return _types.SimpleNamespace(inp=inp, out=out, ln=(gamma, beta, _gbuf(gamma), _gbuf(beta), eps), drop_p=drop_p, H=H)
+
+
+def attn_handle(wq, bq, wk, bk, wv, bv, wfc, bfc, gamma, beta, H, drop_p, eps):
+    """inp = the fused q/k/v projection, or with wk = None q alone (cross-attention: [K|V] come pre-projected); out = fc."""
+    inp = Lin((wq,), (bq,)) if wk is None else Lin((wq, wk, wv), (bq, bk, bv))
+    return _sublayer(inp, Lin((wfc,), (bfc,)), gamma, beta, eps, drop_p, H)
+
+
+def ffn_handle(w1, b1, w2, b2, gamma, beta, drop_p, eps):
+    return _sublayer(Lin((w1,), (b1,)), Lin((w2,), (b2,)), gamma, beta, eps, drop_p)
+
+
+def kv_block(mods):
+    """(weights, biases) of the cross-attention modules' K/V projections in the order of the block [K_0; V_0; K_1; ...]"""
+    return [w for m in mods for w in (m.w_ks.weight, m.w_vs.weight)], [b for m in mods for b in (m.w_ks.bias, m.w_vs.bias)]
+
+
+def _new(like, *shape):
+    return torch.empty(shape, device=like.device, dtype=torch.float32)
+
+
+def lin_fwd(lin, x, out=None, relu=0):
+    """out (M, N) = x W^T + b (ReLU)."""
+    M, ldx = _rows(x)
+    if out is None:
+        out = _new(x, M, lin.N)
+    gemm(0, 1, M, lin.N, lin.K, x, ldx, lin.w, lin.K, out, lin.N, bias=lin.b, relu=relu)
+    return out
+
+
+def out_ln_fwd(h, a, res, seed, off, bufs=None):
+    """The closing half of sub-layer h: o = a W_out^T + b, y = LayerNorm(dropout(o) + res), into bufs = (o, y, mean, rstd)
+    when given.  Returns (o, y, mean, rstd)."""
+    M = a.size(0)
+    o, y, mean, rstd = bufs or (None, _new(a, M, h.out.N), _new(a, M), _new(a, M))
+    o = lin_fwd(h.out, a, o)
+    call("sbl_add_layernorm_fwd", _p(o), _p(res), _p(h.ln[0]), _p(h.ln[1]), _p(y), _p(mean), _p(rstd), M, h.out.N, h.ln[4],
+         h.drop_p, _p(seed) if h.drop_p > 0 else None, off, _s())
+    return o, y, mean, rstd
+
+
+def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o):
+    """Attention sub-layer on the rows x (B * sum(segL), D) of a ragged batch: segment s has B sequences of length segL[s].
+    kv = None: self-attention inside each segment; else cross-attention to the rows kv (B * Lk, 2 * H * 64) = [K|V] (a
+    column block of a wider buffer is fine).  Returns (y, (qkv, att, p, o, mean, rstd)): the second is what attn_bwd wants
+    back; p = the segments' (H*B, L, Lk) probability blocks back to back."""
+    HD = a.H * 64
+    qkv = lin_fwd(a.inp, x)
+    if kv is None:
+        k, v, ldk, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, 0       # Lk = 0: keys = the segment's own rows
+        psize = a.H * B * sum(l * l for l in segL)
+    else:
+        k, v, ldk, Lk = kv, kv[:, HD:], _rows(kv)[1], kv.size(0) // B
+        psize = a.H * B * sum(segL) * Lk
+    att = _new(x, x.size(0), HD)
+    p = _new(x, psize)
+    call("sbl_attention_seg_fwd", _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(att), HD, _p(p), mask_kind, _p(mask_t), B, a.H,
+         *_segs(segL), Lk, 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+    o, y, mean, rstd = out_ln_fwd(a, att, x, seed, off_o)
+    return y, (qkv, att, p, o, mean, rstd)
+
+
+def ffn_fwd(f, x, seed, off, h=None, bufs=None):
+    """Feed-forward sub-layer on the rows x (M, D).  Returns (y, (h, o, mean, rstd)), the second for ffn_bwd."""
+    h = lin_fwd(f.inp, x, h, relu=1)
+    o, y, mean, rstd = out_ln_fwd(f, h, x, seed, off, bufs)
+    return y, (h, o, mean, rstd)
+
+
+def project_kv_block(x, mods):
+    """[K_0 | V_0 | K_1 | ...] = x [Wk_0; Wv_0; Wk_1; ...]^T + b for the cross-attention modules `mods`, whose K/V projections
+    are rows of one matrix in that order: ONE GEMM.  Returns (the block's Lin, the buffer, every module's column block of
+    it: read in place, its row stride is the buffer's)."""
+    lin = Lin(*kv_block(mods))
+    kv = lin_fwd(lin, x)
+    return lin, kv, kv.split(lin.N // len(mods), 1)
+
+
+def ln_bwd(dy, o, res, ln, mean, rstd, drop_p, seed, off, separate_do):
+    """Adjoint of y = LayerNorm(dropout(o) + res) -> (dz, do): dz = gradient of the residual `res` (of the sum when res is
+    None), do = gradient of the pre-dropout o; dgamma / dbeta accumulate into ln[2] / ln[3].  do is a buffer of its own with
+    dropout, and whenever the caller says so (`separate_do`): callers go on to accumulate the sub-layer's input gradient
+    into dz in place, so a weight-gradient GEMM that is issued later (a deferring sink) must not find do aliased to it.
+    Otherwise do IS dz."""
+    M, D = dy.shape
+    dz = _new(dy, M, D)
+    do = _new(dy, M, D) if separate_do or drop_p > 0 else None
+    call("sbl_add_layernorm_bwd", _p(dy), _p(o), _p(res), _p(ln[0]), _p(mean), _p(rstd), _p(dz), _p(do), _p(ln[2]), _p(ln[3]),
+         M, D, drop_p, _p(seed) if drop_p > 0 else None, off, _s())
+    return dz, (dz if do is None else do)
+
+
+def _out_ln_bwd(h, dy, a, o, res, mean, rstd, seed, off, separate_do, sink, relu_mask=None):
+    """Adjoint of out_ln_fwd -> (dz = gradient of res, da = gradient of a; `relu_mask` = a when a is a ReLU's output: its
+    adjoint is fused into the GEMM epilogue)."""
+    lin = h.out
+    dz, do = ln_bwd(dy, o, res, h.ln, mean, rstd, h.drop_p, seed, off, separate_do)
+    sink(lin, do, a)
+    M = dy.size(0)
+    da = _new(dy, M, lin.K)
+    gemm(0, 0, M, lin.K, lin.N, do, lin.N, lin.w, lin.K, da, lin.K, mask=relu_mask, ldm=0 if relu_mask is None else lin.K)
+    return dz, da
+
+
+def _lin_bwd(lin, dY, x, dx, sink):
+    """Adjoint of lin_fwd: dx, which already holds the residual-branch gradient, += dY W."""
+    sink(lin, dY, x)
+    gemm(0, 0, x.size(0), lin.K, lin.N, dY, lin.N, lin.w, lin.K, dx, lin.K, accumulate=1)
+
+
+def attn_bwd(a, dy, x, acts, B, segL, kv, seed, off_a, off_o, separate_do, sink, dkv=None):
+    """Adjoint of attn_fwd (acts = what it returned) -> (dx, dkv).  Cross-attention: dkv (B * Lk, 2 * H * 64) is written,
+    not accumulated (several segments share the keys / values: their dK / dV contributions are summed inside the call);
+    allocated when not given, a column block of a wider buffer is fine."""
+    qkv, att, p, o, mean, rstd = acts
+    HD = a.H * 64
+    dx, datt = _out_ln_bwd(a, dy, att, o, x, mean, rstd, seed, off_o, separate_do, sink)
+    dq = _new(dy, x.size(0), a.inp.N)                  # self-attention: [dQ | dK | dV]
+    if kv is None:
+        k, v, ldk, dk, dv, ldd, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, dq[:, HD:], dq[:, 2 * HD:], 3 * HD, 0
+    else:
+        dkv = _new(dy, kv.size(0), 2 * HD) if dkv is None else dkv
+        k, v, ldk, dk, dv, ldd, Lk = kv, kv[:, HD:], _rows(kv)[1], dkv, dkv[:, HD:], _rows(dkv)[1], kv.size(0) // B
+    call("sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(p), _p(dq), a.inp.N, _p(dk), ldd,
+         _p(dv), ldd, B, a.H, *_segs(segL), Lk, 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+    _lin_bwd(a.inp, dq, x, dx, sink)
+    return dx, dkv
+
+
+def ffn_bwd(f, dy, x, acts, seed, off, separate_do, sink):
+    """Adjoint of ffn_fwd (acts = what it returned) -> dx."""
+    h, o, mean, rstd = acts
+    dx, dh = _out_ln_bwd(f, dy, h, o, x, mean, rstd, seed, off, separate_do, sink, relu_mask=h)
+    _lin_bwd(f.inp, dh, x, dx, sink)
+    return dx
+
+
+# ---- the tape's side of it: gradients go to the persistent buffers, or to fresh ones that are handed back to autograd
+def _ln_targets(ln, dev):
+    """(ln with somewhere for dgamma / dbeta to go, (what to hand back to autograd for gamma, for beta))"""
+    gamma, beta, gg, gb, eps = ln
+    gg, _, gg_ret = _target(gg, gamma.shape, dev, zero=True)
+    gb, _, gb_ret = _target(gb, beta.shape, dev, zero=True)
+    return (gamma, beta, gg, gb, eps), (gg_ret, gb_ret)
+
+
+def _tape_bwd(ctx, dev):
+    """-> (handle with LayerNorm gradient targets, separate_do, sink, rets) for a tape node's *_bwd call.  The sink issues a
+    weight gradient now or defers it (wgrad_gemm); rets[lin] = (dW, db) and rets["ln"] are autograd's, None if accumulated."""
+    h = _copy.copy(ctx.h)
+    h.ln, ln_ret = _ln_targets(h.ln, dev)
+    rets = {"ln": ln_ret}
+
+    def sink(lin, dY, X):
+        dw, acc, dw_ret = _target(lin.gw, (lin.N, lin.K), dev)
+        db, _, db_ret = _target(lin.gb, (lin.N,), dev, zero=True)
+        wgrad_gemm(lin.N, lin.K, X.size(0), dY, lin.N, X, lin.K, dw, lin.K, acc, db, ctx.defer)
+        rets[lin] = (dw_ret, db_ret)
+
+    return h, ctx.defer is not None and h.out.gw is not None, sink, rets
+
+
+def _param_grads(ret, parts):
+    """(dW, db) of a Lin of `parts` stacked weights -> (dW_0, db_0, dW_1, ...) for autograd"""
+    dw, db = ret
+    if dw is None:
+        return (None,) * (2 * parts)
+    n = dw.size(0) // parts
+    return tuple(t[i * n:(i + 1) * n] for i in range(parts) for t in (dw, db))
+
+
 class KVProjectFn(torch.autograd.Function):
     """[K | V] = x [Wk; Wv]^T + [bk; bv] -> (B*Lk, 2*H*64).  For decoder cross-attention this is hoisted out
     of the 16-step loop (step-invariant: SURVEY 3.2 consequence ii).  Wk/Wv (and bk/bv) must be adjacent rows of
@@ -702,45 +910,36 @@ class KVProjectFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2, wk, bk, wv, bv):
         _need_cuda(x2, wk, wv)
-        assert _adjacent(wk, wv) and _adjacent(bk, bv)
-        M, ldx = _rows(x2)
-        N2, K = 2 * wk.size(0), wk.size(1)
-        kv = torch.empty(M, N2, device=x2.device, dtype=torch.float32)
-        gemm(0, 1, M, N2, K, x2, ldx, wk, K, kv, N2, bias=bk)
+        ctx.lin = Lin((wk, wv), (bk, bv))
         ctx.save_for_backward(x2, wk, wv)
-        gw, gb = (_gbuf(wk), _gbuf(wv)), (_gbuf(bk), _gbuf(bv))
-        ctx.gb = (gw[0], gb[0]) if all(g is not None for g in gw + gb) and _adjacent(*gw) and _adjacent(*gb) else (None, None)
-        return kv
+        return lin_fwd(ctx.lin, x2)
 
     @staticmethod
     @_bw
     def backward(ctx, dkv):
-        x2, wk, wv = ctx.saved_tensors
+        x2 = ctx.saved_tensors[0]
+        lin = ctx.lin
         dkv = dkv.contiguous()
         _xs_in(dkv, x2)
         M, ldx = _rows(x2)
-        N2, K = 2 * wk.size(0), wk.size(1)
         dev = dkv.device
-        dx = torch.empty(M, K, device=dev, dtype=torch.float32)
+        dx = torch.empty(M, lin.K, device=dev, dtype=torch.float32)
         _xs_out(dx)
-        gemm(0, 0, M, K, N2, dkv, N2, wk, K, dx, K)
-        dw, acc, dw_ret = _target(ctx.gb[0], (N2, K), dev)
-        db, _, db_ret = _target(ctx.gb[1], (N2,), dev, zero=True)
-        wgrad_gemm(N2, K, M, dkv, N2, x2, ldx, dw, K, acc, db)
+        gemm(0, 0, M, lin.K, lin.N, dkv, lin.N, lin.w, lin.K, dx, lin.K)
+        dw, acc, dw_ret = _target(lin.gw, (lin.N, lin.K), dev)
+        db, _, db_ret = _target(lin.gb, (lin.N,), dev, zero=True)
+        wgrad_gemm(lin.N, lin.K, M, dkv, lin.N, x2, ldx, dw, lin.K, acc, db)
         _xs_out(dw_ret, db_ret)
         _side_to_main()     # dx joins the other direction's dx in the encoder-output gradient on the main stream
-        h = N2 // 2
-        if dw_ret is None:
-            return dx, None, None, None, None
-        return dx, dw_ret[:h], db_ret[:h], dw_ret[h:], db_ret[h:]
+        return (dx,) + _param_grads((dw_ret, db_ret), 2)
 
 
 class MHAFn(torch.autograd.Function):
-    """One whole MultiHeadAttention.forward (attention.py:32-60) as a single tape node:
+    """One whole MultiHeadAttention.forward (attention.py:32-60) as a single tape node over attn_fwd / attn_bwd:
     projections -> attention core -> fc -> dropout -> LayerNorm(out + residual).
 
-    self_attn=True : q, k, v all come from x through ONE fused (M x 3*H*64) GEMM.
-    self_attn=False: q from x, [K|V] given pre-projected (kv, shape (B*Lk, 2*H*64)).
+    self-attention (kv = None): q, k, v all come from x through ONE fused (M x 3*H*64) GEMM.
+    cross-attention (wk = bk = wv = bv = None): q from x, [K|V] given pre-projected (kv, shape (B*Lk, 2*H*64)).
     The output dropout is fused into the LayerNorm kernels, the bias gradients into the weight-gradient GEMMs.
     """
 
@@ -750,114 +949,36 @@ class MHAFn(torch.autograd.Function):
         (B, L, D) case).  Returns (y (R, D), p = the segments' (H*B, L, Lk) probability blocks back to back)."""
         _need_cuda(x, wq, wfc)
         x2 = x.contiguous()
-        M, D = x2.shape
-        assert M == B * sum(segL), (M, B, segL)
-        seg_arr, nseg = _segs(segL)
-        HD = H * 64
-        dev = x.device
-        self_attn = kv is None
-        if self_attn:
-            assert _adjacent(wq, wk, wv) and _adjacent(bq, bk, bv)
-            qkv = torch.empty(M, 3 * HD, device=dev, dtype=torch.float32)
-            gemm(0, 1, M, 3 * HD, D, x2, D, wq, D, qkv, 3 * HD, bias=bq)
-            qp, kp, vp = qkv, qkv[:, HD:], qkv[:, 2 * HD:]
-            ldq = ldk = ldv = 3 * HD
-            Lk = 0                                   # keys = the segment's own rows
-            psize = H * B * sum(l * l for l in segL)
-            gw, gb = (_gbuf(wq), _gbuf(wk), _gbuf(wv)), (_gbuf(bq), _gbuf(bk), _gbuf(bv))
-            fused_ok = all(g is not None for g in gw + gb) and _adjacent(*gw) and _adjacent(*gb)
-            g_qkv = (gw[0], gb[0]) if fused_ok else (None, None)
-        else:
-            qkv = torch.empty(M, HD, device=dev, dtype=torch.float32)
-            gemm(0, 1, M, HD, D, x2, D, wq, D, qkv, HD, bias=bq)
-            Lk = kv.size(0) // B
-            psize = H * B * sum(segL) * Lk
-            qp, kp, vp = qkv, kv, kv[:, HD:]
-            ldq, ldk, ldv = HD, 2 * HD, 2 * HD
-            g_qkv = (_gbuf(wq), _gbuf(bq))
-            if g_qkv[0] is None or g_qkv[1] is None:
-                g_qkv = (None, None)
-        att = torch.empty(M, HD, device=dev, dtype=torch.float32)
-        p = torch.empty(psize, device=dev, dtype=torch.float32)
+        assert x2.size(0) == B * sum(segL), (x2.shape, B, segL)
+        assert (kv is None) == (wk is not None)
+        a = attn_handle(wq, bq, wk, bk, wv, bv, wfc, bfc, gamma, beta, H, drop_p, eps)
         seed, off_a, off_o = None, 0, 0
         if drop_p > 0:
-            st = dropout_state(dev)
+            st = dropout_state(x.device)
             seed, off_a, off_o = st.seed, st.next_offset(), st.next_offset()
-        call("sbl_attention_seg_fwd", _p(qp), ldq, _p(kp), ldk, _p(vp), ldv, _p(att), HD, _p(p), mask_kind, _p(mask_t), B, H,
-             seg_arr, nseg, Lk, 1.0 / 8.0, drop_p, _p(seed), off_a, _s())
-        o = torch.empty(M, D, device=dev, dtype=torch.float32)
-        gemm(0, 1, M, D, HD, att, HD, wfc, HD, o, D, bias=bfc)
-        y = torch.empty(M, D, device=dev, dtype=torch.float32)
-        mean = torch.empty(M, device=dev, dtype=torch.float32)
-        rstd = torch.empty(M, device=dev, dtype=torch.float32)
-        call("sbl_add_layernorm_fwd", _p(o), _p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, drop_p,
-             _p(seed), off_o, _s())
-        ctx.save_for_backward(x2, kv, qkv, att, p, o, mean, rstd, wq, wk, wv, wfc, gamma, seed)
-        ctx.cfg = (B, tuple(segL), Lk, D, H, drop_p, off_a, off_o, self_attn)
-        ctx.gb = (g_qkv, (_gbuf(wfc), _gbuf(bfc)), (_gbuf(gamma), _gbuf(beta)))
+        y, acts = attn_fwd(a, x2, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o)
+        # (the weights ride along for autograd's modified-in-place check; backward reads them through the handle)
+        ctx.save_for_backward(x2, kv, seed, *acts, wq, wk, wv, wfc, gamma)
+        ctx.h, ctx.cfg = a, (B, tuple(segL), off_a, off_o)
         ctx.defer = getattr(_tls, "collector", None)
-        ctx.mark_non_differentiable(p)
+        ctx.mark_non_differentiable(acts[2])
         ctx.set_materialize_grads(False)      # else autograd zero-fills a gradient for p before every backward
-        return y, p
+        return y, acts[2]
 
     @staticmethod
     @_bw
     def backward(ctx, dy, _dp):
         if dy is None:
             return (None,) * 19
-        x2, kv, qkv, att, p, o, mean, rstd, wq, wk, wv, wfc, gamma, seed = ctx.saved_tensors
-        B, segL, Lk, D, H, drop_p, off_a, off_o, self_attn = ctx.cfg
-        g_qkv, g_fc, g_ln = ctx.gb
-        seg_arr, nseg = _segs(segL)
-        M, HD, dev = B * sum(segL), H * 64, dy.device
+        saved = ctx.saved_tensors
+        (x2, kv, seed), acts = saved[:3], saved[3:9]
+        B, segL, off_a, off_o = ctx.cfg
         _xs_in(dy)
-        dy2 = dy.contiguous().view(M, D)
-        # LayerNorm(dropout(o) + x) adjoint: dz = grad of the residual x, do = grad of the pre-dropout o
-        dz = torch.empty(M, D, device=dev, dtype=torch.float32)
-        # a separate pre-dropout gradient buffer is also needed without dropout when the deferred weight-gradient GEMM
-        # reads it later while this stream accumulates the input gradient into dz in place
-        sep = drop_p > 0 or (ctx.defer is not None and g_fc[0] is not None)
-        do = torch.empty(M, D, device=dev, dtype=torch.float32) if sep else None
-        dgamma, _, dgamma_ret = _target(g_ln[0], (D,), dev, zero=True)
-        dbeta, _, dbeta_ret = _target(g_ln[1], (D,), dev, zero=True)
-        call("sbl_add_layernorm_bwd", _p(dy2), _p(o), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(dz), _p(do), _p(dgamma),
-             _p(dbeta), M, D, drop_p, _p(seed), off_o, _s())
-        if do is None:
-            do = dz
-        # fc: dW (+ bias grad riding on it), then input gradient
-        dwfc, acc, dwfc_ret = _target(g_fc[0], (D, HD), dev)
-        dbfc, _, dbfc_ret = _target(g_fc[1], (D,), dev, zero=True)
-        wgrad_gemm(D, HD, M, do, D, att, HD, dwfc, HD, acc, dbfc, ctx.defer)
-        datt = torch.empty(M, HD, device=dev, dtype=torch.float32)
-        gemm(0, 0, M, HD, D, do, D, wfc, HD, datt, HD)
-        dx = dz          # residual-branch gradient; the projection's input gradient accumulates on top of it
-        if self_attn:
-            dqkv = torch.empty(M, 3 * HD, device=dev, dtype=torch.float32)
-            ld = 3 * HD
-            call("sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), ld, _p(qkv[:, HD:]), ld, _p(qkv[:, 2 * HD:]), ld, _p(p),
-                 _p(dqkv), ld, _p(dqkv[:, HD:]), ld, _p(dqkv[:, 2 * HD:]), ld, B, H, seg_arr, nseg, 0, 1.0 / 8.0, drop_p,
-                 _p(seed), off_a, _s())
-            dw, acc, dw_ret = _target(g_qkv[0], (3 * HD, D), dev)
-            db, _, db_ret = _target(g_qkv[1], (3 * HD,), dev, zero=True)
-            wgrad_gemm(3 * HD, D, M, dqkv, 3 * HD, x2, D, dw, D, acc, db, ctx.defer)
-            gemm(0, 0, M, D, 3 * HD, dqkv, 3 * HD, wq, D, dx, D, accumulate=1)
-            if dw_ret is None:
-                wret = (None,) * 6
-            else:
-                wret = (dw_ret[:HD], db_ret[:HD], dw_ret[HD:2 * HD], db_ret[HD:2 * HD], dw_ret[2 * HD:], db_ret[2 * HD:])
-            _xs_out(dx)
-            return (dx, None) + wret + (dwfc_ret, dbfc_ret, dgamma_ret, dbeta_ret) + (None,) * 7
-        dq = torch.empty(M, HD, device=dev, dtype=torch.float32)
-        # several segments share the keys/values: their dK/dV contributions are summed inside the call
-        dkv = torch.empty(B * Lk, 2 * HD, device=dev, dtype=torch.float32)
-        call("sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), HD, _p(kv), 2 * HD, _p(kv[:, HD:]), 2 * HD, _p(p), _p(dq), HD,
-             _p(dkv), 2 * HD, _p(dkv[:, HD:]), 2 * HD, B, H, seg_arr, nseg, Lk, 1.0 / 8.0, drop_p, _p(seed), off_a, _s())
-        dwq, acc, dwq_ret = _target(g_qkv[0], (HD, D), dev)
-        dbq, _, dbq_ret = _target(g_qkv[1], (HD,), dev, zero=True)
-        wgrad_gemm(HD, D, M, dq, HD, x2, D, dwq, D, acc, dbq, ctx.defer)
-        gemm(0, 0, M, D, HD, dq, HD, wq, D, dx, D, accumulate=1)
+        a, sep, sink, rets = _tape_bwd(ctx, dy.device)
+        dx, dkv = attn_bwd(a, dy.contiguous().view(x2.shape), x2, acts, B, segL, kv, seed, off_a, off_o, sep, sink)
         _xs_out(dx, dkv)
-        return (dx, dkv, dwq_ret, dbq_ret, None, None, None, None, dwfc_ret, dbfc_ret, dgamma_ret, dbeta_ret) + (None,) * 7
+        return (dx, dkv) + _param_grads(rets[a.inp], 3 if kv is None else 1) + (None,) * (0 if kv is None else 4) \
+            + rets[a.out] + rets["ln"] + (None,) * 7
 
 
 # tests only: callable(w1, h) handed every feed-forward's post-ReLU hidden activation (tests/test_hip_parity.py compares the
@@ -866,69 +987,38 @@ _ffn_probe = None
 
 
 class FFNFn(torch.autograd.Function):
-    """PositionwiseFeedForward.forward (module.py:47-52) as one tape node:
+    """PositionwiseFeedForward.forward (module.py:47-52) as one tape node over ffn_fwd / ffn_bwd:
     LayerNorm(dropout(relu(x W1^T + b1) W2^T + b2) + x); dropout fused into the LayerNorm kernels."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, gamma, beta, drop_p, eps):
         _need_cuda(x, w1, w2)
         shp = x.shape
-        D = shp[-1]
-        x2 = x.contiguous().view(-1, D)
-        M, F_, dev = x2.size(0), w1.size(0), x.device
-        h = torch.empty(M, F_, device=dev, dtype=torch.float32)
-        gemm(0, 1, M, F_, D, x2, D, w1, D, h, F_, bias=b1, relu=1)
-        if _ffn_probe is not None:
-            _ffn_probe(w1, h)
-        o = torch.empty(M, D, device=dev, dtype=torch.float32)
-        gemm(0, 1, M, D, F_, h, F_, w2, F_, o, D, bias=b2)
+        x2 = x.contiguous().view(-1, shp[-1])
+        f = ffn_handle(w1, b1, w2, b2, gamma, beta, drop_p, eps)
         seed, off = None, 0
         if drop_p > 0:
-            st = dropout_state(dev)
+            st = dropout_state(x.device)
             seed, off = st.seed, st.next_offset()
-        y = torch.empty(M, D, device=dev, dtype=torch.float32)
-        mean = torch.empty(M, device=dev, dtype=torch.float32)
-        rstd = torch.empty(M, device=dev, dtype=torch.float32)
-        call("sbl_add_layernorm_fwd", _p(o), _p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, drop_p,
-             _p(seed), off, _s())
-        ctx.save_for_backward(x2, h, o, mean, rstd, w1, w2, gamma, seed)
-        ctx.cfg = (shp, drop_p, off)
-        ctx.gb = ((_gbuf(w1), _gbuf(b1)), (_gbuf(w2), _gbuf(b2)), (_gbuf(gamma), _gbuf(beta)))
+        y, acts = ffn_fwd(f, x2, seed, off)
+        if _ffn_probe is not None:
+            _ffn_probe(w1, acts[0])
+        ctx.save_for_backward(x2, seed, *acts, w1, w2, gamma)      # (the weights: as in MHAFn.forward)
+        ctx.h, ctx.cfg = f, (shp, off)
         ctx.defer = getattr(_tls, "collector", None)
         return y.view(shp)
 
     @staticmethod
     @_bw
     def backward(ctx, dy):
-        x2, h, o, mean, rstd, w1, w2, gamma, seed = ctx.saved_tensors
-        shp, drop_p, off = ctx.cfg
-        g1, g2, g_ln = ctx.gb
-        M, D = x2.shape
-        F_, dev = w1.size(0), dy.device
+        saved = ctx.saved_tensors
+        (x2, seed), acts = saved[:2], saved[2:6]
+        shp, off = ctx.cfg
         _xs_in(dy)
-        dy2 = dy.contiguous().view(M, D)
-        dz = torch.empty(M, D, device=dev, dtype=torch.float32)
-        # (same as in MHAFn.backward)
-        sep = drop_p > 0 or (ctx.defer is not None and g2[0] is not None)
-        do = torch.empty(M, D, device=dev, dtype=torch.float32) if sep else None
-        dgamma, _, dgamma_ret = _target(g_ln[0], (D,), dev, zero=True)
-        dbeta, _, dbeta_ret = _target(g_ln[1], (D,), dev, zero=True)
-        call("sbl_add_layernorm_bwd", _p(dy2), _p(o), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(dz), _p(do), _p(dgamma),
-             _p(dbeta), M, D, drop_p, _p(seed), off, _s())
-        if do is None:
-            do = dz
-        dw2, acc, dw2_ret = _target(g2[0], (D, F_), dev)
-        db2, _, db2_ret = _target(g2[1], (D,), dev, zero=True)
-        wgrad_gemm(D, F_, M, do, D, h, F_, dw2, F_, acc, db2, ctx.defer)
-        dh = torch.empty(M, F_, device=dev, dtype=torch.float32)
-        gemm(0, 0, M, F_, D, do, D, w2, F_, dh, F_, mask=h, ldm=F_)      # ReLU adjoint fused in the epilogue
-        dw1, acc, dw1_ret = _target(g1[0], (F_, D), dev)
-        db1, _, db1_ret = _target(g1[1], (F_,), dev, zero=True)
-        wgrad_gemm(F_, D, M, dh, F_, x2, D, dw1, D, acc, db1, ctx.defer)
-        dx = dz
-        gemm(0, 0, M, D, F_, dh, F_, w1, D, dx, D, accumulate=1)
+        f, sep, sink, rets = _tape_bwd(ctx, dy.device)
+        dx = ffn_bwd(f, dy.contiguous().view(x2.shape), x2, acts, seed, off, sep, sink)
         _xs_out(dx)
-        return dx.view(shp), dw1_ret, db1_ret, dw2_ret, db2_ret, dgamma_ret, dbeta_ret, None, None
+        return (dx.view(shp),) + rets[f.inp] + rets[f.out] + rets["ln"] + (None, None)
 
 
 # --------------------------------------------------------------------------- #

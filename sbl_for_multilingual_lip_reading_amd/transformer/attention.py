@@ -62,17 +62,17 @@ class MultiHeadAttention(nn.Module):
             # which is all the cross-attention path (KVProjectFn / decoder_stages) needs
             assert ops._adjacent(*ws[1:]) and ops._adjacent(*bs[1:]), "flat model: K/V projection weights are not adjacent"
             return
-        with torch.no_grad():
-            fw = torch.cat([w.data for w in ws], 0).contiguous()
-            fb = torch.cat([b.data for b in bs], 0).contiguous()
-            if fw.is_cuda:      # one-time set-up: the old storages are released below, so the copies must have run
-                torch.cuda.current_stream(fw.device).synchronize()
-            r = 0
-            for w, b in zip(ws, bs):
-                n = w.size(0)
-                w.data = fw[r:r + n]
-                b.data = fb[r:r + n]
-                r += n
+        ops.fuse_rows(ws, bs)
+
+    def _params(self, cross):
+        """The leading arguments of ops.attn_handle, which are also those of ops.MHAFn after (x, kv)."""
+        self._fuse()
+        kv = (None,) * 4 if cross else (self.w_ks.weight, self.w_ks.bias, self.w_vs.weight, self.w_vs.bias)
+        return (self.w_qs.weight, self.w_qs.bias) + kv + (self.fc.weight, self.fc.bias, self.layer_norm.weight, self.layer_norm.bias)
+
+    def handle(self, cross=False):
+        """This sub-layer's parameter handle for the ops.attn_* functions; cross: [K|V] come pre-projected."""
+        return ops.attn_handle(*self._params(cross), self.n_head, self.dropout.p if self.training else 0.0, self.layer_norm.eps)
 
     def project_kv(self, k):
         """[K | V] = k [W_k; W_v]^T + [b_k; b_v], shape (B*Lk, 2*n_head*64) — attention.py:42-43 for both at once."""
@@ -85,22 +85,15 @@ class MultiHeadAttention(nn.Module):
         segL[s] (the SBL decoder batches the steps of one teacher-forced run this way).  kv_proj=None: self-attention
         inside each segment; else cross-attention to the pre-projected [K|V] rows (B*Lk, 2*n_head*64).
         mask: None | 'causal' (| a (B,Lq,Lk) tensor when there is a single segment).  Returns (out rows, attn flat)."""
-        self._fuse()
         drop_p = self.dropout.p if self.training else 0.0
-        ln = self.layer_norm
         if isinstance(mask, str) or mask is None:
             mask_kind, mask_t = (1, None) if mask == "causal" else (0, None)
         else:
             assert len(segL) == 1
             Lk = segL[0] if kv_proj is None else kv_proj.size(0) // B
             mask_kind, mask_t = _as_mask(mask, B, segL[0], Lk)
-        if kv_proj is None:
-            return ops.MHAFn.apply(x2, None, self.w_qs.weight, self.w_qs.bias, self.w_ks.weight, self.w_ks.bias,
-                                   self.w_vs.weight, self.w_vs.bias, self.fc.weight, self.fc.bias, ln.weight, ln.bias,
-                                   self.n_head, mask_kind, mask_t, drop_p, ln.eps, B, tuple(segL))
-        return ops.MHAFn.apply(x2, kv_proj, self.w_qs.weight, self.w_qs.bias, None, None, None, None,
-                               self.fc.weight, self.fc.bias, ln.weight, ln.bias,
-                               self.n_head, mask_kind, mask_t, drop_p, ln.eps, B, tuple(segL))
+        return ops.MHAFn.apply(x2, kv_proj, *self._params(kv_proj is not None), self.n_head, mask_kind, mask_t, drop_p,
+                               self.layer_norm.eps, B, tuple(segL))
 
     def forward(self, q, k, v, mask=None, kv_proj=None):
         sz_b, len_q, d = q.size()

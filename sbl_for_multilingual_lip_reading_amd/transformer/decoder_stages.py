@@ -15,6 +15,9 @@ next token); the cross-attention K/V of all 12 layers come from one GEMM before 
 an offset that folds its row base in (the generator is affine in both, see _fold), so the batched backward
 regenerates exactly the masks of the forward with plain whole-buffer indices.
 
+The backward of a layer is ops.ffn_bwd / ops.attn_bwd (what the per-stage tape's MHAFn / FFNFn run) over these buffers, with a
+sink that collects the weight gradients for one grouped launch; only the paired forward is a launch sequence of this file.
+
 Used by Decoder.forward when gradients accumulate into persistent buffers (dp.FlatModel) and the coins are known on
 the host (supported() has the full list); every other case keeps the per-stage tape (Decoder._run).  Same numbers as that
 path (tests compare them).
@@ -37,7 +40,7 @@ def _fold(offset, base):
 
 
 def supported(dec, encoder_outputs):
-    """The parameter handles ([direction][layer] of _Layer) the fast path runs on, or None when it does not apply.  It needs
+    """The parameter handles ([direction][layer] of _layer) the fast path runs on, or None when it does not apply.  It needs
     persistent gradient buffers for every decoder parameter (kernels accumulate there), host coins, CUDA, the 512-wide /
     at-most-64-token geometry the fused stage head and tail are built for, the 2 * n_layers cross-attention [W_k; W_v]
     pairs (biases and gradient buffers too) as rows of one matrix in (direction, layer) order - dp.FlatModel lays a whole
@@ -49,48 +52,20 @@ def supported(dec, encoder_outputs):
         return None
     if any(ops._gbuf(p) is None for p in dec.parameters()):
         return None
-    layers = [[_Layer(l) for l in dec._layers(d)] for d in (0, 1)]
-    kv = layers[0] + layers[1]
-    if not (ops._adjacent(*[w for L in kv for w in (L.wkv, L.wv_e)]) and ops._adjacent(*[b for L in kv for b in (L.bkv, L.bv_e)])
-            and ops._adjacent(*[g for L in kv for g in (L.g_wkv, L.g_wv_e)]) and ops._adjacent(*[g for L in kv for g in (L.g_bkv, L.g_bv_e)])):
+    ws, bs = ops.kv_block([l.enc_attn for d in (0, 1) for l in dec._layers(d)])
+    if not all(ops._adjacent(*ts) and ops._adjacent(*map(ops._gbuf, ts)) for ts in (ws, bs)):
         return None
-    if any(L0.shared != L1.shared for L0, L1 in zip(*layers)):
+    layers = [[_layer(l) for l in dec._layers(d)] for d in (0, 1)]
+    if any((h0.drop_p, h0.ln[4]) != (h1.drop_p, h1.ln[4]) for L0, L1 in zip(*layers) for h0, h1 in zip(L0, L1)):      # one value per launch
         return None
     return layers
 
 
-class _Layer:
-    """Parameter handles of one DecoderLayer (fused QKV weights of the self-attention are adjacent rows)."""
-
-    def __init__(self, lay):
-        lay.slf_attn._fuse()
-        lay.enc_attn._fuse()
-        sa, ea, ff = lay.slf_attn, lay.enc_attn, lay.pos_ffn
-        self.wqkv, self.bqkv = sa.w_qs.weight, sa.w_qs.bias                  # first of three adjacent blocks
-        assert ops._adjacent(sa.w_qs.weight, sa.w_ks.weight, sa.w_vs.weight) and ops._adjacent(sa.w_qs.bias, sa.w_ks.bias, sa.w_vs.bias)
-        gw = [ops._gbuf(t) for t in (sa.w_qs.weight, sa.w_ks.weight, sa.w_vs.weight)]
-        gb = [ops._gbuf(t) for t in (sa.w_qs.bias, sa.w_ks.bias, sa.w_vs.bias)]
-        assert ops._adjacent(*gw) and ops._adjacent(*gb)
-        self.g_wqkv, self.g_bqkv = gw[0], gb[0]
-        self.wfc_s, self.bfc_s, self.g_wfc_s, self.g_bfc_s = sa.fc.weight, sa.fc.bias, ops._gbuf(sa.fc.weight), ops._gbuf(sa.fc.bias)
-        self.ln_s = (sa.layer_norm.weight, sa.layer_norm.bias, ops._gbuf(sa.layer_norm.weight), ops._gbuf(sa.layer_norm.bias), sa.layer_norm.eps)
-        self.wq, self.bq, self.g_wq, self.g_bq = ea.w_qs.weight, ea.w_qs.bias, ops._gbuf(ea.w_qs.weight), ops._gbuf(ea.w_qs.bias)
-        assert ops._adjacent(ea.w_ks.weight, ea.w_vs.weight) and ops._adjacent(ea.w_ks.bias, ea.w_vs.bias)
-        self.wkv, self.bkv = ea.w_ks.weight, ea.w_ks.bias
-        self.wv_e, self.bv_e = ea.w_vs.weight, ea.w_vs.bias
-        gkw, gkb = [ops._gbuf(t) for t in (ea.w_ks.weight, ea.w_vs.weight)], [ops._gbuf(t) for t in (ea.w_ks.bias, ea.w_vs.bias)]
-        assert ops._adjacent(*gkw) and ops._adjacent(*gkb)
-        self.g_wkv, self.g_bkv = gkw[0], gkb[0]
-        self.g_wv_e, self.g_bv_e = gkw[1], gkb[1]
-        self.wfc_e, self.bfc_e, self.g_wfc_e, self.g_bfc_e = ea.fc.weight, ea.fc.bias, ops._gbuf(ea.fc.weight), ops._gbuf(ea.fc.bias)
-        self.ln_e = (ea.layer_norm.weight, ea.layer_norm.bias, ops._gbuf(ea.layer_norm.weight), ops._gbuf(ea.layer_norm.bias), ea.layer_norm.eps)
-        self.w1, self.b1, self.g_w1, self.g_b1 = ff.w_1.weight, ff.w_1.bias, ops._gbuf(ff.w_1.weight), ops._gbuf(ff.w_1.bias)
-        self.w2, self.b2, self.g_w2, self.g_b2 = ff.w_2.weight, ff.w_2.bias, ops._gbuf(ff.w_2.weight), ops._gbuf(ff.w_2.bias)
-        self.ln_f = (ff.layer_norm.weight, ff.layer_norm.bias, ops._gbuf(ff.layer_norm.weight), ops._gbuf(ff.layer_norm.bias), ff.layer_norm.eps)
-        self.drop_s = sa.dropout.p if sa.training else 0.0
-        self.drop_e = ea.dropout.p if ea.training else 0.0
-        self.drop_f = ff.dropout.p if ff.training else 0.0
-        self.shared = (self.drop_s, self.drop_e, self.drop_f, self.ln_s[4], self.ln_e[4], self.ln_f[4])    # one value per launch
+def _layer(lay):
+    """The (self-attention, cross-attention, feed-forward) parameter handles (ops.SubLayer) of one DecoderLayer."""
+    hs = (lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle())
+    assert all(lin.gw is not None for h in hs for lin in (h.inp, h.out)), "fused gradient buffers are not adjacent"
+    return hs
 
 
 class DecoderStagesFn(torch.autograd.Function):
@@ -119,9 +94,7 @@ class DecoderStagesFn(torch.autograd.Function):
         training = dec.training
         p_emb = dec.dropout.p if training else 0.0
 
-        def E(*shape):
-            return torch.empty(*shape, device=dev, dtype=torch.float32)
-
+        E = lambda *shape: ops._new(enc_out, *shape)      # noqa: E731
         # ---- all-stage buffers
         B_ = [[None] * nl for _ in (0, 1)]
         for d in (0, 1):
@@ -145,58 +118,58 @@ class DecoderStagesFn(torch.autograd.Function):
         # ---- hoisted cross-attention K/V (attention.py:42-43 for every layer and direction; step-invariant).  The 12
         # [W_k; W_v] pairs are rows of ONE (12*1024, 512) matrix (supported()): one GEMM writes KV_all (N*T, 12*1024), layer
         # (d, n) reads its column block in place (row stride ldkv).
-        ldkv = 2 * HD * 2 * nl
-        kv_all = E(N * T, ldkv)
-        ops.gemm(0, 1, N * T, ldkv, D, enc2, D, layers[0][0].wkv, D, kv_all, ldkv, bias=layers[0][0].bkv)
+        kv_lin, kv_all, blocks = ops.project_kv_block(enc2, [l.enc_attn for d in (0, 1) for l in dec._layers(d)])
+        ldkv = kv_lin.N
         for d in (0, 1):
             for n in range(nl):
-                B_[d][n]["kv"] = kv_all[:, (d * nl + n) * 2 * HD:(d * nl + n + 1) * 2 * HD]
+                B_[d][n]["kv"] = blocks[d * nl + n]
 
         def layer_fwd(n, r0, r1, i0, segL):
             """Both directions of layer n in shared launches (same shapes, their own operands): kernel boundaries cost
             ~5 us each and small launches on two streams do not overlap, so the directions share launches, not streams."""
-            L0, L1, b0, b1 = layers[0][n], layers[1][n], B_[0][n], B_[1][n]
+            b0, b1 = B_[0][n], B_[1][n]
+            (s0, e0, f0), (s1, e1, f1) = layers[0][n], layers[1][n]
             M = r1 - r0
             seg_arr, nseg = segs(segL)
             sl = lambda b, k: b[k][r0:r1]
             sp = _p(seed) if training else None
             # self-attention sub-layer
             q0, q1 = sl(b0, "qkv"), sl(b1, "qkv")
-            ops.gemm2(M, 3 * HD, D, sl(b0, "x"), sl(b1, "x"), D, L0.wqkv, L1.wqkv, D, q0, q1, 3 * HD, L0.bqkv, L1.bqkv)
+            ops.gemm2(M, 3 * HD, D, sl(b0, "x"), sl(b1, "x"), D, s0.inp.w, s1.inp.w, D, q0, q1, 3 * HD, s0.inp.b, s1.inp.b)
             call("sbl_attention_seg2_fwd", _p(q0), _p(q1), 3 * HD, _p(q0[:, HD:]), _p(q1[:, HD:]), 3 * HD, _p(q0[:, 2 * HD:]), _p(q1[:, 2 * HD:]),
                  3 * HD, _p(sl(b0, "att")), _p(sl(b1, "att")), HD, b0["ps"].data_ptr() + 4 * ps_off[i0], b1["ps"].data_ptr() + 4 * ps_off[i0],
-                 1 if n == 0 else 0, N, H, seg_arr, nseg, 0, 0.125, L0.drop_s, sp if L0.drop_s > 0 else None,
+                 1 if n == 0 else 0, N, H, seg_arr, nseg, 0, 0.125, s0.drop_p, sp if s0.drop_p > 0 else None,
                  _fold(b0["off"][0], ps_off[i0]), _fold(b1["off"][0], ps_off[i0]), ops._s())
-            ops.gemm2(M, D, HD, sl(b0, "att"), sl(b1, "att"), HD, L0.wfc_s, L1.wfc_s, HD, sl(b0, "o_s"), sl(b1, "o_s"), D, L0.bfc_s, L1.bfc_s)
+            ops.gemm2(M, D, HD, sl(b0, "att"), sl(b1, "att"), HD, s0.out.w, s1.out.w, HD, sl(b0, "o_s"), sl(b1, "o_s"), D, s0.out.b, s1.out.b)
 
             def ln2(o, res, y, mu, rs, ln0, ln1, drop_p, k):
                 call("sbl_add_layernorm2_fwd", _p(sl(b0, o)), _p(sl(b1, o)), _p(sl(b0, res)), _p(sl(b1, res)), _p(ln0[0]), _p(ln1[0]),
                      _p(ln0[1]), _p(ln1[1]), _p(sl(b0, y)), _p(sl(b1, y)), _p(sl(b0, mu)), _p(sl(b1, mu)), _p(sl(b0, rs)), _p(sl(b1, rs)),
                      M, D, ln0[4], drop_p, sp if drop_p > 0 else None, _fold(b0["off"][k], r0 * D), _fold(b1["off"][k], r0 * D), ops._s())
 
-            ln2("o_s", "x", "y_s", "mu_s", "rs_s", L0.ln_s, L1.ln_s, L0.drop_s, 1)
+            ln2("o_s", "x", "y_s", "mu_s", "rs_s", s0.ln, s1.ln, s0.drop_p, 1)
             # cross-attention sub-layer
-            ops.gemm2(M, HD, D, sl(b0, "y_s"), sl(b1, "y_s"), D, L0.wq, L1.wq, D, sl(b0, "q"), sl(b1, "q"), HD, L0.bq, L1.bq)
+            ops.gemm2(M, HD, D, sl(b0, "y_s"), sl(b1, "y_s"), D, e0.inp.w, e1.inp.w, D, sl(b0, "q"), sl(b1, "q"), HD, e0.inp.b, e1.inp.b)
             kv0, kv1 = b0["kv"], b1["kv"]
             call("sbl_attention_seg2_fwd", _p(sl(b0, "q")), _p(sl(b1, "q")), HD, _p(kv0), _p(kv1), ldkv, _p(kv0[:, HD:]), _p(kv1[:, HD:]), ldkv,
                  _p(sl(b0, "att2")), _p(sl(b1, "att2")), HD, b0["pe"].data_ptr() + 4 * pe_off[i0], b1["pe"].data_ptr() + 4 * pe_off[i0],
-                 0, N, H, seg_arr, nseg, T, 0.125, L0.drop_e, sp if L0.drop_e > 0 else None,
+                 0, N, H, seg_arr, nseg, T, 0.125, e0.drop_p, sp if e0.drop_p > 0 else None,
                  _fold(b0["off"][2], pe_off[i0]), _fold(b1["off"][2], pe_off[i0]), ops._s())
-            ops.gemm2(M, D, HD, sl(b0, "att2"), sl(b1, "att2"), HD, L0.wfc_e, L1.wfc_e, HD, sl(b0, "o_e"), sl(b1, "o_e"), D, L0.bfc_e, L1.bfc_e)
-            ln2("o_e", "y_s", "y_e", "mu_e", "rs_e", L0.ln_e, L1.ln_e, L0.drop_e, 3)
+            ops.gemm2(M, D, HD, sl(b0, "att2"), sl(b1, "att2"), HD, e0.out.w, e1.out.w, HD, sl(b0, "o_e"), sl(b1, "o_e"), D, e0.out.b, e1.out.b)
+            ln2("o_e", "y_s", "y_e", "mu_e", "rs_e", e0.ln, e1.ln, e0.drop_p, 3)
             # position-wise feed-forward sub-layer
-            ops.gemm2(M, F_, D, sl(b0, "y_e"), sl(b1, "y_e"), D, L0.w1, L1.w1, D, sl(b0, "h"), sl(b1, "h"), F_, L0.b1, L1.b1, relu=1)
-            ops.gemm2(M, D, F_, sl(b0, "h"), sl(b1, "h"), F_, L0.w2, L1.w2, F_, sl(b0, "o_f"), sl(b1, "o_f"), D, L0.b2, L1.b2)
+            ops.gemm2(M, F_, D, sl(b0, "y_e"), sl(b1, "y_e"), D, f0.inp.w, f1.inp.w, D, sl(b0, "h"), sl(b1, "h"), F_, f0.inp.b, f1.inp.b, relu=1)
+            ops.gemm2(M, D, F_, sl(b0, "h"), sl(b1, "h"), F_, f0.out.w, f1.out.w, F_, sl(b0, "o_f"), sl(b1, "o_f"), D, f0.out.b, f1.out.b)
             if n + 1 < nl:
                 # the sub-layer's LayerNorm and the cross-direction fusion that feeds layer n + 1, one launch; y_f is not stored
                 nb0, nb1 = B_[0][n + 1]["x"][r0:r1], B_[1][n + 1]["x"][r0:r1]
                 call("sbl_add_layernorm2_fusion_fwd", _p(sl(b0, "o_f")), _p(sl(b1, "o_f")), _p(sl(b0, "y_e")), _p(sl(b1, "y_e")),
-                     _p(L0.ln_f[0]), _p(L1.ln_f[0]), _p(L0.ln_f[1]), _p(L1.ln_f[1]), _p(nb0), _p(nb1), _p(sl(b0, "mu_f")), _p(sl(b1, "mu_f")),
-                     _p(sl(b0, "rs_f")), _p(sl(b1, "rs_f")), N, seg_arr, nseg, D, L0.ln_f[4], L0.drop_f, sp if L0.drop_f > 0 else None,
+                     _p(f0.ln[0]), _p(f1.ln[0]), _p(f0.ln[1]), _p(f1.ln[1]), _p(nb0), _p(nb1), _p(sl(b0, "mu_f")), _p(sl(b1, "mu_f")),
+                     _p(sl(b0, "rs_f")), _p(sl(b1, "rs_f")), N, seg_arr, nseg, D, f0.ln[4], f0.drop_p, sp if f0.drop_p > 0 else None,
                      _fold(b0["off"][4], r0 * D), _fold(b1["off"][4], r0 * D), ops._s())
             else:
                 # (the last fusion is only ever read at the last positions: stage tail)
-                ln2("o_f", "y_e", "y_f", "mu_f", "rs_f", L0.ln_f, L1.ln_f, L0.drop_f, 4)
+                ln2("o_f", "y_e", "y_f", "mu_f", "rs_f", f0.ln, f1.ln, f0.drop_p, 4)
 
         for (i0, i1) in _decoder.stages_of(coins, ML):
             segL = tuple(range(i0 + 1, i1 + 2))
@@ -215,10 +188,10 @@ class DecoderStagesFn(torch.autograd.Function):
                  _p(last[0][lrows]), _p(last[1][lrows]), _p(pred[0][lrows]), _p(pred[1][lrows]), V, _p(ys[0]), _p(ys[1]),
                  ys[0].stride(0), i1, int(bool(coins[i1])), N, seg_arr, nseg, D, V, ops._s())
 
-        ctx.state = dict(N=N, T=T, D=D, H=H, HD=HD, F=F_, V=V, ML=ML, nl=nl, R=R, layers=layers, B=B_, last=last, ys=ys,
+        ctx.state = dict(N=N, T=T, D=D, HD=HD, V=V, ML=ML, nl=nl, R=R, layers=layers, B=B_, last=last, ys=ys,
                          heads=heads, g_heads=(ops._gbuf(heads[0]), ops._gbuf(heads[1])), g_emb=ops._gbuf(emb), seed=seed,
                          p_emb=p_emb, off_emb=off_emb, streams=streams, two=side is not None, enc2=enc2, training=training,
-                         ldkv=ldkv)
+                         kv_lin=kv_lin)
         ctx.set_materialize_grads(False)
         dec.last_ys = ys
         # (ML*N, V) step-major -> (N, ML, V) views
@@ -229,22 +202,20 @@ class DecoderStagesFn(torch.autograd.Function):
     def backward(ctx, dpl, dpr):
         S = ctx.state
         call, gemm, segs, _p = ops.call, ops.gemm, ops._segs, ops._p
-        N, T, D, H, HD, F_, V, ML, nl, R = (S[k] for k in ("N", "T", "D", "H", "HD", "F", "V", "ML", "nl", "R"))
+        N, T, D, HD, V, ML, nl, R = (S[k] for k in ("N", "T", "D", "HD", "V", "ML", "nl", "R"))
         layers, B_, streams = S["layers"], S["B"], S["streams"]
         main, side = streams[0], (streams[1] if S["two"] else None)
         dev = S["enc2"].device
         seed = S["seed"]
         segL = tuple(range(1, ML + 1))
         seg_arr, nseg = segs(segL)
-        ldkv = S["ldkv"]
+        ldkv = S["kv_lin"].N
 
-        def E(*shape):
-            return torch.empty(*shape, device=dev, dtype=torch.float32)
-
+        E = lambda *shape: ops._new(S["enc2"], *shape)      # noqa: E731
         wg = {}           # deferred weight gradients by row count: (C, ldc, colsum, [A], lda, [B], ldb, M, N), see ops.wgrad_group
 
-        def dW(C, colsum, A, lda, Bm, ldb, M, Nn, rows=R):
-            wg.setdefault(rows, []).append((C, Nn, colsum, [A], lda, [Bm], ldb, M, Nn))
+        def dW(lin, dY, X):      # the weight-gradient sink of ops.attn_bwd / ops.ffn_bwd
+            wg.setdefault(X.size(0), []).append((lin.gw, lin.K, lin.gb, [dY], lin.N, [X], lin.K, lin.N, lin.K))
 
         if side is not None:
             side.wait_stream(main)
@@ -262,54 +233,22 @@ class DecoderStagesFn(torch.autograd.Function):
                 dx[d] = E(R, D)
                 call("sbl_gather_last_bwd", _p(dlast), _p(dx[d]), N, seg_arr, nseg, D, ops._s())
 
-        def ln_bwd(dy, o, res, ln, mu, rs, drop_p, off):
-            g, _, gg, gb, _ = ln
-            dz = E(R, D)
-            do = E(R, D)          # separate: the deferred weight gradient reads it after dz has been accumulated into
-            call("sbl_add_layernorm_bwd", _p(dy), _p(o), _p(res), _p(g), _p(mu), _p(rs), _p(dz), _p(do), _p(gg), _p(gb), R, D, drop_p,
-                 _p(seed) if drop_p > 0 else None, off, ops._s())
-            return dz, do
-
         def layer_bwd(d, n, dy):
-            L, b = layers[d][n], B_[d][n]
-            # feed-forward
-            dz, do = ln_bwd(dy, b["o_f"], b["y_e"], L.ln_f, b["mu_f"], b["rs_f"], L.drop_f, b["off"][4])
-            dW(L.g_w2, L.g_b2, do, D, b["h"], F_, D, F_)
-            dh = E(R, F_)
-            gemm(0, 0, R, F_, D, do, D, L.w2, F_, dh, F_, mask=b["h"], ldm=F_)
-            dW(L.g_w1, L.g_b1, dh, F_, b["y_e"], D, F_, D)
-            gemm(0, 0, R, D, F_, dh, F_, L.w1, D, dz, D, accumulate=1)
-            # cross-attention
-            dz2, do2 = ln_bwd(dz, b["o_e"], b["y_s"], L.ln_e, b["mu_e"], b["rs_e"], L.drop_e, b["off"][3])
-            dW(L.g_wfc_e, L.g_bfc_e, do2, D, b["att2"], HD, D, HD)
-            datt = E(R, HD)
-            gemm(0, 0, R, HD, D, do2, D, L.wfc_e, HD, datt, HD)
-            dq = E(R, HD)
-            kv = b["kv"]
-            dkv = dkv_all[:, (d * nl + n) * 2 * HD:(d * nl + n + 1) * 2 * HD]
-            # the 16 segments share the keys: one workgroup per (batch, head) sums their dK / dV contributions in LDS
-            call("sbl_attention_seg_bwd", _p(datt), HD, _p(b["q"]), HD, _p(kv), ldkv, _p(kv[:, HD:]), ldkv, _p(b["pe"]), _p(dq), HD,
-                 _p(dkv), ldkv, _p(dkv[:, HD:]), ldkv, N, H, seg_arr, nseg, T, 0.125, L.drop_e,
-                 _p(seed) if L.drop_e > 0 else None, b["off"][2], ops._s())
-            dW(L.g_wq, L.g_bq, dq, HD, b["y_s"], D, HD, D)
-            gemm(0, 0, R, D, HD, dq, HD, L.wq, D, dz2, D, accumulate=1)
-            # self-attention
-            dz3, do3 = ln_bwd(dz2, b["o_s"], b["x"], L.ln_s, b["mu_s"], b["rs_s"], L.drop_s, b["off"][1])
-            dW(L.g_wfc_s, L.g_bfc_s, do3, D, b["att"], HD, D, HD)
-            datt = E(R, HD)
-            gemm(0, 0, R, HD, D, do3, D, L.wfc_s, HD, datt, HD)
-            dqkv = E(R, 3 * HD)
-            qkv = b["qkv"]
-            call("sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), 3 * HD, _p(qkv[:, HD:]), 3 * HD, _p(qkv[:, 2 * HD:]), 3 * HD, _p(b["ps"]),
-                 _p(dqkv), 3 * HD, _p(dqkv[:, HD:]), 3 * HD, _p(dqkv[:, 2 * HD:]), 3 * HD, N, H, seg_arr, nseg, 0, 0.125, L.drop_s,
-                 _p(seed) if L.drop_s > 0 else None, b["off"][0], ops._s())
-            dW(L.g_wqkv, L.g_bqkv, dqkv, 3 * HD, b["x"], D, 3 * HD, D)
-            gemm(0, 0, R, D, 3 * HD, dqkv, 3 * HD, L.wqkv, D, dz3, D, accumulate=1)
-            return dz3
+            """The sub-layers' adjoints over the rows of all steps, with the forward's offsets; always a separate pre-dropout
+            gradient (the grouped launch below reads it after the input gradient has been accumulated into dz)."""
+            (slf, enc, ffn), b = layers[d][n], B_[d][n]
+            off = b["off"]
+            dy = ops.ffn_bwd(ffn, dy, b["y_e"], (b["h"], b["o_f"], b["mu_f"], b["rs_f"]), seed, off[4], True, dW)
+            dy, _ = ops.attn_bwd(enc, dy, b["y_s"], (b["q"], b["att2"], b["pe"], b["o_e"], b["mu_e"], b["rs_e"]), N, segL, b["kv"],
+                                 seed, off[2], off[3], True, dW, dkv=dkv_blocks[d * nl + n])
+            dy, _ = ops.attn_bwd(slf, dy, b["x"], (b["qkv"], b["att"], b["ps"], b["o_s"], b["mu_s"], b["rs_s"]), N, segL, None,
+                                 seed, off[0], off[1], True, dW)
+            return dy
 
         # gradient of the hoisted K/V: column block (direction, layer) of one (N*T, 12*1024) buffer, so that its input gradient
         # is ONE product over K = 12*1024 below
         dkv_all = E(N * T, ldkv)
+        dkv_blocks = dkv_all.split(2 * HD, 1)
         for n in range(nl - 1, -1, -1):
             if side is not None:
                 main.wait_stream(side)
@@ -334,9 +273,8 @@ class DecoderStagesFn(torch.autograd.Function):
             main.wait_stream(side)
         # dEnc = [dKV_0 | ... | dKV_11] (N*T, 12*1024) x [Wkv_0; ...; Wkv_11] (12*1024, 512): ONE product instead of 12
         # launches plus the adds of their partial results; its weight gradient is one (12*1024, 512) problem too
-        L = layers[0][0]
-        gemm(0, 0, N * T, D, ldkv, dkv_all, ldkv, L.wkv, D, denc, D)
-        dW(L.g_wkv, L.g_bkv, dkv_all, ldkv, S["enc2"], D, ldkv, D, rows=N * T)
+        gemm(0, 0, N * T, D, ldkv, dkv_all, ldkv, S["kv_lin"].w, D, denc, D)
+        dW(S["kv_lin"], dkv_all, S["enc2"])
         # ---- every weight gradient of the decoder: one grouped launch over the R rows of all steps (and the K/V problem over
         # its N*T rows) on the side stream, issued right here: it then runs beside the encoder backward, a dependent chain of
         # 928-row products that cannot fill the chip.  (Issuing it after backward has passed the encoder measured slower for the

@@ -34,10 +34,17 @@ class PositionwiseFeedForward(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.layer_norm = nn.LayerNorm(d_model)
 
+    def _params(self):
+        """The arguments of ops.ffn_handle, which are also those of ops.FFNFn after x."""
+        return (self.w_1.weight, self.w_1.bias, self.w_2.weight, self.w_2.bias, self.layer_norm.weight, self.layer_norm.bias,
+                self.dropout.p if self.training else 0.0, self.layer_norm.eps)
+
+    def handle(self):
+        """This sub-layer's parameter handle for the ops.ffn_* functions."""
+        return ops.ffn_handle(*self._params())
+
     def forward(self, x):
-        drop_p = self.dropout.p if self.training else 0.0
-        return ops.FFNFn.apply(x, self.w_1.weight, self.w_1.bias, self.w_2.weight, self.w_2.bias,
-                               self.layer_norm.weight, self.layer_norm.bias, drop_p, self.layer_norm.eps)
+        return ops.FFNFn.apply(x, *self._params())
 
 
 def mask_rows(x, non_pad_mask):

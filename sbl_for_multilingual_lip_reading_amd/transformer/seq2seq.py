@@ -4,7 +4,8 @@ LRW1000 directory has the same classes with a 48-token vocabulary), the baseline
 Seq2SeqDecoder / Seq2SeqTransformer keep the constructor and forward signatures and the state-dict keys of
 LRW/transformer/decoder.py:Decoder and LRW/transformer/transformer.py:Transformer.  The teacher-forced pass is built from the
 entry points the SBL model uses; the greedy decode keeps a K/V cache per layer and processes one new row per clip and step
-(csrc/decode_step.hip) instead of re-running the whole prefix at every step as LRW/transformer/decoder.py:146-164 does: every
+(csrc/decode_step.hip; the GEMM / LayerNorm launches around that one-row attention core are the shared sub-layer functions
+of ops.py) instead of re-running the whole prefix at every step as LRW/transformer/decoder.py:146-164 does: every
 layer of this decoder is causal, so row i of every sub-layer depends on rows <= i only."""
 import torch
 import torch.nn as nn
@@ -78,25 +79,14 @@ class Seq2SeqDecoder(nn.Module):
         for lay in self.layer_stack:
             lay.slf_attn._fuse()
         mods = self.cross_attention_modules()
-        ws = [w for m in mods for w in (m.w_ks.weight, m.w_vs.weight)]
-        bs = [b for m in mods for b in (m.w_ks.bias, m.w_vs.bias)]
+        ws, bs = ops.kv_block(mods)
         for m in mods:
             m.kv_in_block = True
         if ops._adjacent(*ws) and ops._adjacent(*bs):
             return
         if getattr(ws[0], "_sbl_flat", None) is not None:
             raise _lib.SblHipError("Seq2SeqDecoder: the flat model's cross-attention K/V block is not contiguous")
-        with torch.no_grad():
-            fw = torch.cat([w.data for w in ws], 0).contiguous()
-            fb = torch.cat([b.data for b in bs], 0).contiguous()
-            if fw.is_cuda:      # one-time set-up: the old storages are released below, so the copies must have run
-                torch.cuda.current_stream(fw.device).synchronize()
-            r = 0
-            for w, b in zip(ws, bs):
-                n = w.size(0)
-                w.data = fw[r:r + n]
-                b.data = fb[r:r + n]
-                r += n
+        ops.fuse_rows(ws, bs)
 
     # ------------------------------------------------------------------ teacher-forced pass
     def preprocess(self, padded_input):
@@ -195,48 +185,33 @@ class Seq2SeqDecoder(nn.Module):
             raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
         N, T, D = enc.shape
         dev = enc.device
-        layers = list(self.layer_stack)
+        layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
         nl, H = len(layers), self.n_head
         HD, F_ = H * 64, self.d_inner
-        call, gemm, _p, _s = ops.call, ops.gemm, ops._p, ops._s
         new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
 
         # the K / V of the encoder output for all layers: one GEMM against the [K_0; V_0; K_1; ...] block
-        cross = self.cross_attention_modules()
-        enc2 = enc.contiguous().view(N * T, D)
-        kv = new(N * T, nl * 2 * HD)
-        gemm(0, 1, N * T, nl * 2 * HD, D, enc2, D, cross[0].w_ks.weight, D, kv, nl * 2 * HD, bias=cross[0].w_ks.bias)
-        kv3 = kv.view(N, T, nl * 2 * HD)
+        kv = [blk.view(N, T, 2 * HD) for blk in ops.project_kv_block(enc.contiguous().view(N * T, D), self.cross_attention_modules())[2]]
         cache = new(nl, 2, N, T, HD)          # self-attention K / V rows of every layer; row i is written at step i
         ys = self._new_ys(enc)
         emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
         V, scale = emb.size(0), float(self.x_logit_scale)
         x = new(N, D)
-        call("sbl_embed_scale_pe_fwd", _p(ys), ys.stride(0), _p(emb), _p(pe), _p(x), N, 1, D, V, scale, 0, _s())
+        ops.call("sbl_embed_scale_pe_fwd", ops._p(ys), ys.stride(0), ops._p(emb), ops._p(pe), ops._p(x), N, 1, D, V, scale, 0, ops._s())
         qkv, q, att, o, h = new(N, 3 * HD), new(N, HD), new(N, HD), new(N, D), new(N, F_)
         ya, yb, yc = new(N, D), new(N, D), new(N, D)
         mean, rstd = new(N), new(N)
 
-        def add_ln(x_, res, ln, out):
-            call("sbl_add_layernorm_fwd", _p(x_), _p(res), _p(ln.weight), _p(ln.bias), _p(out), _p(mean), _p(rstd), N, D, ln.eps,
-                 0.0, None, 0, _s())
-
         for i in range(T):
             cur = x
-            for l, lay in enumerate(layers):
-                sa, ca, ff = lay.slf_attn, lay.enc_attn, lay.pos_ffn
-                gemm(0, 1, N, 3 * HD, D, cur, D, sa.w_qs.weight, D, qkv, 3 * HD, bias=sa.w_qs.bias)
+            for l, (sa, ca, ff) in enumerate(layers):
+                ops.lin_fwd(sa.inp, cur, qkv)
                 ops.decode_attn_step(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], T, att, H, i, True)
-                gemm(0, 1, N, D, HD, att, HD, sa.fc.weight, HD, o, D, bias=sa.fc.bias)
-                add_ln(o, cur, sa.layer_norm, ya)
-                gemm(0, 1, N, HD, D, ya, D, ca.w_qs.weight, D, q, HD, bias=ca.w_qs.bias)
-                c0 = l * 2 * HD
-                ops.decode_attn_step(q, None, None, kv3[:, :, c0:c0 + HD], kv3[:, :, c0 + HD:c0 + 2 * HD], T, att, H, T, False)
-                gemm(0, 1, N, D, HD, att, HD, ca.fc.weight, HD, o, D, bias=ca.fc.bias)
-                add_ln(o, ya, ca.layer_norm, yb)
-                gemm(0, 1, N, F_, D, yb, D, ff.w_1.weight, D, h, F_, bias=ff.w_1.bias, relu=1)
-                gemm(0, 1, N, D, F_, h, F_, ff.w_2.weight, F_, o, D, bias=ff.w_2.bias)
-                add_ln(o, yb, ff.layer_norm, yc)
+                ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
+                ops.lin_fwd(ca.inp, ya, q)
+                ops.decode_attn_step(q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
+                ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
+                ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
                 cur = yc
             ops.decode_tail(cur, w, ys, i, emb, pe, scale, x_next=x if i + 1 < T else None)
         return ys
