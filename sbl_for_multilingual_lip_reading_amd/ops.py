@@ -9,6 +9,7 @@ non-zero status raises.
 All Functions are hipGraph-capturable: no host sync, no host read of device data;
 dropout seeds and teacher-forcing coins live in device memory.
 """
+import collections as _collections
 import copy as _copy
 import ctypes as _ct
 import functools as _functools
@@ -1373,177 +1374,247 @@ def _dgrad_weight(w, w_dg):
     return w_dg
 
 
-class ConvBNFn(torch.autograd.Function):
-    """conv (3x3 pad 1 | 1x1 pad 0, bias-free) -> BatchNorm2d -> [+ residual] -> [ReLU] on NHWC activations;
-    video_frontend.py:28-41,69-71.  The BN batch statistics are reduced in the conv epilogue."""
+# --- the ResNet trunk: plain functions over explicit tensors, then one tape node per BasicBlock ---
+# One conv -> BatchNorm2d pair of a block: its three differentiable tensors, then what the BN layer keeps and the settings.
+ConvBN = _collections.namedtuple("ConvBN", "w gamma beta running_mean running_var nbt stride momentum eps")
+
+
+def _conv_geom(x, w, stride):
+    """The nine integers every trunk convolution entry point takes: NHWC x, OIHW weight, 3x3 pad 1 or 1x1 pad 0."""
+    NIMG, H, W, Cin = x.shape
+    Cout, _, KH, KW = w.shape
+    return NIMG, H, W, Cin, Cout, KH, KW, stride, (1 if KH == 3 else 0)
+
+
+def conv_bn_fwd(x, c, res, relu, training, need_dg):
+    """conv (bias-free) -> BatchNorm2d -> [+ res] -> [ReLU] on NHWC activations; video_frontend.py:28-41,69-71.
+    -> (pre-BN output, y, mean, invstd, the weight image the input gradient reads or None).  The BN batch statistics are
+    reduced in the conv epilogue; BN side effects (running statistics, c.nbt += 1) like nn.BatchNorm2d."""
+    g = _conv_geom(x, c.w, c.stride)
+    NIMG, H, W, _, Cout, KH, KW, stride, pad = g
+    Ho = (H + 2 * pad - KH) // stride + 1
+    Wo = (W + 2 * pad - KW) // stride + 1
+    dev = x.device
+    # packed weight images (OHWI; and [Cin][kh][kw][Cout] for the input gradient, kept for backward): cached across
+    # steps, see packed_conv_weight.  The BN statistics the convolution's epilogue accumulates into come zero-filled from
+    # the step's pooled memset (or are zeroed by the pack launch / a fill when the pool is not armed).
+    # (Measured and not kept in round 2: all 19 packs on the side stream while the stem runs - same-box A/B 32.94 vs
+    # 32.72 ms, the fork/join and the contention with the stem cost more than the 10 us per convolution they take off.)
+    stats, pooled_stats = _zeros_or_empty(dev, (2 * Cout,), torch.float64) if training else (None, False)
+    w_ohwi, w_dg = packed_conv_weight(c.w, training and need_dg, None if pooled_stats else stats)
+    conv = torch.empty(NIMG, Ho, Wo, Cout, device=dev, dtype=torch.float32)
+    mean = torch.empty(Cout, device=dev, dtype=torch.float32)
+    invstd = torch.empty(Cout, device=dev, dtype=torch.float32)
+    y = torch.empty_like(conv)
+    call("sbl_conv2d_fwd", _p(x), _p(w_ohwi), _p(conv), _p(stats), int(training), *g, _workspace().data_ptr(), WS_BYTES, _s())
+    if training:
+        # the BatchNorm "finalize" (mean / invstd / running statistics / num_batches_tracked) rides on the apply launch
+        call("sbl_bn_apply_fwd_stats", _p(conv), _p(res), _p(stats), NIMG * Ho * Wo, _p(c.running_mean), _p(c.running_var), c.momentum,
+             c.eps, _p(c.gamma), _p(c.beta), _p(y), _p(mean), _p(invstd), _p(c.nbt), NIMG * Ho * Wo, Cout, int(relu), _s())
+    else:
+        call("sbl_bn_eval_stats", _p(c.running_mean), _p(c.running_var), c.eps, _p(mean), _p(invstd), Cout, _s())
+        call("sbl_bn_apply_fwd", _p(conv), _p(res), _p(mean), _p(invstd), _p(c.gamma), _p(c.beta), _p(y), NIMG * Ho * Wo, Cout,
+             int(relu), _s())
+    return conv, y, mean, invstd, w_dg
+
+
+def bn_bwd_reduce(dy, y, bn):
+    """The two fp64 backward sums per channel (sum g, sum g * xhat; g = dy * [y > 0], y None: no ReLU) of bn = (pre-BN
+    output, mean, invstd), in a pass of their own: for a BatchNorm nobody's input-gradient epilogue reduced them for."""
+    conv, mean, invstd = bn
+    Cout = conv.size(-1)
+    sums = torch.empty(2 * Cout, device=conv.device, dtype=torch.float64)
+    call("sbl_bn_bwd_reduce", _p(dy), _p(y), _p(conv), _p(mean), _p(invstd), _p(sums), conv.numel() // Cout, Cout, int(y is not None),
+         _workspace().data_ptr(), WS_BYTES, _s())
+    return sums
+
+
+def bn_bwd_apply(dy, y, bn, gamma, beta, sums, with_res):
+    """BatchNorm (+ ReLU when y is given) backward from its sums -> (dconv, the residual branch's gradient or None, dgamma,
+    dbeta).  With persistent gradient buffers the kernel adds dgamma / dbeta into them and None goes back to autograd."""
+    conv, mean, invstd = bn
+    Cout = conv.size(-1)
+    dconv = torch.empty_like(conv)
+    dres = torch.empty_like(conv) if with_res else None
+    dgamma, dbeta = _gbuf(gamma), _gbuf(beta)
+    acc = dgamma is not None and dbeta is not None
+    if not acc:
+        dgamma = torch.empty(Cout, device=conv.device, dtype=torch.float32)
+        dbeta = torch.empty(Cout, device=conv.device, dtype=torch.float32)
+    call("sbl_bn_bwd_apply", _p(dy), _p(y), _p(conv), _p(mean), _p(invstd), _p(gamma), _p(sums), _p(dconv), _p(dres),
+         _p(dgamma), _p(dbeta), conv.numel() // Cout, Cout, int(y is not None), int(acc), _s())
+    return (dconv, dres, None, None) if acc else (dconv, dres, dgamma, dbeta)
+
+
+def conv_dgrad(dconv, w, w_dg, x, stride, addend=None, bn=None, bn_ds=None):
+    """Input gradient of a trunk convolution and what rides on its epilogue -> (dx, sums or None).
+    bn / bn_ds = (pre-BN output, mean, invstd) of the BatchNorm(s) + ReLU that produced x: their backward sums are
+    reduced over the finished dx (2 * Cin fp64 each, bn's first).  addend: added to dx first - the residual branch's
+    gradient, or the compact even/even-pixel gradient of a 1x1 / stride-2 shortcut.  Without an addend this is
+    sbl_conv2d_dgrad_bnstats, with one sbl_conv2d_dgrad_fused; a block's backward has no use for the plain
+    sbl_conv2d_dgrad."""
+    Cin = x.size(-1)
+    w_dg = _dgrad_weight(w, w_dg)
+    dx = torch.empty_like(x)
+    n_bn = (bn is not None) + (bn_ds is not None)
+    sums, pooled = _zeros_or_empty(x.device, (2 * n_bn * Cin,), torch.float64) if n_bn else (None, False)
+    head = (_p(dconv), _p(w_dg), _p(dx), *_conv_geom(x, w, stride), _workspace().data_ptr(), WS_BYTES)
+    if addend is None:
+        call("sbl_conv2d_dgrad_bnstats", *head, _p(x), *map(_p, bn), _p(sums), int(pooled), _s())
+    else:
+        call("sbl_conv2d_dgrad_fused", *head, _p(addend), _p(x if n_bn else None), *map(_p, bn or (None,) * 3), *map(_p, bn_ds or (None,) * 3),
+             _p(sums), int(pooled), _s())
+    return dx, sums
+
+
+def conv_wgrad(x, dconv, w, stride):
+    """Weight gradient of a trunk convolution -> dw (OIHW), or None after adding it into w's persistent gradient buffer.
+    The weight gradient is off backward's dependency chain: with a persistent gradient buffer it is issued on the second
+    stream, where its workgroups fill the CUs that the chain's kernels (tile-count quantisation: 522 workgroups on 256 CUs)
+    leave idle; joined by an end-of-backward engine callback."""
+    g = _conv_geom(x, w, stride)
+    _, _, _, Cin, Cout, KH, KW, _, _ = g
+    dev = x.device
+
+    def launch(dw_ohwi, pooled, target, acc):
+        call("sbl_conv2d_wgrad", _p(x), _p(dconv), _p(dw_ohwi), *g, int(pooled), _s())
+        call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(target), Cout, Cin, KH, KW, acc, _s())
+
+    gw = _gbuf(w)
+    if gw is None:
+        dw = torch.empty_like(w)
+        launch(torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32), False, dw, 0)
+        return dw
+    side = side_stream(dev)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        launch(*_zeros_or_empty(dev, (Cout, KH, KW, Cin), torch.float32), gw, 1)
+    x.record_stream(side)
+    dconv.record_stream(side)
+    _arm_side_join()
+    return None
+
+
+class BlockHandoff:
+    """The one thing two consecutive BasicBlocks share.  It travels with the activation between them, as
+    `y._sbl_handoff` on the producer's output, so nn.Sequential stages and forward pre-hooks need not know about it.
+
+    Forward, the producer publishes: `bn2` and `bn_ds` - (pre-BN output, mean, invstd) of its bn2 and of its downsample
+    BatchNorm (None without one) - and `act`, the identity of y.
+    Backward, the consumer deposits: `sums` - the fp64 backward sums of those BatchNorms (bn2's 2 * C, then the
+    downsample's), which its conv1 input-gradient epilogue reduced over its dx - and `dx_ptr`, the identity of that dx.
+    The producer's backward takes the sums if its dy is that dx; otherwise (last block, a block on its own, a dy that
+    autograd summed from several consumers) it falls back to sbl_bn_bwd_reduce.
+
+    Only the ADDRESS of the activation is kept: the object hangs on y itself, a tensor in it would be a reference cycle
+    that only the cyclic GC frees - ~1 GB of trunk activations per step.  take() drops the published tensors, so a
+    second backward through the same graph finds nothing here and takes the fallbacks on both sides."""
+
+    __slots__ = ("act", "bn2", "bn_ds", "sums", "dx_ptr")
+
+    def __init__(self):
+        self.act = self.bn2 = self.bn_ds = self.sums = self.dx_ptr = None
+
+    def publish(self, y, bn2, bn_ds):
+        self.act, self.bn2, self.bn_ds = y.data_ptr(), bn2, bn_ds
+
+    def describes(self, x):
+        return self.bn2 is not None and self.act == x.data_ptr()
+
+    def deposit(self, sums, dx):
+        self.sums, self.dx_ptr = sums, dx.data_ptr()
+
+    def take(self, dy):
+        if self.sums is None or self.dx_ptr != dy.data_ptr():
+            return None
+        sums = self.sums
+        self.__init__()
+        return sums
+
+
+class BlockFn(torch.autograd.Function):
+    """A BasicBlock (video_frontend.py:28-41) on NHWC activations as ONE tape node: conv1-bn1-relu, the 1x1 / stride-2
+    conv-bn shortcut when there is one, conv2-bn2-(+shortcut)-relu.  Backward is the three convolutions' backward in
+    reverse, with every BatchNorm's reduction pass but the last block's bn2 riding on an input-gradient epilogue."""
 
     @staticmethod
-    def forward(ctx, x, w, gamma, beta, running_mean, running_var, res, relu, stride, training, momentum, eps, box_out=None,
-                box_in=None, nbt=None, ctl=None):
-        """box_out / box_in (dicts or None) link conv1 -> bn1 -> relu to the conv2 that consumes it (BasicBlock,
-        video_frontend.py:31-35): this node publishes (pre-BN output, mean, invstd) in box_out; the consumer, given the same
-        dict as box_in, computes bn1's backward reduction in the epilogue of its input-gradient convolution
-        (sbl_conv2d_dgrad_bnstats) and leaves the sums there, so this node's backward skips its reduction pass."""
-        _need_cuda(x, w, gamma, beta)
+    def forward(ctx, x, prev, pub, c1, c2, ds, training, *params):
+        """prev / pub: the BlockHandoff x came with / the one y will carry (None: none).  c1, c2, ds: ConvBN (ds None:
+        identity shortcut); params repeats their (w, gamma, beta) so that autograd sees them."""
+        _need_cuda(x, *params)
         x = x.contiguous()
-        NIMG, H, W, Cin = x.shape
-        Cout, _, KH, KW = w.shape
-        pad = 1 if KH == 3 else 0
-        Ho = (H + 2 * pad - KH) // stride + 1
-        Wo = (W + 2 * pad - KW) // stride + 1
-        dev = x.device
-        # packed weight images (OHWI; and [Cin][kh][kw][Cout] for the input gradient, kept for backward): cached across
-        # steps, see packed_conv_weight.  The BN statistics the convolution's epilogue accumulates into come zero-filled from
-        # the step's pooled memset (or are zeroed by the pack launch / a fill when the pool is not armed).
-        # (Measured and not kept in round 2: all 19 packs on the side stream while the stem runs - same-box A/B 32.94 vs
-        # 32.72 ms, the fork/join and the contention with the stem cost more than the 10 us per convolution they take off.)
-        stats, pooled_stats = _zeros_or_empty(dev, (2 * Cout,), torch.float64) if training else (None, False)
-        w_ohwi, w_dg = packed_conv_weight(w, training and ctx.needs_input_grad[0], None if pooled_stats else stats)
-        conv = torch.empty(NIMG, Ho, Wo, Cout, device=dev, dtype=torch.float32)
-        mean = torch.empty(Cout, device=dev, dtype=torch.float32)
-        invstd = torch.empty(Cout, device=dev, dtype=torch.float32)
-        y = torch.empty_like(conv)
-        r = None if res is None else res.contiguous()
-        if training:
-            call("sbl_conv2d_fwd", _p(x), _p(w_ohwi), _p(conv), _p(stats), 1, NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                 _workspace().data_ptr(), WS_BYTES, _s())
-            # the BatchNorm "finalize" (mean / invstd / running statistics / num_batches_tracked) rides on the apply launch
-            call("sbl_bn_apply_fwd_stats", _p(conv), _p(r), _p(stats), NIMG * Ho * Wo, _p(running_mean), _p(running_var), momentum, eps,
-                 _p(gamma), _p(beta), _p(y), _p(mean), _p(invstd), _p(nbt), NIMG * Ho * Wo, Cout, int(relu), _s())
-        else:
-            call("sbl_conv2d_fwd", _p(x), _p(w_ohwi), _p(conv), None, 0, NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                 _workspace().data_ptr(), WS_BYTES, _s())
-            call("sbl_bn_eval_stats", _p(running_mean), _p(running_var), eps, _p(mean), _p(invstd), Cout, _s())
-            call("sbl_bn_apply_fwd", _p(conv), _p(r), _p(mean), _p(invstd), _p(gamma), _p(beta), _p(y), NIMG * Ho * Wo, Cout,
-                 int(relu), _s())
-        ctx.save_for_backward(x, w, conv, y if relu else None, mean, invstd, gamma, w_dg)
-        ctx.cfg = (relu, stride, pad, training, res is not None)
-        ctx.gb_bn = (_gbuf(gamma), _gbuf(beta))
-        ctx.box_out = ctx.box_in = None
-        # ctl (BasicBlock, video_frontend.py:28-41) = {"role": "conv1" | "ds" | "conv2", "link": dict shared by the block's
-        # three nodes, "prev": the dict the PREVIOUS block published on its output tensor, "pub": the dict this block
-        # publishes}.  It lets backward (a) fold the residual branch's gradient into conv1's input-gradient epilogue instead
-        # of an autograd add, and (b) reduce the previous block's bn2 (+ downsample BN) backward sums in that same epilogue.
-        ctx.ctl = ctl if training else None
-        if ctx.ctl is not None:
-            if ctl["role"] == "conv2":
-                # (only the address of the activation is kept: the dict hangs on y itself (`y._sbl_pub`), a tensor in it
-                # would be a reference cycle that only the cyclic GC frees - ~1 GB of trunk activations per step)
-                ctl["pub"].update(conv=conv, mean=mean, invstd=invstd, act=y.data_ptr())
-            elif ctl["role"] == "ds":
-                ctl["pub"].update(conv2=conv, mean2=mean, invstd2=invstd)
-        if training:      # (grad mode is off inside Function.forward; backward only runs if a tape exists)
-            if box_out is not None and relu and res is None:
-                box_out.update(conv=conv, mean=mean, invstd=invstd, act=y.data_ptr())
-                ctx.box_out = box_out
-            if box_in is not None and stride == 1 and box_in.get("act") == x.data_ptr():
-                ctx.box_in = box_in
+        need_dx = ctx.needs_input_grad[0]
+        conv1, out, mean1, invstd1, w_dg1 = conv_bn_fwd(x, c1, None, True, training, need_dx)
+        res, bn_ds, saved_ds = x, None, ()
+        if ds is not None:
+            conv_ds, res, mean_ds, invstd_ds, w_dg_ds = conv_bn_fwd(x, ds, None, False, training, need_dx)
+            bn_ds, saved_ds = (conv_ds, mean_ds, invstd_ds), (conv_ds, mean_ds, invstd_ds, w_dg_ds)
+        need_dout = pub is not None and (need_dx or any(ctx.needs_input_grad[7:10]))       # conv1's output gets a gradient
+        conv2, y, mean2, invstd2, w_dg2 = conv_bn_fwd(out, c2, res, True, training, need_dout)
+        ctx.save_for_backward(x, conv1, out, mean1, invstd1, w_dg1, conv2, y, mean2, invstd2, w_dg2, *params, *saved_ds)
+        ctx.training, ctx.strides, ctx.prev, ctx.pub = training, (c1.stride, ds.stride if ds is not None else None), prev, pub
+        if pub is not None:
+            pub.publish(y, (conv2, mean2, invstd2), bn_ds)
         return y
 
     @staticmethod
     @_bw
     def backward(ctx, dy):
-        x, w, conv, y, mean, invstd, gamma, w_dg = ctx.saved_tensors
-        relu, stride, pad, training, has_res = ctx.cfg
-        if not training:
+        if not ctx.training:
             raise _lib.SblHipError("ConvBN backward is implemented for training-mode BatchNorm only")
-        NIMG, H, W, Cin = x.shape
-        Cout, _, KH, KW = w.shape
-        dev = x.device
+        x, conv1, out, mean1, invstd1, w_dg1, conv2, y, mean2, invstd2, w_dg2, *params = ctx.saved_tensors
+        w1, gamma1, beta1, w2, gamma2, beta2, *ds = params
+        stride1, stride_ds = ctx.strides
+        need_dx = ctx.needs_input_grad[0]
+        bn1, bn2 = (conv1, mean1, invstd1), (conv2, mean2, invstd2)
         dy = dy.contiguous()
-        rows = conv.numel() // Cout
-        box = ctx.box_out
-        ctl = ctx.ctl
-        role = ctl["role"] if ctl is not None else None
-        pub = ctl["pub"] if role in ("conv2", "ds") else None
-        if box is not None and box.get("sums") is not None and box.get("dx_ptr") == dy.data_ptr():
-            sums = box.pop("sums")           # reduced in the epilogue of the consumer's input-gradient convolution
-            box.clear()
-        elif role == "conv2" and pub.get("sums") is not None and pub.get("dx_ptr") == dy.data_ptr():
-            # the NEXT block's conv1 input-gradient epilogue reduced them (dy is that convolution's output, residual included)
-            full = pub.pop("sums")
-            sums = full[:2 * Cout]
-            if full.numel() == 4 * Cout:
-                ctl["link"]["ds_sums"] = full[2 * Cout:]     # the downsample BatchNorm's pair: same g, its own xhat
-            pub.clear()                                       # consumed: drop the published tensors now
-        elif role == "ds" and ctl["link"].get("ds_sums") is not None:
-            sums = ctl["link"].pop("ds_sums")
-        else:
-            sums = torch.empty(2 * Cout, device=dev, dtype=torch.float64)
-            call("sbl_bn_bwd_reduce", _p(dy), _p(y), _p(conv), _p(mean), _p(invstd), _p(sums), rows, Cout, int(relu),
-                 _workspace().data_ptr(), WS_BYTES, _s())
-        dconv = torch.empty_like(conv)
-        dres = torch.empty_like(conv) if has_res else None
-        if ctx.gb_bn[0] is not None and ctx.gb_bn[1] is not None:      # persistent gradient buffers: += in the kernel
-            call("sbl_bn_bwd_apply", _p(dy), _p(y), _p(conv), _p(mean), _p(invstd), _p(gamma), _p(sums), _p(dconv), _p(dres),
-                 _p(ctx.gb_bn[0]), _p(ctx.gb_bn[1]), rows, Cout, int(relu), 1, _s())
-            dgamma = dbeta = None
-        else:
-            dgamma = torch.empty(Cout, device=dev, dtype=torch.float32)
-            dbeta = torch.empty(Cout, device=dev, dtype=torch.float32)
-            call("sbl_bn_bwd_apply", _p(dy), _p(y), _p(conv), _p(mean), _p(invstd), _p(gamma), _p(sums), _p(dconv), _p(dres),
-                 _p(dgamma), _p(dbeta), rows, Cout, int(relu), 0, _s())
-        dres_ret = dres
-        if role == "conv2" and ctl["link"].get("identity"):
-            ctl["link"]["dres"] = dres        # conv1's input-gradient epilogue adds it (conv1's backward runs after this one)
-            dres_ret = None
+        # conv2 - bn2 - (+ shortcut) - relu.  The next block's conv1 epilogue reduced bn2's and the shortcut BN's sums over
+        # dy (its dx, residual included); this one's dgrad epilogue reduces bn1's over dout.
+        sums2 = ctx.pub.take(dy) if ctx.pub is not None else None
+        sums_ds = None
+        if sums2 is None:
+            sums2 = bn_bwd_reduce(dy, y, bn2)
+        elif ds:
+            sums2, sums_ds = sums2[:sums2.numel() // 2], sums2[sums2.numel() // 2:]      # same g, each BN its own xhat
+        dconv2, dres, dgamma2, dbeta2 = bn_bwd_apply(dy, y, bn2, gamma2, beta2, sums2, True)
+        dout, sums1 = conv_dgrad(dconv2, w2, w_dg2, out, 1, bn=bn1)
+        dw2 = conv_wgrad(out, dconv2, w2, 1)
+        # the shortcut.  1x1 / stride-2: its input gradient lives on the even/even pixels; conv1's epilogue adds the
+        # compact form instead of a zero-filled full-size tensor + an add
+        grads_ds, addend = (), dres
+        if ds:
+            w_ds, gamma_ds, beta_ds, conv_ds, mean_ds, invstd_ds, w_dg_ds = ds
+            bn_ds = (conv_ds, mean_ds, invstd_ds)
+            if sums_ds is None:
+                sums_ds = bn_bwd_reduce(dres, None, bn_ds)
+            dconv_ds, _, dgamma_ds, dbeta_ds = bn_bwd_apply(dres, None, bn_ds, gamma_ds, beta_ds, sums_ds, False)
+            if need_dx:
+                NIMG, H, W, Cin = x.shape
+                addend = torch.empty(NIMG, (H + 1) // 2, (W + 1) // 2, Cin, device=x.device, dtype=torch.float32)
+                call("sbl_conv1x1s2_dgrad_compact", _p(dconv_ds), _p(_dgrad_weight(w_ds, w_dg_ds)), _p(addend), NIMG, H, W, Cin,
+                     w_ds.size(0), _workspace().data_ptr(), WS_BYTES, _s())
+            grads_ds = (conv_wgrad(x, dconv_ds, w_ds, stride_ds), dgamma_ds, dbeta_ds)
+        # conv1 - bn1 - relu; its epilogue adds the shortcut's gradient and reduces the previous block's sums
+        dconv1, _, dgamma1, dbeta1 = bn_bwd_apply(dout, out, bn1, gamma1, beta1, sums1, False)
         dx = None
-        if ctx.needs_input_grad[0] and role == "ds" and not ctl["link"].get("main_done"):
-            # 1x1 / stride-2: the gradient lives on the even/even pixels; hand the compact form to conv1's epilogue (this node
-            # was created after conv1, so the engine runs it first) instead of a zero-filled full-size tensor + autograd add
-            w_dg = _dgrad_weight(w, w_dg)
-            dxc = torch.empty(NIMG, (H + 1) // 2, (W + 1) // 2, Cin, device=dev, dtype=torch.float32)
-            call("sbl_conv1x1s2_dgrad_compact", _p(dconv), _p(w_dg), _p(dxc), NIMG, H, W, Cin, Cout, _workspace().data_ptr(), WS_BYTES, _s())
-            ctl["link"]["dx_ds"] = dxc
-        elif ctx.needs_input_grad[0]:
-            w_dg = _dgrad_weight(w, w_dg)
-            dx = torch.empty_like(x)
-            bi = ctx.box_in
-            if role == "conv1":
-                link = ctl["link"]
-                addend = link.pop("dres", None) if link.get("identity") else link.pop("dx_ds", None)
-                link["main_done"] = True
-                prev = ctl.get("prev")
-                fuse = prev is not None and addend is not None and prev.get("act") == x.data_ptr()
-                if fuse:
-                    two = prev.get("conv2") is not None
-                    nsums, pooled = _zeros_or_empty(dev, ((4 if two else 2) * Cin,), torch.float64)
-                    call("sbl_conv2d_dgrad_fused", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                         _workspace().data_ptr(), WS_BYTES, _p(addend), _p(x), _p(prev["conv"]), _p(prev["mean"]), _p(prev["invstd"]),
-                         _p(prev.get("conv2")), _p(prev.get("mean2")), _p(prev.get("invstd2")), _p(nsums), int(pooled), _s())
-                    prev["sums"], prev["dx_ptr"] = nsums, dx.data_ptr()
-                else:
-                    call("sbl_conv2d_dgrad_fused", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                         _workspace().data_ptr(), WS_BYTES, _p(addend), None, None, None, None, None, None, None, None, 0, _s())
-            elif bi is not None and bi.get("conv") is not None:
-                nsums, pooled = _zeros_or_empty(dev, (2 * Cin,), torch.float64)
-                call("sbl_conv2d_dgrad_bnstats", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                     _workspace().data_ptr(), WS_BYTES, _p(x), _p(bi["conv"]), _p(bi["mean"]), _p(bi["invstd"]), _p(nsums), int(pooled), _s())
-                bi["sums"], bi["dx_ptr"] = nsums, dx.data_ptr()
+        if need_dx:
+            prev = ctx.prev if ctx.prev is not None and ctx.prev.describes(x) else None
+            if prev is None:
+                dx, _ = conv_dgrad(dconv1, w1, w_dg1, x, stride1, addend)
             else:
-                call("sbl_conv2d_dgrad", _p(dconv), _p(w_dg), _p(dx), NIMG, H, W, Cin, Cout, KH, KW, stride, pad,
-                     _workspace().data_ptr(), WS_BYTES, _s())
-        gw = _gbuf(w)
-        if gw is not None:
-            # the weight gradient is off backward's dependency chain: with a persistent gradient buffer it is issued
-            # on the second stream, where its workgroups fill the CUs that the chain's kernels (tile-count
-            # quantisation: 522 workgroups on 256 CUs) leave idle; joined by an end-of-backward engine callback
-            cur = torch.cuda.current_stream()
-            side = side_stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                dw_ohwi, pooled = _zeros_or_empty(dev, (Cout, KH, KW, Cin), torch.float32)
-                call("sbl_conv2d_wgrad", _p(x), _p(dconv), _p(dw_ohwi), NIMG, H, W, Cin, Cout, KH, KW, stride, pad, int(pooled), _s())
-                call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(gw), Cout, Cin, KH, KW, 1, _s())
-            x.record_stream(side)
-            dconv.record_stream(side)
-            _arm_side_join()
-            return dx, None, dgamma, dbeta, None, None, dres_ret, None, None, None, None, None, None, None, None, None
-        dw_ohwi = torch.empty(Cout, KH, KW, Cin, device=dev, dtype=torch.float32)
-        call("sbl_conv2d_wgrad", _p(x), _p(dconv), _p(dw_ohwi), NIMG, H, W, Cin, Cout, KH, KW, stride, pad, 0, _s())
-        dw = torch.empty_like(w)
-        call("sbl_conv_wgrad_unpack", _p(dw_ohwi), _p(dw), Cout, Cin, KH, KW, 0, _s())
-        return dx, dw, dgamma, dbeta, None, None, dres_ret, None, None, None, None, None, None, None, None, None
+                dx, sums_prev = conv_dgrad(dconv1, w1, w_dg1, x, stride1, addend, prev.bn2, prev.bn_ds)
+                prev.deposit(sums_prev, dx)
+        dw1 = conv_wgrad(x, dconv1, w1, stride1)
+        return (dx, None, None, None, None, None, None, dw1, dgamma1, dbeta1, dw2, dgamma2, dbeta2, *grads_ds)
+
+
+def basic_block(x, c1, c2, ds, training):
+    """BasicBlock forward; c1, c2, ds: ConvBN (ds None: identity shortcut).  Hands the BlockHandoff on from x to y."""
+    pub = BlockHandoff() if training and torch.is_grad_enabled() else None
+    y = BlockFn.apply(x, getattr(x, "_sbl_handoff", None), pub, c1, c2, ds, training, *c1[:3], *c2[:3], *(ds[:3] if ds is not None else ()))
+    if pub is not None:
+        y._sbl_handoff = pub
+    return y
 
 
 class AvgPoolFn(torch.autograd.Function):

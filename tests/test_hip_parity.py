@@ -490,6 +490,72 @@ def test_basic_block_fwd_bwd(ops, cin, cout, stride, hw):
             assert maxdiff(v, sd["b." + k]) < 1e-5, k
 
 
+def test_basic_block_chain_fwd_bwd(ops):
+    """Three chained blocks - (64 -> 64, s1), (64 -> 128, s2 with downsample), (128 -> 128, s1) - against the chained
+    oracle, so that backward takes the cross-block path: every BatchNorm's backward sums but the last bn2's come from an
+    input-gradient epilogue.  Then the same chain with the hand-off severed (each block's output cloned before the next
+    block), which takes the sbl_bn_bwd_reduce fallback for every bn2 and the downsample BN: two fresh forward passes,
+    compared under the float-reorder bound of test_backward_cut_at_frontend_features_equals_single_backward.
+    Tolerances are test_basic_block_fwd_bwd's (5e-5 / 5e-4 / 1e-3 / 1e-5) and that test's 3e-2: the implementation with
+    three tape nodes per block, which this test was first run on, measured 9.5e-6 / 9.5e-7 / 1.9e-6 / 1.2e-7 and, for
+    the severed chain, 5.1e-7 (worst of both arithmetics)."""
+    from oracle import sbl_oracle as O
+    from sbl_for_multilingual_lip_reading_amd.transformer.video_frontend import BasicBlock
+    import torch.nn as nn
+    ds = nn.Sequential(nn.Conv2d(64, 128, 1, 2, bias=False), nn.BatchNorm2d(128))
+    net = nn.Sequential(BasicBlock(64, 64), BasicBlock(64, 128, 2, ds), BasicBlock(128, 128))
+    sd = {"c." + k: torch.from_numpy(detfill.fill_value("chain." + k, tuple(v.shape)).copy()) for k, v in net.state_dict().items()}
+    net.load_state_dict({k[2:]: v for k, v in sd.items()})
+    for k in list(sd):
+        if sd[k].is_floating_point() and "running" not in k:
+            sd[k] = sd[k].clone().requires_grad_(True)
+    x = U("chain.x", (6, 64, 10, 10)).requires_grad_(True)
+    ref = x
+    for i, stride in enumerate((1, 2, 1)):
+        ref = O.basic_block(sd, "c.%d" % i, ref, stride, True)
+    dy = U("chain.dy", tuple(ref.shape))
+    ref.backward(dy)
+    net.to(DEV).train()
+    dyd = _nhwc(dy).to(DEV)
+
+    def backward_counting(out):
+        names, inner = [], ops.call
+        ops.call = lambda name, *a: (names.append(name), inner(name, *a))[1]
+        try:
+            out.backward(dyd)
+        finally:
+            ops.call = inner
+        return names
+
+    xd = _nhwc(x.detach()).to(DEV).requires_grad_(True)
+    out = net(xd)
+    e_out = maxdiff(out, _nhwc(ref.detach()))
+    e_stats = max(maxdiff(v, sd["c." + k]) for k, v in net.state_dict().items() if "running" in k or "num_batches" in k)
+    names = backward_counting(out)
+    e_dx = relerr(xd.grad, _nhwc(x.grad))
+    e_p = {k: relerr(p.grad, sd["c." + k].grad) for k, p in net.named_parameters()}
+    print("chain: out %.2e  dx %.2e  params %.2e  running %.2e" % (e_out, e_dx, max(e_p.values()), e_stats))
+    assert e_out < 5e-5 and e_dx < 5e-4 and e_stats < 1e-5
+    assert all(v < 1e-3 for v in e_p.values()), e_p
+    # the last block's bn2 is the only BatchNorm with a reduction pass of its own; the shortcut's gradient goes compact
+    assert names.count("sbl_bn_bwd_reduce") == 1 and names.count("sbl_conv1x1s2_dgrad_compact") == 1
+    assert names.count("sbl_conv2d_dgrad") == 0
+
+    first = {k: p.grad.clone() for k, p in net.named_parameters()}
+    first["x"] = xd.grad.clone()
+    net.zero_grad()
+    xd.grad = None
+    h = xd
+    for blk in net:
+        h = blk(h).clone()
+    names = backward_counting(h)
+    assert names.count("sbl_bn_bwd_reduce") == 4 and names.count("sbl_conv2d_dgrad") == 0
+    second = dict({k: p.grad for k, p in net.named_parameters()}, x=xd.grad)
+    rel = {k: float((second[k] - g).double().norm() / g.double().norm()) for k, g in first.items()}
+    print("chain severed: worst %.2e (%s)" % (max(rel.values()), max(rel, key=rel.get)))
+    assert all(v < 3e-2 for v in rel.values()), rel
+
+
 # --------------------------------------------------------------------------- LayerNorm / attention / fusion / loss / misc
 def test_add_layernorm(ops):
     x, r = U("ln.x", (37, 512), 2.0).requires_grad_(True), U("ln.r", (37, 512)).requires_grad_(True)
