@@ -179,7 +179,8 @@ int sbl_bn_apply_fwd_stats(const float* x, const float* res, const double* stats
                            sbl_stream_t stream);
 /* sums = double[2C] (sum g, sum g*xhat), g = dy * (y>0 if relu); overwritten by the call.
  * ws: NULL or the calling stream's sbl_gemm_f32 workspace (>= 16 KiB of int counters that are zero between launches,
- * then fp32 scratch): block partials + a last-arriver reduction replace 2C contended double atomics per block. */
+ * then fp32 scratch): block partials + a last-arriver reduction replace 2C contended double atomics per block.
+ * C/4 must divide 256 and C <= 512 (the last-arriver reduction has 256 lanes for the 2C/4 partial columns). */
 int sbl_bn_bwd_reduce(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
                       double* sums, long rows, int C, int relu, void* ws, long ws_bytes, sbl_stream_t stream);
 /* dx = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)); dres = g (if non-null); dgamma, dbeta from sums

@@ -281,6 +281,8 @@ extern "C" int sbl_bn_apply_fwd_stats(const float* x, const float* res, const do
                                       int C, int relu, sbl_stream_t stream) {
     SBL_REQUIRE(x && stats && gamma && beta && y && save_mean && save_invstd && rows > 0 && count > 0 && C >= 4 && C % 4 == 0,
                 "sbl_bn_apply_fwd_stats: bad args rows=%ld C=%d", rows, C);
+    // C = 1024 stays legal here, unlike sbl_bn_bwd_reduce: the kernel only needs the grid stride (a multiple of 256) to be a
+    // multiple of C/4, it has no per-block combine, and the first C/4 <= 256 threads of block 0 cover every channel quad
     SBL_REQUIRE((C / 4) <= 256 && 256 % (C / 4) == 0, "sbl_bn_apply_fwd_stats: C=%d unsupported (C/4 must divide 256)", C);
     SBL_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "sbl_bn_apply_fwd_stats: running stats must both be set or both null");
     SBL_REQUIRE(sbl_aligned16(x) && sbl_aligned16(y) && (!res || sbl_aligned16(res)), "sbl_bn_apply_fwd_stats: unaligned");
@@ -297,6 +299,9 @@ extern "C" int sbl_bn_bwd_reduce(const float* dy, const float* y, const float* x
     hipStream_t s = (hipStream_t)stream;
     SBL_REQUIRE(dy && x && mean && invstd && sums && rows > 0 && C >= 4 && C % 4 == 0 && (!relu || y), "sbl_bn_bwd_reduce: bad args");
     SBL_REQUIRE((C / 4) <= 256 && 256 % (C / 4) == 0, "sbl_bn_bwd_reduce: C=%d unsupported (C/4 must divide 256)", C);
+    // the last block's combine gives each of the 2C/4 float4 partial columns one of its 256 lanes (G = 256 / (C/2) block
+    // groups): at C = 1024 that is G = 0, a loop that never advances
+    SBL_REQUIRE(C / 2 <= 256, "sbl_bn_bwd_reduce: C=%d unsupported (the workspace combine covers C <= 512)", C);
     SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= 16384), "sbl_bn_bwd_reduce: workspace unaligned or < 16 KiB");
     // ws = the stream's GEMM workspace (int counters, all zero between launches, then fp32 slabs): block partials go
     // to the slabs and the last-arriving block reduces them; without a workspace every block ends with 2*C double

@@ -65,6 +65,24 @@ def test_invalid_arguments_are_rejected_on_the_host():
         _lib.call("sbl_add_layernorm_fwd", None, None, None, None, None, None, None, 4, 256, 1e-5, 0.0, None, 0, None)
 
 
+def test_bn_bwd_reduce_refuses_channel_counts_its_combine_cannot_cover():
+    """With a workspace the last block of sbl_bn_bwd_reduce combines the partials with G = 256 / (C/2) block groups; at
+    C = 1024 (which 'C/4 divides 256' admits) G is 0 and its loop never advances, so the host refuses C > 512 before any
+    launch.  The addresses are host dummies: nothing is dereferenced before the refusal.  C = 512 and C = 4 pass the
+    range check and are stopped by a later argument (a 1-byte workspace), so nothing is launched here either."""
+    import ctypes
+    from sbl_for_multilingual_lip_reading_amd import _lib
+    buf = ctypes.create_string_buffer(64)
+    a = (ctypes.addressof(buf) + 15) & ~15
+    with pytest.raises(_lib.SblHipError, match="C=1024"):
+        _lib.call("sbl_bn_bwd_reduce", a, a, a, a, a, a, 8, 1024, 1, a, 16 << 20, None)
+    with pytest.raises(_lib.SblHipError, match="C=1024"):
+        _lib.call("sbl_bn_bwd_reduce", a, a, a, a, a, a, 8, 1024, 0, None, 0, None)
+    for C in (512, 4):
+        with pytest.raises(_lib.SblHipError, match="workspace unaligned or < 16 KiB"):
+            _lib.call("sbl_bn_bwd_reduce", a, a, a, a, a, a, 8, C, 1, a, 1, None)
+
+
 def test_state_dict_surface_matches_reference():
     from oracle import sbl_oracle as O
     from sbl_for_multilingual_lip_reading_amd.transformer.decoder import Decoder
