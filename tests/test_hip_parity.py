@@ -93,7 +93,9 @@ def test_gemm_epilogues_and_strides(ops):
     x = Ad[:, :K]                                     # row stride K+8: strided operand view
     ref = A[:, :K].double() @ W.double().t() + b.double()
     C = torch.full((M, N + 4), 7.0, device=DEV)
+    last_kernel = ops._lib.load().sbl_profile_last_kernel
     ops.gemm(0, 1, M, N, K, x, K + 8, Wd, K, C, N + 4, bias=bd)          # ldc > N
+    assert last_kernel() == 1                         # M <= 512, K % 8 == 0, aligned rows: the register-only skinny kernel
     assert maxdiff(C[:, :N], ref) < 1e-5 and float(C[:, N:].min()) == 7.0
     C2 = torch.empty(M, N, device=DEV)
     ops.gemm(0, 1, M, N, K, x, K + 8, Wd, K, C2, N, bias=bd, relu=1)
@@ -103,17 +105,20 @@ def test_gemm_epilogues_and_strides(ops):
     ops.gemm(0, 1, M, N, K, x, K + 8, Wd, K, C3, N, mask=mask, ldm=N)
     assert maxdiff(C3, (A[:, :K].double() @ W.double().t()) * (mask.cpu() > 0)) < 1e-5
     C4 = C2.clone()
-    ops.gemm(0, 1, M, N, K, x, K + 8, Wd, K, C4, N, accumulate=1)        # small K: non-split accumulate
+    ops.gemm(0, 1, M, N, K, x, K + 8, Wd, K, C4, N, accumulate=1)        # += in the skinny kernel's epilogue
     assert maxdiff(C4, ref.clamp_min(0) + A[:, :K].double() @ W.double().t()) < 2e-5
-    # split-K path (plain epilogue, few tiles, K >= 256), overwrite and accumulate
+    assert last_kernel() == 1
+    # long K, one output tile, overwrite and accumulate: still a skinny shape (its 8 waves share K; no split-K over workgroups -
+    # the tile engine's epilogues and split-K reductions are tested leaf by leaf in test_gemm_routes_gpu.py)
     M, N, K = 64, 64, 4096
     A, W = U("sA", (M, K)), U("sW", (N, K))
     ref = A.double() @ W.double().t()
     C5 = torch.full((M, N), 3.0, device=DEV)
     ops.gemm(0, 1, M, N, K, A.to(DEV), K, W.to(DEV), K, C5, N)
     assert maxdiff(C5, ref) < 1e-4
+    assert last_kernel() == 1
     ops.gemm(0, 1, M, N, K, A.to(DEV), K, W.to(DEV), K, C5, N, accumulate=1)
-    assert maxdiff(C5, 2 * ref) < 2e-4
+    assert maxdiff(C5, 2 * ref) < 2e-4 and last_kernel() == 1
     cs = torch.empty(N, device=DEV)
     ops.call("sbl_colsum_f32", C5.data_ptr(), N, cs.data_ptr(), M, N, 0, ops._s())
     assert maxdiff(cs, (2 * ref).sum(0)) < 1e-3

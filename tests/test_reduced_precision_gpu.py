@@ -234,7 +234,8 @@ def test_wgrad_seg(rp, M, N, seg_rows):
     """sbl_wgrad_seg_f32 through ops._wgrad_seg: C += sum_s A_s^T B_s over segments of unequal row counts (rows that are
     not multiples of 16: the unaligned 64x64 loaders; 2048x512 with aligned rows would take the 128x128 tiles - see the
     grouped test for those), accumulating into a non-zero C, with the bias gradient's column sums.  No twin in
-    test_hip_parity.py (the merged weight gradients are only reached through whole steps there): the GEMM tolerance
+    test_hip_parity.py (the merged weight gradients are only reached through whole steps there; their f32 / bf16x6
+    instantiations are tested in test_gemm_routes_gpu.py): the GEMM tolerance
     4e-7 * sqrt(K) * 4 over K = all rows, split-K float atomics included; column sums as test_gemm_epilogues' colsum."""
     ops, mode = rp
     A = [U("ws.a%d%d%d" % (s, r, M), (r, M)) for s, r in enumerate(seg_rows)]
