@@ -677,14 +677,10 @@ static int at_rows_sz(const SegDesc& d, int nseg, int Lk_fixed) {
     for (int i = 0; i < nseg; ++i) m = d.L[i] > m ? d.L[i] : m;
     return ((m + 31) & ~31) * AT_LD;
 }
-static int at_attr(const void* fn, size_t lds, bool* flags) {
-    int dev = 0;
-    SBL_HIP(hipGetDevice(&dev));
-    if (!flags[dev & 63]) {   // > 64 KB of dynamic LDS: raise the cap once per device
-        SBL_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        flags[dev & 63] = true;
-    }
-    return 0;
+// The shared-keys form of the one-wavefront backward kernel takes up to 8 x 16 KB of dynamic LDS (two launch sites below).
+static hipError_t at_small_bwd_lds_cap() {
+    static bool set[64] = {false};
+    return sbl_raise_lds_cap((const void*)attention_small_bwd_kernel<true>, 8 * 16384, set);
 }
 
 // Segmented form: seg_L = host array of nseg prefix lengths (1..16 entries).  Lk_fixed == 0: self-attention inside
@@ -725,7 +721,7 @@ extern "C" int sbl_attention_seg_fwd(const float* q, long ldq, const float* k, l
     const int sz = at_rows_sz(d, nseg, Lk_fixed);
     const size_t lds = sizeof(float) * 4 * sz;
     static bool attr_set[64] = {false};
-    if (int e = at_attr((const void*)attention_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set)) return e;
+    SBL_HIP(sbl_raise_lds_cap((const void*)attention_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
     hipLaunchKernelGGL(attention_fwd_kernel, dim3(nseg * B * H), dim3(256), lds, (hipStream_t)stream, q, ldq, k, ldk, v, ldv, o,
                        ldo, p_out, mask_kind, mask, B, H, d, Lk_fixed, scale, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u,
                        1.f / (1.f - drop_p), seed, offset, sz, sbl_next_stamp_slot(SBL_KID_ATTENTION));
@@ -777,8 +773,7 @@ extern "C" int sbl_attention_seg_bwd(const float* dout, long lddo, const float* 
         const int nwv = nseg < 8 ? nseg : 8;      // 8 wavefronts = 2 per SIMD at this kernel's register use; beyond 8 segments each
                                                    // wavefront takes several (sbl_make_segs caps nseg at SBL_MAX_SEG = 16)
         if (Lk_fixed > 0 && nseg > 1) {      // shared keys: one workgroup per (batch, head) sums the segments' dK / dV in LDS
-            static bool attr_set2[64] = {false};
-            if (int e = at_attr((const void*)attention_small_bwd_kernel<true>, 8 * 16384, attr_set2)) return e;
+            SBL_HIP(at_small_bwd_lds_cap());
             hipLaunchKernelGGL(attention_small_bwd_kernel<true>, dim3(B * H), dim3(64 * nwv), (size_t)nwv * 16384, (hipStream_t)stream, dout, lddo, q,
                                ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, d, Lk_fixed, scale,
                                drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, nprob, (unsigned long long*)nullptr);
@@ -793,8 +788,7 @@ extern "C" int sbl_attention_seg_bwd(const float* dout, long lddo, const float* 
     if (at_qtile_ok(d, Lk_fixed, 0) && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0 && sbl_aligned16(dq) && sbl_aligned16(dk) && sbl_aligned16(dv)) {
         const int Lk = Lk_fixed > 0 ? Lk_fixed : d.L[0];
         const SegDesc t = at_qtile_desc(d.L[0], Lk);
-        static bool attr_set3[64] = {false};
-        if (int e = at_attr((const void*)attention_small_bwd_kernel<true>, 8 * 16384, attr_set3)) return e;
+        SBL_HIP(at_small_bwd_lds_cap());
         hipLaunchKernelGGL(attention_small_bwd_kernel<true>, dim3(B * H), dim3(128), (size_t)2 * 16384, (hipStream_t)stream, dout, lddo, q, ldq, k,
                            ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, t, Lk, scale,
                            drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, 2 * B * H, sbl_next_stamp_slot(SBL_KID_ATTENTION));
@@ -808,7 +802,7 @@ extern "C" int sbl_attention_seg_bwd(const float* dout, long lddo, const float* 
     const int sz = at_rows_sz(d, nseg, Lk_fixed);
     const size_t lds = sizeof(float) * 6 * sz;
     static bool attr_set[64] = {false};
-    if (int e = at_attr((const void*)attention_bwd_kernel, sizeof(float) * 6 * AT_SZ, attr_set)) return e;
+    SBL_HIP(sbl_raise_lds_cap((const void*)attention_bwd_kernel, sizeof(float) * 6 * AT_SZ, attr_set));
     hipLaunchKernelGGL(attention_bwd_kernel, dim3(nseg * B * H), dim3(256), lds, (hipStream_t)stream, dout, lddo, q, ldq, k, ldk,
                        v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, d, Lk_fixed, scale,
                        drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, sz, sbl_next_stamp_slot(SBL_KID_ATTENTION));

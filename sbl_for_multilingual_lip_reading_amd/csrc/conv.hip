@@ -32,100 +32,48 @@ static int check_conv(const char* who, int NIMG, int H, int W, int Cin, int Cout
 }
 static inline int out_dim(int H, int K, int stride, int pad) { return (H + 2 * pad - K) / stride + 1; }
 
-// Position-major path for 3x3 / stride-1 convolutions on small maps (ResNet layers 2-4: 11x11, 6x6, 3x3): SBL_CONV_PM_HW =
-// largest Ho*Wo that takes it (0 = off; A/B knob; the 22x22 maps of layer 1 lose: 6 % padding, 434 vs 396 us)
-constexpr int g_pm_hw = 121;
-// forward / input-gradient tile of that path: 1 = 128x128, 2 = 128x64, 3 = 64x64, 0 = the ordinary launches' rule.  The
-// tiles are uneven (4 / 6 / 9 taps) and co-resident, so small tiles balance best: layer 4 forward 400 -> 307 us
-// (128 TF of algorithmic FLOPs), input gradient 431 -> 324 us; layer 2 352 -> 327 us
-constexpr int g_pm_tile = 3;
-static inline bool conv_pm_ok(int Ho, int Wo, int KH, int stride) { return KH == 3 && stride == 1 && Ho * Wo <= g_pm_hw; }
+// Position-major path for 3x3 / stride-1 convolutions on small maps (sbl_pm_max_hw, tuning.h).  Its forward / input-gradient
+// tiles are always 64x64: the tiles are uneven (4 / 6 / 9 taps) and co-resident, so small tiles balance best (against the
+// ordinary launches' rule: layer 4 forward 400 -> 307 us, 128 TF of algorithmic FLOPs, input gradient 431 -> 324 us; layer 2
+// 352 -> 327 us).
+static inline bool conv_pm_ok(int Ho, int Wo, int KH, int stride) { return KH == 3 && stride == 1 && Ho * Wo <= sbl_pm_max_hw; }
 
-#define SBL_CONV_WS_COUNTERS 4096      // same workspace convention as sbl_gemm_f32: int counters, then fp32 slabs
-constexpr int g_tailsplit = 1;
-extern "C" int sbl_conv2d_fwd(const float* x, const float* w, float* y, double* stats, int stats_zeroed, int NIMG, int H, int W,
-                              int Cin, int Cout, int KH, int KW, int stride, int pad, void* ws, long ws_bytes, sbl_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (int e = check_conv("sbl_conv2d_fwd", NIMG, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
-    SBL_REQUIRE(x && w && y && sbl_aligned16(x) && sbl_aligned16(w), "sbl_conv2d_fwd: null/unaligned pointer");
-    const int Ho = out_dim(H, KH, stride, pad), Wo = out_dim(W, KW, stride, pad);
-    const int M = NIMG * Ho * Wo, N = Cout, K = KH * KW * Cin;
-    ConvGeom g{NIMG, Ho, Wo, H, W, Cin, KH, KW, stride, pad, 0, 0, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    sbl_geom_finish(g);
-    if (stats && !stats_zeroed) SBL_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 2 * Cout, s));
-    const long t128 = (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128);
-    SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * SBL_CONV_WS_COUNTERS), "sbl_conv2d_fwd: workspace unaligned or < 16 KiB");
-#define SBL_CONV_FWD(BM, BN, WN)                                                                               \
-    do {                                                                                                       \
-        ConvGatherKC<BM, false> al{x, g, M};                                                                   \
-        DenseKC<BN, true> bl{w, (long)K, N};                                                                   \
-        if (stats) {                                                                                           \
-            EpiStore<0, true> e{y, (long)N, nullptr, 0, stats, nullptr, 0};                                    \
-            if (!(g_tailsplit && sbl_launch_gemm_tailsplit<ConvGatherKC<BM, false>, DenseKC<BN, true>, EpiStore<0, true>, BM, BN, 1>(al, bl, e, M, N, K, s, SBL_KID_CONV_FWD, ws, ws_bytes, SBL_CONV_WS_COUNTERS))) { \
-                SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_FWD)};                 \
-                sbl_launch_gemm<ConvGatherKC<BM, false>, DenseKC<BN, true>, EpiStore<0, true>, BM, BN, 1, WN>(al, bl, e, M, N, K, 1, s, sc); \
-            }                                                                                                  \
-        } else {                                                                                               \
-            EpiStore<0, false> e{y, (long)N, nullptr, 0, nullptr, nullptr, 0};                                 \
-            if (!(g_tailsplit && sbl_launch_gemm_tailsplit<ConvGatherKC<BM, false>, DenseKC<BN, true>, EpiStore<0, false>, BM, BN, 1>(al, bl, e, M, N, K, s, SBL_KID_CONV_FWD, ws, ws_bytes, SBL_CONV_WS_COUNTERS))) { \
-                SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_FWD)};                 \
-                sbl_launch_gemm<ConvGatherKC<BM, false>, DenseKC<BN, true>, EpiStore<0, false>, BM, BN, 1, WN>(al, bl, e, M, N, K, 1, s, sc); \
-            }                                                                                                  \
-        }                                                                                                      \
-    } while (0)
-    if (KH == 3 && stride == 1) {
-        // every map sbl_conv_patch_tile accepts in the current mode (layers 1 and 2 in all split-bf16 modes, layers 3 and 4 too
-        // at two planes / one plane): the input patch of a tile staged once in LDS for all nine taps (conv_patch.h)
-        bool done;
-        const PatchEpi pe{y, stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (stats) done = sbl_launch_conv_patch<false, 1>(x, w, pe, NIMG, H, W, Cin, Cout, SBL_KID_CONV_FWD, s);
-        else done = sbl_launch_conv_patch<false, 0>(x, w, pe, NIMG, H, W, Cin, Cout, SBL_KID_CONV_FWD, s);
-        if (done) {
-            SBL_LAUNCH_CHECK("sbl_conv2d_fwd(patch)");
-            return 0;
-        }
-    }
-    if (conv_pm_ok(Ho, Wo, KH, stride)) {
-        // position-major rows: border pixels skip their out-of-bounds taps (mfma_gemm.h, ConvGatherPM)
-#define SBL_KPM_T_(P) sbl_conv_pm_kernel<ConvGatherPM<BM_, false>, DenseKCTapList<BN_>, EpiStore<0, true>, BM_, BN_, false, P>
-#define SBL_KPM_F_(P) sbl_conv_pm_kernel<ConvGatherPM<BM_, false>, DenseKCTapList<BN_>, EpiStore<0, false>, BM_, BN_, false, P>
-#define SBL_CONV_FWD_PM(BM, BN)                                                                                \
-    do {                                                                                                       \
-        constexpr int BM_ = BM, BN_ = BN;                                                                      \
-        ConvGatherPM<BM, false> al{x, g, M, 0ull};                                                             \
-        DenseKCTapList<BN> bl{w, (long)K, N, Cin, 0ull};                                                       \
-        SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_FWD)};                         \
-        dim3 grid(sbl_cdiv(N, BN), sbl_cdiv(M, BM), 1);                                                        \
-        if (stats) {                                                                                           \
-            EpiStore<0, true> e{y, (long)N, nullptr, 0, stats, nullptr, 0, 2, NIMG, Ho * Wo, 0, 0, 0, 0};      \
-            SBL_PREC_LAUNCH(SBL_KPM_T_, grid, s, al, bl, e, sc, M, N);                                        \
-        } else {                                                                                               \
-            EpiStore<0, false> e{y, (long)N, nullptr, 0, nullptr, nullptr, 0, 2, NIMG, Ho * Wo, 0, 0, 0, 0};   \
-            SBL_PREC_LAUNCH(SBL_KPM_F_, grid, s, al, bl, e, sc, M, N);                                        \
-        }                                                                                                      \
-    } while (0)
-        if (g_pm_tile == 1 || (!g_pm_tile && N >= 128 && t128 >= 512)) SBL_CONV_FWD_PM(128, 128);
-        else if (g_pm_tile == 2 || (!g_pm_tile && (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64) >= 512)) SBL_CONV_FWD_PM(128, 64);
-        else SBL_CONV_FWD_PM(64, 64);
-#undef SBL_CONV_FWD_PM
-#undef SBL_KPM_T_
-#undef SBL_KPM_F_
-        SBL_LAUNCH_CHECK("sbl_conv2d_fwd(pm)");
-        return 0;
-    }
-    // all tiles are co-resident (<= 4 workgroups per CU), so the launch lasts as long as the fullest CU: pick the
-    // largest tile whose count per CU (256 CUs) does not round up by more than ~20 % (522 128x128 tiles = 2.04/CU
-    // would run at 3/CU speed; 1044 128x64 tiles = 4.08/CU at 5/CU)
-    constexpr int q128 = 1;
-    const bool waste128 = q128 && N >= 128 && t128 >= 512 && t128 < 1024 && (double)(sbl_cdiv(t128, 256) * 256) / (double)t128 > 1.25;
-    // (a 256x64 tile with 4x1 wavefronts of 64x64 was measured slower than 128x64 on the 64-channel layer: 442 vs 405 us)
-    if (N >= 128 && t128 >= 512 && !waste128) SBL_CONV_FWD(128, 128, 2);
-    else if ((N < 128 || waste128) && (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64) >= 512) SBL_CONV_FWD(128, 64, 2);
-    else SBL_CONV_FWD(64, 64, 2);
-#undef SBL_CONV_FWD
-    SBL_LAUNCH_CHECK("sbl_conv2d_fwd");
-    return 0;
+constexpr int kConvWsCounters = 4096;      // same workspace convention as sbl_gemm_f32: int counters, then fp32 slabs
+
+// ------------------------------------------------------------------ the tile rule
+// Forward, input gradient and the parity-class launch choose among three tiles.  All tiles are co-resident (<= 4 workgroups
+// per CU), so the launch lasts as long as the fullest CU: pick the largest tile whose count per CU (256 CUs) does not round
+// up by more than ~20 % (522 128x128 tiles = 2.04/CU would run at 3/CU speed; 1044 128x64 tiles = 4.08/CU at 5/CU).
+// (A 256x64 tile with 4x1 wavefronts of 64x64 was measured slower than 128x64 on the 64-channel layer: 442 vs 405 us.)
+//   t128, t128x64  the launch's tile counts at 128x128 and 128x64 (the class launch sums them over its classes);
+//   waste_rule     forward and plain input gradient: 512-1023 128x128 tiles that round up by more than 25 % go to 128x64;
+//   no128          input gradients with the fused statistics epilogue: the 128x128 tile needs > 168 registers with it
+//                  (one wave per SIMD), 128x64 instead.
+enum ConvTile { kTile128x128, kTile128x64, kTile64x64 };
+static ConvTile conv_tile(int N, long t128, long t128x64, bool waste_rule, bool no128) {
+    const bool waste128 = waste_rule && N >= 128 && t128 >= 512 && t128 < 1024 && (double)(sbl_cdiv(t128, 256) * 256) / (double)t128 > 1.25;
+    const bool skip128 = waste128 || no128;
+    if (N >= 128 && t128 >= 512 && !skip128) return kTile128x128;
+    if ((N < 128 || skip128) && t128x64 >= 512) return kTile128x64;
+    return kTile64x64;
 }
+static inline int conv_tile_m(ConvTile t) { return t == kTile64x64 ? 64 : 128; }
+static inline int conv_tile_n(ConvTile t) { return t == kTile128x128 ? 128 : 64; }
+// fn(sbl_int<BM>{}, sbl_int<BN>{}) of the tile
+template <class F>
+static auto with_tile(ConvTile t, F&& fn) {
+    switch (t) {
+        case kTile128x128: return fn(sbl_int<128>{}, sbl_int<128>{});
+        case kTile128x64: return fn(sbl_int<128>{}, sbl_int<64>{});
+        default: return fn(sbl_int<64>{}, sbl_int<64>{});
+    }
+}
+
+// ------------------------------------------------------------------ epilogues
+// The output row map of EpiStore (mfma_gemm.h): cmap 0 = GEMM row m is output row m, 1 = parity class, 2 = position-major.
+struct RowMap { int cmap, ca, cb, cH, cW, cph, cpw; };
+static const RowMap kRowsDirect{0, 0, 0, 0, 0, 0, 0};
+static inline RowMap rows_pm(int NIMG, int HW) { return RowMap{2, NIMG, HW, 0, 0, 0, 0}; }
 
 // What may ride on an input-gradient convolution's epilogue (all optional):
 //   addend      the residual branch's gradient, added before the store: laid out like dx (identity shortcut), or - stride-2
@@ -147,6 +95,105 @@ struct DgradFuse {
     double* sums;
     int sums_zeroed;       // the caller hands over zeros (one pooled memset per step instead of one per convolution)
 };
+
+static EpiStore<0, false> epi_plain(float* C, int N, const RowMap& r) {
+    return {C, (long)N, nullptr, 0, nullptr, nullptr, 0, r.cmap, r.ca, r.cb, r.cH, r.cW, r.cph, r.cpw};
+}
+// + per-channel sum / sum of squares (training BatchNorm statistics of the forward)
+static EpiStore<0, true> epi_stats(float* C, int N, double* stats, const RowMap& r) {
+    return {C, (long)N, nullptr, 0, stats, nullptr, 0, r.cmap, r.ca, r.cb, r.cH, r.cW, r.cph, r.cpw};
+}
+// + addend (add_ld: EpiStore::add_ld) and, SUMS, the BatchNorm backward sums of f; without SUMS only the addend travels
+template <bool SUMS>
+static EpiStore<0, SUMS, true> epi_fused(float* C, int N, const DgradFuse& f, const float* add, long add_ld, const RowMap& r) {
+    const DgradFuse b = SUMS ? f : DgradFuse{};
+    return {C, (long)N, nullptr, 0, b.sums, nullptr, 0, r.cmap, r.ca, r.cb, r.cH, r.cW, r.cph, r.cpw,
+            b.y, b.x, b.mean, b.inv, b.x2, b.mean2, b.inv2, add, add_ld};
+}
+// forward: statistics or not; fn(epilogue)
+template <class F>
+static auto with_fwd_epi(float* y, int N, double* stats, const RowMap& r, F&& fn) {
+    if (stats) return fn(epi_stats(y, N, stats, r));
+    return fn(epi_plain(y, N, r));
+}
+// input gradient: sums (+ addend), addend only, or plain.  One launch may need several epilogues of the chosen flavour (one per
+// parity class, each with its row map and addend), so fn gets their maker: make(row map, addend, add_ld) -> epilogue.
+template <class F>
+static auto with_dgrad_epi(float* dx, int N, const DgradFuse& f, F&& fn) {
+    if (f.sums) return fn([&](const RowMap& r, const float* add, long add_ld) { return epi_fused<true>(dx, N, f, add, add_ld, r); });
+    if (f.addend) return fn([&](const RowMap& r, const float* add, long add_ld) { return epi_fused<false>(dx, N, f, add, add_ld, r); });
+    return fn([&](const RowMap& r, const float*, long) { return epi_plain(dx, N, r); });
+}
+
+// ------------------------------------------------------------------ launches shared by forward and input gradient
+// The tail split (mfma_gemm.h: two launches, two stamp slots) where it applies, else one plain launch.
+template <class AL, class BL, class EPI, int BM, int BN>
+static void launch_tailsplit_or_plain(const AL& al, const BL& bl, const EPI& e, int M, int N, int K, int kid, void* ws, long ws_bytes,
+                                      hipStream_t s) {
+    if (sbl_launch_gemm_tailsplit<AL, BL, EPI, BM, BN, 1>(al, bl, e, M, N, K, s, kid, ws, ws_bytes, kConvWsCounters)) return;
+    SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(kid)};
+    sbl_launch_gemm<AL, BL, EPI, BM, BN, 1, 2>(al, bl, e, M, N, K, 1, s, sc);
+}
+// Per-tap gather implicit GEMM: forward (src = x, wk = w) or stride-1 input gradient (DGRAD: src = dy, wk = wt).
+template <bool DGRAD, class EPI>
+static void launch_conv_gemm(const float* src, const float* wk, const ConvGeom& g, const EPI& e, ConvTile tile, int M, int N, int K, int kid,
+                             void* ws, long ws_bytes, hipStream_t s) {
+    with_tile(tile, [&](auto bm, auto bn) {
+        constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+        ConvGatherKC<BM, DGRAD> al{src, g, M};
+        DenseKC<BN, true> bl{wk, (long)K, N};
+        launch_tailsplit_or_plain<ConvGatherKC<BM, DGRAD>, DenseKC<BN, true>, EPI, BM, BN>(al, bl, e, M, N, K, kid, ws, ws_bytes, s);
+    });
+}
+// Position-major rows: border pixels skip their out-of-bounds taps (mfma_gemm.h, ConvGatherPM).  C = channels of src.
+template <bool DGRAD, class EPI>
+static void launch_conv_pm(const float* src, const float* wk, const ConvGeom& g, const EPI& e, int M, int N, int K, int C, int kid, hipStream_t s) {
+    ConvGatherPM<64, DGRAD> al{src, g, M, 0ull};
+    DenseKCTapList<64> bl{wk, (long)K, N, C, 0ull};
+    SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(kid)};
+    const dim3 grid(sbl_cdiv(N, 64), sbl_cdiv(M, 64), 1);
+    sbl_with_prec([&](auto p) {
+        hipLaunchKernelGGL((sbl_conv_pm_kernel<ConvGatherPM<64, DGRAD>, DenseKCTapList<64>, EPI, 64, 64, DGRAD, decltype(p)::value>), grid, dim3(256), 0, s,
+                           al, bl, e, sc, M, N);
+    });
+}
+
+extern "C" int sbl_conv2d_fwd(const float* x, const float* w, float* y, double* stats, int stats_zeroed, int NIMG, int H, int W,
+                              int Cin, int Cout, int KH, int KW, int stride, int pad, void* ws, long ws_bytes, sbl_stream_t stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (int e = check_conv("sbl_conv2d_fwd", NIMG, H, W, Cin, Cout, KH, KW, stride, pad)) return e;
+    SBL_REQUIRE(x && w && y && sbl_aligned16(x) && sbl_aligned16(w), "sbl_conv2d_fwd: null/unaligned pointer");
+    const int Ho = out_dim(H, KH, stride, pad), Wo = out_dim(W, KW, stride, pad);
+    const int M = NIMG * Ho * Wo, N = Cout, K = KH * KW * Cin;
+    ConvGeom g{NIMG, Ho, Wo, H, W, Cin, KH, KW, stride, pad, 0, 0, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    sbl_geom_finish(g);
+    if (stats && !stats_zeroed) SBL_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 2 * Cout, s));
+    SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * kConvWsCounters), "sbl_conv2d_fwd: workspace unaligned or < 16 KiB");
+    if (KH == 3 && stride == 1) {
+        // every map sbl_conv_patch_tile accepts in the current mode (layers 1 and 2 in all split-bf16 modes, layers 3 and 4 too
+        // at two planes / one plane): the input patch of a tile staged once in LDS for all nine taps (conv_patch.h)
+        bool done;
+        const PatchEpi pe{y, stats, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (stats) done = sbl_launch_conv_patch<false, 1>(x, w, pe, NIMG, H, W, Cin, Cout, SBL_KID_CONV_FWD, s);
+        else done = sbl_launch_conv_patch<false, 0>(x, w, pe, NIMG, H, W, Cin, Cout, SBL_KID_CONV_FWD, s);
+        if (done) {
+            SBL_LAUNCH_CHECK("sbl_conv2d_fwd(patch)");
+            return 0;
+        }
+    }
+    if (conv_pm_ok(Ho, Wo, KH, stride)) {
+        with_fwd_epi(y, N, stats, rows_pm(NIMG, Ho * Wo), [&](const auto& e) { launch_conv_pm<false>(x, w, g, e, M, N, K, Cin, SBL_KID_CONV_FWD, s); });
+        SBL_LAUNCH_CHECK("sbl_conv2d_fwd(pm)");
+        return 0;
+    }
+    const ConvTile tile = conv_tile(N, (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128), (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64), true, false);
+    with_fwd_epi(y, N, stats, kRowsDirect, [&](const auto& e) { launch_conv_gemm<false>(x, w, g, e, tile, M, N, K, SBL_KID_CONV_FWD, ws, ws_bytes, s); });
+    SBL_LAUNCH_CHECK("sbl_conv2d_fwd");
+    return 0;
+}
+
+// One parity class of a stride-2 input gradient: its geometry, the linear indices of its taps, GEMM rows and depth.
+struct DgradClass { ConvGeom g; int lin[4]; int M, K, ph, pw; };
 static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NIMG, int H, int W, int Cin, int Cout,
                              int KH, int KW, int stride, int pad, void* ws, long ws_bytes, sbl_stream_t stream,
                              const DgradFuse& f, int compact_out) {
@@ -168,12 +215,11 @@ static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NI
         const int N = Cin;
         if (KH == 1 && !compact_out) SBL_HIP(hipMemsetAsync(dx, 0, sizeof(float) * (size_t)NIMG * H * W * Cin, s));
         // the classes, heaviest (most taps) first
-        struct Cls { ConvGeom g; int lin[4]; int M, K, ph, pw; };
-        Cls cls[4];
+        DgradClass cls[4];
         int nc = 0;
         for (int ph = 0; ph < 2; ++ph)
             for (int pw = 0; pw < 2; ++pw) {
-                Cls c{ConvGeom{NIMG, (H - ph + 1) / 2, (W - pw + 1) / 2, Ho, Wo, Cout, KH, KW, stride, pad, 1, ph, pw, 0, {0, 0, 0, 0}, {0, 0, 0, 0}}, {0, 0, 0, 0}, 0, 0, ph, pw};
+                DgradClass c{ConvGeom{NIMG, (H - ph + 1) / 2, (W - pw + 1) / 2, Ho, Wo, Cout, KH, KW, stride, pad, 1, ph, pw, 0, {0, 0, 0, 0}, {0, 0, 0, 0}}, {0, 0, 0, 0}, 0, 0, ph, pw};
                 sbl_geom_finish(c.g);
                 for (int kh = 0; kh < KH; ++kh)
                     for (int kw = 0; kw < KW; ++kw)
@@ -196,57 +242,45 @@ static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NI
             t128 += (long)sbl_cdiv(cls[i].M, 128) * sbl_cdiv(N, 128);
             t128x64 += (long)sbl_cdiv(cls[i].M, 128) * sbl_cdiv(N, 64);
         }
-#define SBL_CONV_DGC_GO(BM, BN, EPI_T, MAKE_EPI)                                                              \
-    do {                                                                                                      \
-        ClassSet<ConvGatherKC<BM, true>, DenseKCTaps<BN>, EPI_T> cs;                                          \
-        cs.nclass = nc;                                                                                       \
-        cs.tiles_n = sbl_cdiv(N, BN);                                                                         \
-        long tt = 0;                                                                                          \
-        for (int i = 0; i < SBL_MAX_CLASSES; ++i) {                                                           \
-            const Cls& c = cls[i < nc ? i : 0];                                                               \
-            const float* add = (f.addend && c.ph == 0 && c.pw == 0) ? f.addend : nullptr;                     \
-            cs.al[i] = ConvGatherKC<BM, true>{dy, c.g, c.M};                                                  \
-            cs.bl[i] = DenseKCTaps<BN>{wt, (long)KH * KW * Cout, N, Cout, {c.lin[0], c.lin[1], c.lin[2], c.lin[3]}}; \
-            cs.epi[i] = MAKE_EPI;                                                                             \
-            cs.M[i] = c.M; cs.K[i] = c.K; cs.t0[i] = (int)tt;                                                 \
-            if (i < nc) tt += (long)sbl_cdiv(c.M, BM) * cs.tiles_n;                                           \
-        }                                                                                                     \
-        cs.t0[SBL_MAX_CLASSES] = (int)tt;                                                                     \
-        SBL_REQUIRE(tt < (1L << 30), "sbl_conv2d_dgrad: too many tiles");                                     \
-        SBL_PREC_LAUNCH(SBL_KCL_, dim3((unsigned)tt), s, cs, sc, N);                                          \
-    } while (0)
-#define SBL_CONV_DGC(BM, BN)                                                                                  \
-    do {                                                                                                      \
-        constexpr int BM_ = BM, BN_ = BN;                                                                     \
-        if (f.sums) {                                                                                         \
-            using E_ = EpiStore<0, true, true>;                                                               \
-            SBL_CONV_DGC_GO(BM, BN, E_, (E_{dx, (long)N, nullptr, 0, f.sums, nullptr, 0, cmap, c.g.OH, c.g.OW, H, W, c.ph, c.pw, \
-                                            f.y, f.x, f.mean, f.inv, f.x2, f.mean2, f.inv2, add, (long)N}));   \
-        } else if (fused) {                                                                                   \
-            using E_ = EpiStore<0, false, true>;                                                              \
-            SBL_CONV_DGC_GO(BM, BN, E_, (E_{dx, (long)N, nullptr, 0, nullptr, nullptr, 0, cmap, c.g.OH, c.g.OW, H, W, c.ph, c.pw, \
-                                            nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, add, (long)N})); \
-        } else {                                                                                              \
-            using E_ = EpiStore<0, false>;                                                                    \
-            SBL_CONV_DGC_GO(BM, BN, E_, (E_{dx, (long)N, nullptr, 0, nullptr, nullptr, 0, cmap, c.g.OH, c.g.OW, H, W, c.ph, c.pw})); \
-        }                                                                                                     \
-    } while (0)
-#define SBL_KCL_(P) sbl_conv_classes_kernel<ConvGatherKC<BM_, true>, DenseKCTaps<BN_>, E_, BM_, BN_, P>
-        // (the 128x128 tile with the fused statistics epilogue needs > 168 registers: one wave per SIMD; 128x64 instead)
-        if (N >= 128 && t128 >= 512 && !f.sums) SBL_CONV_DGC(128, 128);
-        else if ((N < 128 || f.sums) && t128x64 >= 512) SBL_CONV_DGC(128, 64);
-        else SBL_CONV_DGC(64, 64);
-#undef SBL_KCL_
-#undef SBL_CONV_DGC
-#undef SBL_CONV_DGC_GO
+        const ConvTile tile = conv_tile(N, t128, t128x64, false, f.sums != nullptr);
+        // the classes' tile ranges inside the one grid
+        int t0[SBL_MAX_CLASSES + 1];
+        long tt = 0;
+        for (int i = 0; i <= SBL_MAX_CLASSES; ++i) {
+            t0[i] = (int)tt;
+            if (i < nc) tt += (long)sbl_cdiv(cls[i].M, conv_tile_m(tile)) * sbl_cdiv(N, conv_tile_n(tile));
+        }
+        SBL_REQUIRE(tt < (1L << 30), "sbl_conv2d_dgrad: too many tiles");
+        with_dgrad_epi(dx, N, f, [&](auto make) {
+            with_tile(tile, [&](auto bm, auto bn) {
+                constexpr int BM = decltype(bm)::value, BN = decltype(bn)::value;
+                using AL = ConvGatherKC<BM, true>;
+                using BL = DenseKCTaps<BN>;
+                using EPI = decltype(make(kRowsDirect, f.addend, 0L));
+                ClassSet<AL, BL, EPI> cs;
+                cs.nclass = nc;
+                cs.tiles_n = sbl_cdiv(N, BN);
+                for (int i = 0; i < SBL_MAX_CLASSES; ++i) {
+                    const DgradClass& c = cls[i < nc ? i : 0];
+                    const float* add = (f.addend && c.ph == 0 && c.pw == 0) ? f.addend : nullptr;
+                    cs.al[i] = AL{dy, c.g, c.M};
+                    cs.bl[i] = BL{wt, (long)KH * KW * Cout, N, Cout, {c.lin[0], c.lin[1], c.lin[2], c.lin[3]}};
+                    cs.epi[i] = make(RowMap{cmap, c.g.OH, c.g.OW, H, W, c.ph, c.pw}, add, (long)N);
+                    cs.M[i] = c.M; cs.K[i] = c.K; cs.t0[i] = t0[i];
+                }
+                cs.t0[SBL_MAX_CLASSES] = t0[SBL_MAX_CLASSES];
+                sbl_with_prec([&](auto p) {
+                    hipLaunchKernelGGL((sbl_conv_classes_kernel<AL, BL, EPI, BM, BN, decltype(p)::value>), dim3((unsigned)tt), dim3(256), 0, s, cs, sc, N);
+                });
+            });
+        });
         SBL_LAUNCH_CHECK("sbl_conv2d_dgrad(classes)");
         return 0;
     }
     const int M = NIMG * H * W, N = Cin, K = KH * KW * Cout;
     ConvGeom g{NIMG, H, W, Ho, Wo, Cout, KH, KW, stride, pad, 0, 0, 0, 0, {0, 0, 0, 0}, {0, 0, 0, 0}};
     sbl_geom_finish(g);
-    const long t128 = (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128);
-    SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * SBL_CONV_WS_COUNTERS), "sbl_conv2d_dgrad: workspace unaligned or < 16 KiB");
+    SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * kConvWsCounters), "sbl_conv2d_dgrad: workspace unaligned or < 16 KiB");
     if (KH == 3 && stride == 1) {
         // the maps sbl_conv_patch_tile accepts (see sbl_conv2d_fwd): patch-resident kernel with mirrored taps (conv_patch.h)
         bool done;
@@ -260,71 +294,16 @@ static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NI
         }
     }
     if (conv_pm_ok(H, W, KH, stride)) {
-#define SBL_KPM_T_(P) sbl_conv_pm_kernel<ConvGatherPM<BM_, true>, DenseKCTapList<BN_>, EpiStore<0, true, true>, BM_, BN_, true, P>
-#define SBL_KPM_A_(P) sbl_conv_pm_kernel<ConvGatherPM<BM_, true>, DenseKCTapList<BN_>, EpiStore<0, false, true>, BM_, BN_, true, P>
-#define SBL_KPM_F_(P) sbl_conv_pm_kernel<ConvGatherPM<BM_, true>, DenseKCTapList<BN_>, EpiStore<0, false>, BM_, BN_, true, P>
-#define SBL_CONV_DG_PM(BM, BN)                                                                                 \
-    do {                                                                                                       \
-        constexpr int BM_ = BM, BN_ = BN;                                                                      \
-        ConvGatherPM<BM, true> al{dy, g, M, 0ull};                                                             \
-        DenseKCTapList<BN> bl{wt, (long)K, N, Cout, 0ull};                                                     \
-        SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_DGRAD)};                       \
-        dim3 grid(sbl_cdiv(N, BN), sbl_cdiv(M, BM), 1);                                                        \
-        if (f.sums) {                                                                                          \
-            EpiStore<0, true, true> e{dx, (long)N, nullptr, 0, f.sums, nullptr, 0, 2, NIMG, H * W, 0, 0, 0, 0, \
-                                      f.y, f.x, f.mean, f.inv, f.x2, f.mean2, f.inv2, f.addend, 0L};           \
-            SBL_PREC_LAUNCH(SBL_KPM_T_, grid, s, al, bl, e, sc, M, N);                                        \
-        } else if (f.addend) {                                                                                 \
-            EpiStore<0, false, true> e{dx, (long)N, nullptr, 0, nullptr, nullptr, 0, 2, NIMG, H * W, 0, 0, 0, 0, \
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, f.addend, 0L}; \
-            SBL_PREC_LAUNCH(SBL_KPM_A_, grid, s, al, bl, e, sc, M, N);                                        \
-        } else {                                                                                               \
-            EpiStore<0, false> e{dx, (long)N, nullptr, 0, nullptr, nullptr, 0, 2, NIMG, H * W, 0, 0, 0, 0};    \
-            SBL_PREC_LAUNCH(SBL_KPM_F_, grid, s, al, bl, e, sc, M, N);                                        \
-        }                                                                                                      \
-    } while (0)
-        if (g_pm_tile == 1 || (!g_pm_tile && N >= 128 && t128 >= 512)) SBL_CONV_DG_PM(128, 128);
-        else if (g_pm_tile == 2 || (!g_pm_tile && (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64) >= 512)) SBL_CONV_DG_PM(128, 64);
-        else SBL_CONV_DG_PM(64, 64);
-#undef SBL_CONV_DG_PM
-#undef SBL_KPM_T_
-#undef SBL_KPM_A_
-#undef SBL_KPM_F_
+        with_dgrad_epi(dx, N, f, [&](auto make) {
+            launch_conv_pm<true>(dy, wt, g, make(rows_pm(NIMG, H * W), f.addend, 0L), M, N, K, Cout, SBL_KID_CONV_DGRAD, s);
+        });
         SBL_LAUNCH_CHECK("sbl_conv2d_dgrad(pm)");
         return 0;
     }
-#define SBL_CONV_DG(BM, BN, WN)                                                                               \
-    do {                                                                                                      \
-        ConvGatherKC<BM, true> al{dy, g, M};                                                                  \
-        DenseKC<BN, true> bl{wt, (long)K, N};                                                                 \
-        if (f.sums) {                                                                                         \
-            EpiStore<0, true, true> e{dx, (long)N, nullptr, 0, f.sums, nullptr, 0, 0, 0, 0, 0, 0, 0, 0,       \
-                                      f.y, f.x, f.mean, f.inv, f.x2, f.mean2, f.inv2, f.addend, 0L};          \
-            if (!(g_tailsplit && sbl_launch_gemm_tailsplit<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, true, true>, BM, BN, 1>(al, bl, e, M, N, K, s, SBL_KID_CONV_DGRAD, ws, ws_bytes, SBL_CONV_WS_COUNTERS))) { \
-                SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_DGRAD)};              \
-                sbl_launch_gemm<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, true, true>, BM, BN, 1, WN>(al, bl, e, M, N, K, 1, s, sc); \
-            }                                                                                                 \
-        } else if (f.addend) {                                                                                \
-            EpiStore<0, false, true> e{dx, (long)N, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0,     \
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, f.addend, 0L}; \
-            if (!(g_tailsplit && sbl_launch_gemm_tailsplit<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, false, true>, BM, BN, 1>(al, bl, e, M, N, K, s, SBL_KID_CONV_DGRAD, ws, ws_bytes, SBL_CONV_WS_COUNTERS))) { \
-                SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_DGRAD)};              \
-                sbl_launch_gemm<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, false, true>, BM, BN, 1, WN>(al, bl, e, M, N, K, 1, s, sc); \
-            }                                                                                                 \
-        } else {                                                                                              \
-            EpiStore<0, false> e{dx, (long)N, nullptr, 0, nullptr, nullptr, 0};                               \
-            if (!(g_tailsplit && sbl_launch_gemm_tailsplit<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, false>, BM, BN, 1>(al, bl, e, M, N, K, s, SBL_KID_CONV_DGRAD, ws, ws_bytes, SBL_CONV_WS_COUNTERS))) { \
-                SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_DGRAD)};              \
-                sbl_launch_gemm<ConvGatherKC<BM, true>, DenseKC<BN, true>, EpiStore<0, false>, BM, BN, 1, WN>(al, bl, e, M, N, K, 1, s, sc); \
-            }                                                                                                 \
-        }                                                                                                     \
-    } while (0)
-    constexpr int q128 = 1;
-    const bool waste128 = q128 && N >= 128 && t128 >= 512 && t128 < 1024 && (double)(sbl_cdiv(t128, 256) * 256) / (double)t128 > 1.25;
-    if (N >= 128 && t128 >= 512 && !waste128 && !f.sums) SBL_CONV_DG(128, 128, 2);
-    else if ((N < 128 || waste128 || f.sums) && (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64) >= 512) SBL_CONV_DG(128, 64, 2);
-    else SBL_CONV_DG(64, 64, 2);
-#undef SBL_CONV_DG
+    const ConvTile tile = conv_tile(N, (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 128), (long)sbl_cdiv(M, 128) * sbl_cdiv(N, 64), true, f.sums != nullptr);
+    with_dgrad_epi(dx, N, f, [&](auto make) {
+        launch_conv_gemm<true>(dy, wt, g, make(kRowsDirect, f.addend, 0L), tile, M, N, K, SBL_KID_CONV_DGRAD, ws, ws_bytes, s);
+    });
     SBL_LAUNCH_CHECK("sbl_conv2d_dgrad");
     return 0;
 }
@@ -354,6 +333,12 @@ extern "C" int sbl_conv1x1s2_dgrad_compact(const float* dy, const float* wt, flo
     return conv2d_dgrad_impl(dy, wt, dx_compact, NIMG, H, W, Cin, Cout, 1, 1, 2, 0, ws, ws_bytes, stream, kNoFuse, 1);
 }
 
+// K splits of a weight-gradient launch: about `target` workgroups over `tiles` output tiles, chunks of at least 256 pixels
+static inline int wgrad_splits(long target, long tiles, int K) {
+    int splits = (int)((target + tiles - 1) / tiles);
+    if (splits > K / 256) splits = K / 256;
+    return splits < 1 ? 1 : splits;
+}
 extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int NIMG, int H, int W, int Cin, int Cout,
                                 int KH, int KW, int stride, int pad, int dw_zeroed, sbl_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
@@ -370,48 +355,38 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
     // layers 1-4); chunks stay >= 256 pixels
     const bool big = M >= 128 && N >= 1152 && !(stride == 2 && sbl_wg_s2_small);
     const int wg_target = stride == 2 ? sbl_wg_s2_target : (big ? 1536 : 3072);
+    // (the stamp slot is taken before the patch-resident route is tried: whichever route launches uses it)
     SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(SBL_KID_CONV_WGRAD)};
     if (KH == 3 && KW == 3 && stride == 1 && pad == 1 && sbl_launch_conv_patch_wgrad(x, dy, dw, NIMG, H, W, Cin, Cout, sc.stamp, s)) {
         SBL_LAUNCH_CHECK("sbl_conv2d_wgrad(patch)");
         return 0;
     }
-#define SBL_CONV_WG(BM, BN)                                                                                   \
-    do {                                                                                                      \
-        const long tiles = (long)sbl_cdiv(M, BM) * sbl_cdiv(N, BN);                                           \
-        int splits = (int)((wg_target + tiles - 1) / tiles);                                                  \
-        if (splits > K / 256) splits = K / 256;                                                               \
-        if (splits < 1) splits = 1;                                                                           \
-        DenseMC<BM, true> al{dy, (long)Cout, M};                                                              \
-        ConvGatherMC<BN> bl{x, g, N};                                                                         \
-        EpiStore<2, false> e{dw, (long)N, nullptr, 0, nullptr, nullptr, 0};                                   \
-        sbl_launch_gemm<DenseMC<BM, true>, ConvGatherMC<BN>, EpiStore<2, false>, BM, BN>(al, bl, e, M, N, K, splits, s, sc); \
-    } while (0)
+    const EpiStore<2, false> e{dw, (long)N, nullptr, 0, nullptr, nullptr, 0};
     if (conv_pm_ok(Ho, Wo, KH, stride) && big && M >= 128 && Cin % 128 == 0) {
         // one tap per tile of the (tap, ci) axis: contract only over the pixels that tap can reach
-#define SBL_KPMW_(P) sbl_conv_pm_wgrad_kernel<DenseMCPM<T_>, ConvGatherMCPM<T_>, EpiStore<2, false>, T_, T_, P>
-#define SBL_CONV_WG_PM(T)                                                                                     \
-    do {                                                                                                      \
-        constexpr int T_ = T;                                                                                 \
-        const long tiles = (long)sbl_cdiv(M, T) * sbl_cdiv(N, T);                                             \
-        const int target = (T == 128) ? wg_target : 2 * wg_target;                                            \
-        int splits = (int)((target + tiles - 1) / tiles);                                                     \
-        if (splits > K / 256) splits = K / 256;                                                               \
-        if (splits < 1) splits = 1;                                                                           \
-        DenseMCPM<T> al{dy, (long)Cout, M, NIMG, Ho, Wo, g.fdNIMG, PmRect{0, 0, 1, 0, 0, 1.f}};                              \
-        ConvGatherMCPM<T> bl{x, g, N, PmRect{0, 0, 1, 0, 0, 1.f}};                                              \
-        EpiStore<2, false> e{dw, (long)N, nullptr, 0, nullptr, nullptr, 0};                                   \
-        SBL_PREC_LAUNCH(SBL_KPMW_, dim3(sbl_cdiv(M, T), sbl_cdiv(N, T), splits), s, al, bl, e, sc, M, N);     \
-    } while (0)
-        if (M <= sbl_pm_wg64_max_m) SBL_CONV_WG_PM(64);
-        else SBL_CONV_WG_PM(128);
-#undef SBL_CONV_WG_PM
-#undef SBL_KPMW_
+        auto pm = [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            const int splits = wgrad_splits(T == 128 ? wg_target : 2 * wg_target, (long)sbl_cdiv(M, T) * sbl_cdiv(N, T), K);
+            DenseMCPM<T> al{dy, (long)Cout, M, NIMG, Ho, Wo, g.fdNIMG, PmRect{0, 0, 1, 0, 0, 1.f}};
+            ConvGatherMCPM<T> bl{x, g, N, PmRect{0, 0, 1, 0, 0, 1.f}};
+            sbl_with_prec([&](auto p) {
+                hipLaunchKernelGGL((sbl_conv_pm_wgrad_kernel<DenseMCPM<T>, ConvGatherMCPM<T>, EpiStore<2, false>, T, T, decltype(p)::value>),
+                                   dim3(sbl_cdiv(M, T), sbl_cdiv(N, T), splits), dim3(256), 0, s, al, bl, e, sc, M, N);
+            });
+        };
+        if (M <= sbl_pm_wg64_max_m) pm(sbl_int<64>{});
+        else pm(sbl_int<128>{});
         SBL_LAUNCH_CHECK("sbl_conv2d_wgrad(pm)");
         return 0;
     }
-    if (big && M >= 128) SBL_CONV_WG(128, 128);
-    else SBL_CONV_WG(64, 64);
-#undef SBL_CONV_WG
+    auto plain = [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        DenseMC<T, true> al{dy, (long)Cout, M};
+        ConvGatherMC<T> bl{x, g, N};
+        sbl_launch_gemm<DenseMC<T, true>, ConvGatherMC<T>, EpiStore<2, false>, T, T>(al, bl, e, M, N, K, wgrad_splits(wg_target, (long)sbl_cdiv(M, T) * sbl_cdiv(N, T), K), s, sc);
+    };
+    if (big && M >= 128) plain(sbl_int<128>{});
+    else plain(sbl_int<64>{});
     SBL_LAUNCH_CHECK("sbl_conv2d_wgrad");
     return 0;
 }

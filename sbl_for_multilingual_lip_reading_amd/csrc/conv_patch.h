@@ -282,6 +282,12 @@ static inline bool sbl_conv_patch_tile(int H, int W, int nplanes, int& TR, int& 
     return TR >= 4 && TR * W >= 160;
 }
 
+template <int NT, bool DGRAD, int STATS>
+static inline bool sbl_conv_patch_lds_cap() {
+    static bool set[64] = {false};
+    return sbl_raise_lds_cap((const void*)sbl_conv_patch_kernel<NT, DGRAD, STATS>, 160 * 1024, set) == hipSuccess;
+}
+// Returns false when nothing was launched (the caller goes on to the next route).
 template <bool DGRAD, int STATS>
 static inline bool sbl_launch_conv_patch(const float* src, const float* wk, const PatchEpi& epi, int NIMG, int H, int W, int C, int Nout,
                                          int kid, hipStream_t s) {
@@ -297,20 +303,13 @@ static inline bool sbl_launch_conv_patch(const float* src, const float* wk, cons
     const int gx = ntiles < capx ? ntiles : capx;
     const dim3 grid(gx, gy);
     unsigned long long* stamp = sbl_next_stamp_slot(kid);
-#define SBL_CP_GO(P)                                                                                                           \
-    do {                                                                                                                       \
-        static bool set_##P[64] = {false};                                                                                     \
-        int dev = 0;                                                                                                           \
-        if (hipGetDevice(&dev) != hipSuccess) return false;                                                                    \
-        if (!set_##P[dev & 63]) {                                                                                              \
-            if (hipFuncSetAttribute((const void*)sbl_conv_patch_kernel<P, DGRAD, STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false; \
-            set_##P[dev & 63] = true;                                                                                          \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((sbl_conv_patch_kernel<P, DGRAD, STATS>), grid, dim3(256), lds, s, src, wk, epi, NIMG, H, W, C, Nout, TR, tpi, ntiles, G, stamp); \
-    } while (0)
-    if (g_sbl_prec == 6) SBL_CP_GO(6);
-    else if (g_sbl_prec == 3) SBL_CP_GO(3);
-    else SBL_CP_GO(1);
-#undef SBL_CP_GO
-    return true;
+    return sbl_with_prec([&](auto p) {
+        constexpr int NT = decltype(p)::value;
+        if constexpr (NT == 0) return false;      // (excluded above: no fp32 instantiation of this kernel)
+        else {
+            if (!sbl_conv_patch_lds_cap<NT, DGRAD, STATS>()) return false;
+            hipLaunchKernelGGL((sbl_conv_patch_kernel<NT, DGRAD, STATS>), grid, dim3(256), lds, s, src, wk, epi, NIMG, H, W, C, Nout, TR, tpi, ntiles, G, stamp);
+            return true;
+        }
+    });
 }

@@ -223,6 +223,11 @@ static inline bool sbl_conv_patch_wgrad_geom(int NIMG, int H, int W, int Cin, in
     return true;
 }
 
+template <int NT>
+static inline bool sbl_conv_patch_wgrad_lds_cap() {
+    static bool set[64] = {false};
+    return sbl_raise_lds_cap((const void*)sbl_conv_patch_wgrad_kernel<NT>, 160 * 1024, set) == hipSuccess;
+}
 // dw must be zeroed (or hold the sum to add to).  Returns false when nothing was launched.
 static inline bool sbl_launch_conv_patch_wgrad(const float* x, const float* dy, float* dw, int NIMG, int H, int W, int Cin, int Cout,
                                                unsigned long long* stamp, hipStream_t s) {
@@ -236,20 +241,13 @@ static inline bool sbl_launch_conv_patch_wgrad(const float* x, const float* dy, 
     if (gx < 1) gx = 1;
     if (gx > gm.ntiles) gx = gm.ntiles;
     const size_t lds = (size_t)npl * (gm.xrows + gm.dyrows) * 128 + (size_t)gm.dyrows * 4;      // images + pixel -> patch row table
-#define SBL_PWG_GO(P)                                                                                                          \
-    do {                                                                                                                       \
-        static bool set_##P[64] = {false};                                                                                     \
-        int dev = 0;                                                                                                           \
-        if (hipGetDevice(&dev) != hipSuccess) return false;                                                                    \
-        if (!set_##P[dev & 63]) {                                                                                              \
-            if (hipFuncSetAttribute((const void*)sbl_conv_patch_wgrad_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return false; \
-            set_##P[dev & 63] = true;                                                                                          \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((sbl_conv_patch_wgrad_kernel<P>), dim3(gx, combos), dim3(SBL_PWG_THREADS), lds, s, x, dy, dw, gm, stamp); \
-    } while (0)
-    if (g_sbl_prec == 6) SBL_PWG_GO(6);
-    else if (g_sbl_prec == 3) SBL_PWG_GO(3);
-    else SBL_PWG_GO(1);
-#undef SBL_PWG_GO
-    return true;
+    return sbl_with_prec([&](auto p) {
+        constexpr int NT = decltype(p)::value;
+        if constexpr (NT == 0) return false;      // (excluded above: no fp32 instantiation of this kernel)
+        else {
+            if (!sbl_conv_patch_wgrad_lds_cap<NT>()) return false;
+            hipLaunchKernelGGL((sbl_conv_patch_wgrad_kernel<NT>), dim3(gx, combos), dim3(SBL_PWG_THREADS), lds, s, x, dy, dw, gm, stamp);
+            return true;
+        }
+    });
 }

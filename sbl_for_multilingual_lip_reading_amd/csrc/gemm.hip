@@ -166,20 +166,22 @@ extern "C" int sbl_gemm_f32(int transA, int transB, int M, int N, int K, const f
         }
     }
     sc.stamp = sbl_next_stamp_slot(big ? SBL_KID_TILED128 : SBL_KID_TILED64);
-#define SBL_GO(VEC, BM, BN, KU) \
-    launch_trans<VEC, BM, BN, KU>(transA, transB, A, lda, B, ldb, C, ldc, bias, relu, relu_mask, ldm, mode, M, N, K, splits, sc, s)
+    auto go = [&](auto vec_c, auto tile_c, auto ku_c) {
+        constexpr int T = decltype(tile_c)::value;
+        launch_trans<decltype(vec_c)::value, T, T, decltype(ku_c)::value>(transA, transB, A, lda, B, ldb, C, ldc, bias, relu, relu_mask, ldm, mode, M, N, K,
+                                                                          splits, sc, s);
+    };
     if (big) {
-        if (vec) SBL_GO(true, 128, 128, 1);
-        else SBL_GO(false, 128, 128, 1);
+        if (vec) go(std::true_type{}, sbl_int<128>{}, sbl_int<1>{});
+        else go(std::false_type{}, sbl_int<128>{}, sbl_int<1>{});
     } else {
         // KU = 4 (69 KB of LDS, 2 workgroups per CU) while every workgroup of the launch is resident at once; beyond
         // 512 workgroups KU = 2 (35 KB, 4 per CU) keeps them all resident instead of running a second, part-filled
         // round (measured 1440x2048x512: 36.6 vs 46.9 us)
-        if (!vec) SBL_GO(false, 64, 64, 1);
-        else if (tiles64 * splits > 512) SBL_GO(true, 64, 64, 2);
-        else SBL_GO(true, 64, 64, 4);
+        if (!vec) go(std::false_type{}, sbl_int<64>{}, sbl_int<1>{});
+        else if (tiles64 * splits > 512) go(std::true_type{}, sbl_int<64>{}, sbl_int<2>{});
+        else go(std::true_type{}, sbl_int<64>{}, sbl_int<4>{});
     }
-#undef SBL_GO
     SBL_LAUNCH_CHECK("sbl_gemm_f32");
     return 0;
 }
@@ -418,14 +420,15 @@ extern "C" int sbl_wgrad_group_f32(int nprob, int nseg, const int* seg_rows, con
         hipLaunchKernelGGL(group_write_kernel, dim3(1), dim3(64), 0, s, w, tab, first, count);
     }
     SBL_REQUIRE(tiles < (1L << 30), "sbl_wgrad_group_f32: too many tiles");
-#define SBL_KG1_(P) sbl_wgrad_group_kernel<true, P>
-#define SBL_KG0_(P) sbl_wgrad_group_kernel<false, P>
-    if (nseg == 1)
-        SBL_PREC_LAUNCH(SBL_KG1_, dim3((unsigned)tiles), s, (const GroupProb*)tab, gc, sbl_next_stamp_slot(SBL_KID_SEG_WGRAD));
-    else
-        SBL_PREC_LAUNCH(SBL_KG0_, dim3((unsigned)tiles), s, (const GroupProb*)tab, gc, sbl_next_stamp_slot(SBL_KID_SEG_WGRAD));
-#undef SBL_KG1_
-#undef SBL_KG0_
+    unsigned long long* stamp = sbl_next_stamp_slot(SBL_KID_SEG_WGRAD);
+    sbl_with_prec([&](auto p) {
+        constexpr int P = decltype(p)::value;
+        if (nseg == 1) {
+            hipLaunchKernelGGL((sbl_wgrad_group_kernel<true, P>), dim3((unsigned)tiles), dim3(256), 0, s, (const GroupProb*)tab, gc, stamp);
+        } else {
+            hipLaunchKernelGGL((sbl_wgrad_group_kernel<false, P>), dim3((unsigned)tiles), dim3(256), 0, s, (const GroupProb*)tab, gc, stamp);
+        }
+    });
     SBL_LAUNCH_CHECK("sbl_wgrad_group_f32");
     return 0;
 }

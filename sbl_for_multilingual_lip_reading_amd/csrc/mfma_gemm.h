@@ -343,37 +343,6 @@ __device__ __forceinline__ void sbl_gemm_tile(const AL& al, const BL& bl, const 
         sbl_gemm_tile_bf<AL, BL, EPI, BM, BN, 1, WN, PREC, NH>(al, bl, epi, sc, M, N, m0, n0, kbeg, kend, tile, z, nz, colsum_tile);
 }
 
-// Launch the instantiation of the current matrix-product precision (g_sbl_prec, tuning.h).
-#define SBL_PREC_LAUNCH(KERNEL_P, grid, s, ...)                                                         \
-    do {                                                                                                \
-        switch (g_sbl_prec) {                                                                           \
-            case 6: hipLaunchKernelGGL((KERNEL_P(6)), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            case 3: hipLaunchKernelGGL((KERNEL_P(3)), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            case 1: hipLaunchKernelGGL((KERNEL_P(1)), grid, dim3(256), 0, s, __VA_ARGS__); break;       \
-            default: hipLaunchKernelGGL((KERNEL_P(0)), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-        }                                                                                               \
-    } while (0)
-
-// Same for kernels with a wave-group K split (last template argument NH): the split-bf16 bodies of 64x64 tiles launch 512
-// threads (NH = 2) when the launch has no split-K over workgroups; the fp32 body always runs NH = 1.
-#define SBL_PREC_LAUNCH_NH(KERNEL_PN, nh, grid, s, ...)                                                        \
-    do {                                                                                                       \
-        if ((nh) == 2 && g_sbl_prec != 0) {                                                                    \
-            switch (g_sbl_prec) {                                                                              \
-                case 6: hipLaunchKernelGGL((KERNEL_PN(6, 2)), grid, dim3(512), 0, s, __VA_ARGS__); break;      \
-                case 3: hipLaunchKernelGGL((KERNEL_PN(3, 2)), grid, dim3(512), 0, s, __VA_ARGS__); break;      \
-                default: hipLaunchKernelGGL((KERNEL_PN(1, 2)), grid, dim3(512), 0, s, __VA_ARGS__); break;     \
-            }                                                                                                  \
-        } else {                                                                                               \
-            switch (g_sbl_prec) {                                                                              \
-                case 6: hipLaunchKernelGGL((KERNEL_PN(6, 1)), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-                case 3: hipLaunchKernelGGL((KERNEL_PN(3, 1)), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-                case 1: hipLaunchKernelGGL((KERNEL_PN(1, 1)), grid, dim3(256), 0, s, __VA_ARGS__); break;      \
-                default: hipLaunchKernelGGL((KERNEL_PN(0, 1)), grid, dim3(256), 0, s, __VA_ARGS__); break;     \
-            }                                                                                                  \
-        }                                                                                                      \
-    } while (0)
-
 // When the wave-group K split pays (measured inside the step, same shapes with and without it): launches of about one tile
 // per CU, where a tile's serial slab chain bounds the launch - 2 x 960 x 512 x 2048 58 -> 39 us, 2 x 960 x 512 x 512
 // 18 -> 15 us.  At two tiles per CU single launches still gain (4352 x 512 x 1536 110 -> 91 us) but the step does not (the
@@ -450,14 +419,16 @@ static inline void sbl_launch_gemm2(const AL& al, const BL& bl, const EPI& epi, 
     int kchunk = sbl_cdiv(sbl_cdiv(K, splits), MK) * MK;
     int nz = sbl_cdiv(K, kchunk);
     dim3 grid(sbl_cdiv(M, BM), 2 * sbl_cdiv(N, BN), nz);
+    // (the split-bf16 bodies of 64x64 tiles launch 512 threads, NH = 2, when the launch has no split-K over workgroups)
     if constexpr (BM == 64 && BN == 64) {
-#define SBL_K_(P, H) sbl_mfma_gemm2_kernel<AL, BL, EPI, BM, BN, KU, P, H>
-        SBL_PREC_LAUNCH_NH(SBL_K_, sbl_wave_ksplit_pays((long)grid.x * grid.y, nz) ? 2 : 1, grid, s, al, bl, epi, sc, du, M, N, K, kchunk);
-#undef SBL_K_
+        sbl_with_prec_nh(sbl_wave_ksplit_pays((long)grid.x * grid.y, nz) ? 2 : 1, [&](auto p, auto nh) {
+            constexpr int P = decltype(p)::value, NH = decltype(nh)::value;
+            hipLaunchKernelGGL((sbl_mfma_gemm2_kernel<AL, BL, EPI, BM, BN, KU, P, NH>), grid, dim3(256 * NH), 0, s, al, bl, epi, sc, du, M, N, K, kchunk);
+        });
     } else {
-#define SBL_K_(P) sbl_mfma_gemm2_kernel<AL, BL, EPI, BM, BN, KU, P>
-        SBL_PREC_LAUNCH(SBL_K_, grid, s, al, bl, epi, sc, du, M, N, K, kchunk);
-#undef SBL_K_
+        sbl_with_prec([&](auto p) {
+            hipLaunchKernelGGL((sbl_mfma_gemm2_kernel<AL, BL, EPI, BM, BN, KU, decltype(p)::value>), grid, dim3(256), 0, s, al, bl, epi, sc, du, M, N, K, kchunk);
+        });
     }
 }
 
@@ -555,13 +526,14 @@ static inline void sbl_launch_gemm(const AL& al, const BL& bl, const EPI& epi, i
     int nz = sbl_cdiv(K, kchunk);
     dim3 grid(sbl_cdiv(M, BM), sbl_cdiv(N, BN), nz);
     if constexpr (BM == 64 && BN == 64 && WN == 2 && AL::kDenseOperand && BL::kDenseOperand) {
-#define SBL_K_(P, H) sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, WN, P, H>
-        SBL_PREC_LAUNCH_NH(SBL_K_, sbl_wave_ksplit_pays((long)grid.x * grid.y, nz) ? 2 : 1, grid, s, al, bl, epi, sc, M, N, K, kchunk, -1);
-#undef SBL_K_
+        sbl_with_prec_nh(sbl_wave_ksplit_pays((long)grid.x * grid.y, nz) ? 2 : 1, [&](auto p, auto nh) {
+            constexpr int P = decltype(p)::value, NH = decltype(nh)::value;
+            hipLaunchKernelGGL((sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, WN, P, NH>), grid, dim3(256 * NH), 0, s, al, bl, epi, sc, M, N, K, kchunk, -1);
+        });
     } else {
-#define SBL_K_(P) sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, WN, P>
-        SBL_PREC_LAUNCH(SBL_K_, grid, s, al, bl, epi, sc, M, N, K, kchunk, -1);
-#undef SBL_K_
+        sbl_with_prec([&](auto p) {
+            hipLaunchKernelGGL((sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, WN, decltype(p)::value>), grid, dim3(256), 0, s, al, bl, epi, sc, M, N, K, kchunk, -1);
+        });
     }
 }
 
@@ -586,12 +558,14 @@ static inline bool sbl_launch_gemm_tailsplit(const AL& al, const BL& bl, const E
     if (sp < 2 || rem > ws_counters) return false;
     const long need = (long)sizeof(int) * ws_counters + rem * sp * (long)(BM * BN * sizeof(float));
     if (need > ws_bytes) return false;
-    SplitCtl sa{nullptr, nullptr, nullptr, sbl_next_stamp_slot(stamp_kid)};
-#define SBL_K_(P) sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, 2, P>
-    SBL_PREC_LAUNCH(SBL_K_, dim3(XA, Y, 1), s, al, bl, epi, sa, M, N, K, K, -1);
-    SplitCtl sb{(float*)((char*)ws + sizeof(int) * ws_counters), (int*)ws, nullptr, sbl_next_stamp_slot(stamp_kid)};
     const int kchunk = sbl_cdiv(sbl_cdiv(K, sp), MK) * MK;
-    SBL_PREC_LAUNCH(SBL_K_, dim3(X - XA, Y, sbl_cdiv(K, kchunk)), s, al, bl, epi, sb, M, N, K, kchunk, -(XA + 1));
-#undef SBL_K_
+    sbl_with_prec([&](auto p) {
+        constexpr int P = decltype(p)::value;
+        SplitCtl sa{nullptr, nullptr, nullptr, sbl_next_stamp_slot(stamp_kid)};
+        hipLaunchKernelGGL((sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, 2, P>), dim3(XA, Y, 1), dim3(256), 0, s, al, bl, epi, sa, M, N, K, K, -1);
+        SplitCtl sb{(float*)((char*)ws + sizeof(int) * ws_counters), (int*)ws, nullptr, sbl_next_stamp_slot(stamp_kid)};
+        hipLaunchKernelGGL((sbl_mfma_gemm_kernel<AL, BL, EPI, BM, BN, KU, 2, P>), dim3(X - XA, Y, sbl_cdiv(K, kchunk)), dim3(256), 0, s, al, bl, epi, sb, M, N, K,
+                           kchunk, -(XA + 1));
+    });
     return true;
 }

@@ -99,6 +99,8 @@ __device__ __forceinline__ int sbl_seg_of_row(const SegDesc& d, int r, int B) {
 static inline int sbl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool sbl_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
+#include "launch.h"      // precision dispatch, dynamic-LDS cap
+
 // ---- wave-level reductions (64-wide wavefront; no LDS)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

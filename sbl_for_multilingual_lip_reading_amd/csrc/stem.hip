@@ -488,12 +488,7 @@ static int stem_launch_fwd_bf2(const Src& x, const float* w, float* conv_out, do
                                int Wo, int TY, int TX, int ntiles, hipStream_t s) {
     constexpr int lds = SB_KS * 2 * BfTerms<NT>::NPL * 1024 + 2 * SB_PATCH * 4 + (st_is_raw<Src> ? ST_LUT * 4 : 0);
     static bool set[64] = {false};
-    int dev = 0;
-    SBL_HIP(hipGetDevice(&dev));
-    if (!set[dev & 63]) {
-        SBL_HIP(hipFuncSetAttribute((const void*)stem_conv_fwd_bf2_kernel<NT, typename StemKArg<Src>::type>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        set[dev & 63] = true;
-    }
+    SBL_HIP(sbl_raise_lds_cap((const void*)stem_conv_fwd_bf2_kernel<NT, typename StemKArg<Src>::type>, lds, set));
     const int npairs = (ntiles + 1) / 2;
     const int grid = npairs < 256 ? npairs : 256;          // persistent: one workgroup per CU
     hipLaunchKernelGGL((stem_conv_fwd_bf2_kernel<NT, typename StemKArg<Src>::type>), dim3(grid), dim3(512), lds, s, x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX,
@@ -1182,9 +1177,14 @@ static int stem_conv_fwd_any(const char* who, const Src& x, const float* w, floa
     SBL_REQUIRE(ntiles < (1L << 31), "%s: too many tiles", who);
     SBL_HIP(hipMemsetAsync(stats, 0, sizeof(double) * 128, s));
     if (g_sbl_prec) {
-        const int e = g_sbl_prec == 6 ? stem_launch_fwd_bf2<6>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-                    : g_sbl_prec == 3 ? stem_launch_fwd_bf2<3>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s)
-                                      : stem_launch_fwd_bf2<1>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
+        const int e = sbl_with_prec([&](auto p) {
+            constexpr int NT = decltype(p)::value;
+            if constexpr (NT == 0) {      // (excluded above; a precision without a split-bf16 kernel must not pass for a launch)
+                sbl_set_error("%s: no split-bf16 kernel for matrix precision %d", who, g_sbl_prec);
+                return (int)SBL_ERR_INVALID;
+            }
+            else return stem_launch_fwd_bf2<NT>(x, w, conv_out, stats, N, T, H, W, Ho, Wo, TY, TX, (int)ntiles, s);
+        });
         if (e) return e;
         SBL_LAUNCH_CHECK(st_is_raw<Src> ? "sbl_stem_conv_fwd_u8(bf16)" : "sbl_stem_conv_fwd(bf16)");
         return 0;
@@ -1272,6 +1272,19 @@ extern "C" int sbl_stem_bwd_reduce(const float* conv_out, const float* dpooled, 
     return 0;
 }
 
+template <int NT, class Src>
+static int stem_launch_wgrad_tr(const Src& x, const float* conv_out, const float* dpooled, const uint8_t* argmax, const float* mean,
+                                const float* invstd, const float* gamma, const float* beta, const double* sums, float* dw, float* dgamma,
+                                float* dbeta, int N, int T, int H, int W, int Ho, int Wo, int TY, int TX, int ntiles, int grid, hipStream_t s) {
+    const size_t lds = 2 * BfTerms<NT>::NPL * SW_PLANE + BfTerms<NT>::NPL * SW_DPLANE + 6 * 64 * sizeof(float) +
+                       (st_is_raw<Src> ? ST_LUT * sizeof(float) : 0);
+    static bool set[64] = {false};
+    SBL_HIP(sbl_raise_lds_cap((const void*)stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>, 96 * 1024, set));
+    hipLaunchKernelGGL((stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>), dim3(grid), dim3(SW_THREADS), lds, s, x, conv_out, dpooled, argmax, mean, invstd, gamma,
+                       beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, ntiles, sbl_next_stamp_slot(SBL_KID_STEM));
+    return 0;
+}
+
 template <class Src>
 static int stem_wgrad_any(const char* who, const Src& x, const float* conv_out, const float* dpooled, const uint8_t* argmax,
                           const float* mean, const float* invstd, const float* gamma, const float* beta, const double* sums, float* dw,
@@ -1283,24 +1296,16 @@ static int stem_wgrad_any(const char* who, const Src& x, const float* conv_out, 
     SBL_HIP(hipMemsetAsync(dw, 0, sizeof(float) * 64 * ST_K, s));
     if (g_sbl_prec) {
         const int grid2 = (int)(ntiles < 512 ? ntiles : 512);   // 2 workgroups per CU (77 KB LDS each)
-#define SBL_SWT_(NT)                                                                                                           \
-    do {                                                                                                                       \
-        const size_t lds = 2 * BfTerms<NT>::NPL * SW_PLANE + BfTerms<NT>::NPL * SW_DPLANE + 6 * 64 * sizeof(float) +           \
-                           (st_is_raw<Src> ? ST_LUT * sizeof(float) : 0);                                                            \
-        static bool set_[64] = {false};                                                                                        \
-        int dev = 0;                                                                                                           \
-        SBL_HIP(hipGetDevice(&dev));                                                                                           \
-        if (!set_[dev & 63]) {                                                                                                 \
-            SBL_HIP(hipFuncSetAttribute((const void*)stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); \
-            set_[dev & 63] = true;                                                                                             \
-        }                                                                                                                      \
-        hipLaunchKernelGGL((stem_wgrad_tr_kernel<NT, typename StemKArg<Src>::type>), dim3(grid2), dim3(SW_THREADS), lds, s, x, conv_out, dpooled, argmax, mean, invstd, gamma, \
-                           beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, Ho / 2, Wo / 2, TY, TX, (int)ntiles, sbl_next_stamp_slot(SBL_KID_STEM)); \
-    } while (0)
-        if (g_sbl_prec == 6) SBL_SWT_(6);
-        else if (g_sbl_prec == 3) SBL_SWT_(3);
-        else SBL_SWT_(1);
-#undef SBL_SWT_
+        const int e = sbl_with_prec([&](auto p) {
+            constexpr int NT = decltype(p)::value;
+            if constexpr (NT == 0) {      // (excluded above; a precision without a split-bf16 kernel must not pass for a launch)
+                sbl_set_error("%s: no split-bf16 kernel for matrix precision %d", who, g_sbl_prec);
+                return (int)SBL_ERR_INVALID;
+            }
+            else return stem_launch_wgrad_tr<NT>(x, conv_out, dpooled, argmax, mean, invstd, gamma, beta, sums, dw, dgamma, dbeta, N, T, H, W, Ho, Wo, TY,
+                                                 TX, (int)ntiles, grid2, s);
+        });
+        if (e) return e;
         SBL_LAUNCH_CHECK(st_is_raw<Src> ? "sbl_stem_wgrad_u8(bf16)" : "sbl_stem_wgrad(bf16)");
         return 0;
     }

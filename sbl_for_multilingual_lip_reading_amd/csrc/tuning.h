@@ -26,6 +26,8 @@ constexpr int sbl_wave_ksplit_max_tiles = 320;   // largest tile count that take
 constexpr int sbl_gemm2_split_tiles = 192, sbl_gemm2_split_target = 256, sbl_gemm2_split_max = 8;
 
 // ---- trunk convolutions (conv.hip, conv_patch_wgrad.h)
+constexpr int sbl_pm_max_hw = 121;               // largest Ho*Wo of a 3x3 / stride-1 convolution that takes the position-major path (ResNet
+                                                 // layers 2-4: 11x11, 6x6, 3x3; the 22x22 maps of layer 1 lose: 6 % padding, 434 vs 396 us)
 constexpr bool sbl_wg_s2_small = true;           // stride-2 weight gradients on 64x64 tiles (128 -> 256: 459 -> 335 us, 256 -> 512: 447 -> 400 us)
 constexpr int sbl_wg_s2_target = 1536;           // ... and their workgroup target (same-box step A/B 32.44 / 32.34 / 32.29 ms for 128-tiles /
                                                  // 64-tiles / 64-tiles + 1536)
