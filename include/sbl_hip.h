@@ -422,6 +422,46 @@ int sbl_decode_tail(const float* y, long ldy, const float* w, float* logits, lon
                     const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next, int B, int V, int D,
                     sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- beam search of the single-direction decoder
+ * LRW1000/transformer/decoder.py:131-245, batched: clip n owns the W = beam_size slots n*W .. n*W + W-1 and every launch
+ * runs all S = N * W slots; a slot without a live hypothesis carries the score -inf.  Ties, which the reference leaves to
+ * torch.topk: the lower parent slot first, then the lower token id.  A candidate of score -inf is never kept.
+ *
+ * sbl_decode_attn_step for beam slots (replaces the per-hypothesis prefix recompute of LRW1000/transformer/decoder.py:170-184).
+ * append = 1 (self-attention): anc (S, lda) int32 is the ancestry table - key j < n_prev of slot b is row j of cache slot
+ * anc[b][j] (values are clamped to 0 .. S-1), for the score and the value pass; the new rows k_new / v_new are stored at row
+ * n_prev of slot b's OWN cache and used from registers.  k_cache / v_cache: (S, Lcap, H*64).  No cache row is ever copied.
+ * append = 0 (cross-attention): anc is unused (NULL); slot b reads rows 0 .. n_prev-1 of the hoisted cache of clip b / W, so
+ * k_cache / v_cache hold S / W clips.  Strides, Lcap <= 64, scale and o as in sbl_decode_attn_step. */
+int sbl_beam_attn_step(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                       float* v_cache, long ldc, int Lcap, const int32_t* anc, long lda, float* o, long ldo, int S, int W, int H,
+                       int n_prev, int append, float scale, sbl_stream_t stream);
+/* Tail of beam step `step` in one launch, one workgroup per clip (LRW1000/transformer/decoder.py:186-229): logits = y w^T
+ * (fp32 FMA, V <= 64, 1 <= W <= min(16, V)); local = log_softmax(logits) + log_prior[last_tok[slot]] (log_prior: NULL or
+ * (V, V) fp32, already logged, -inf allowed: decoder.py:163-166,191); candidates = score[slot] + local, fp32; the best W of
+ * the clip's W * V candidates are kept in order.  At step maxlen-1 every kept hypothesis ends (decoder.py:213-218: an <eos> is
+ * appended at no score, also behind an <eos>); before that the ones whose token is eos end (decoder.py:222-227).  Written:
+ *   hist_tok / hist_par / hist_score / hist_flag (N, maxlen, W) at [n][step][rank]: token, parent rank at the previous step,
+ *     accumulated score, flag (0 nothing kept, 1 live, 2 ended);
+ *   end_score / end_ref (N, W*maxlen), end_count (N): the ended list in kept order, ref = step * W + rank (step 0 resets the
+ *     count, so nothing has to be zeroed between calls);
+ *   score / last_tok (S), in place: rank r moves to slot n*W + r; score = -inf unless live;
+ *   anc_new (S, lda >= maxlen): anc_new[r][0..step-1] = anc_old[parent][0..step-1], anc_new[r][step] = the parent's slot
+ *     (anc_old and anc_new must differ: the kernel reads the parents' rows);
+ *   x_next (S, 512), when not NULL: emb[token] * emb_scale + pe[step+1], the next step's input rows. */
+int sbl_beam_tail(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
+                  const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par, float* hist_score,
+                  int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count, int step, int maxlen, int eos,
+                  const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next, int N, int W, int V, int D,
+                  sbl_stream_t stream);
+/* The nbest <= 16 best ended hypotheses of every clip, a stable descending sort by score (LRW1000/transformer/decoder.py:240-245;
+ * no length normalisation), traced back through the history: yseq (N, nbest, maxlen+2) int64 = <sos>, the tokens, eos-filled
+ * behind the end; lengths (N, nbest) int32 (maxlen+2 for a hypothesis that ended at the last step); scores (N, nbest) fp32;
+ * n_hyps (N) int32 = min(ended, nbest).  Ranks beyond n_hyps: length 0, score -inf, an all-eos row. */
+int sbl_beam_finish(const float* end_score, const int32_t* end_ref, const int32_t* end_count, const int32_t* hist_tok,
+                    const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N, int W,
+                    int maxlen, int nbest, int sos, int eos, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
  * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.

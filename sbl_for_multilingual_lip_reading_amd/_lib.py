@@ -67,6 +67,9 @@ SIGNATURES = {
     "sbl_embed_scale_bwd": [P, L, P, P, I, I, I, I, F, P],
     "sbl_decode_attn_step": [P, L, P, P, L, P, P, L, I, P, L, I, I, I, I, F, P],
     "sbl_decode_tail": [P, L, P, P, L, P, L, I, P, P, I, F, P, I, I, I, P],
+    "sbl_beam_attn_step": [P, L, P, P, L, P, P, L, I, P, L, P, L, I, I, I, I, I, F, P],
+    "sbl_beam_tail": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P],
+    "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
     "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],

@@ -1959,3 +1959,72 @@ def decode_tail(y, w, ys, step, emb, pe, emb_scale, x_next=None, logits=None):
     assert x_next is None or (x_next.is_contiguous() and x_next.shape == (B, D) and pe.is_contiguous() and emb.is_contiguous())
     call("sbl_decode_tail", _p(y), y.stride(0), _p(w), _p(logits), 0 if logits is None else logits.stride(0), _p(ys), ys.stride(0),
          int(step), _p(emb), _p(pe), pe.size(0), emb_scale, _p(x_next), B, V, D, _s())
+
+
+def beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale=0.125):
+    """decode_attn_step for beam slots (include/sbl_hip.h, sbl_beam_attn_step): q / k_new / v_new / out are (S, H*64) row views,
+    S = clips * W.  append: k_cache / v_cache (S, Lcap, H*64) and anc (S, >= n_prev) int32 names the cache slot of every key;
+    otherwise (cross-attention) k_cache / v_cache hold S / W clips and anc is None."""
+    S = q.size(0)
+    ldc = k_cache.stride(-2)
+    nc = S if append else S // W
+    assert v_cache.stride(-2) == ldc and k_cache.stride(-1) == 1 and q.stride(1) == 1 and out.stride(1) == 1
+    assert k_cache.dim() == 3 and k_cache.size(0) == nc and k_cache.size(1) == Lcap and k_cache.stride(0) == Lcap * ldc
+    assert v_cache.shape == k_cache.shape and v_cache.stride(0) == Lcap * ldc and out.size(0) == S
+    if append:
+        assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
+        assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.size(0) == S and anc.stride(1) == 1
+    call("sbl_beam_attn_step", _p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache),
+         _p(v_cache), ldc, Lcap, _p(anc) if append else None, anc.stride(0) if append else 0, _p(out), out.stride(0), S, int(W), H,
+         int(n_prev), int(bool(append)), scale, _s())
+    return out
+
+
+class BeamState(object):
+    """The device buffers of one beam search over N clips with W slots each (include/sbl_hip.h, sbl_beam_tail): allocated
+    once per call; reset() restores the start (one hypothesis <sos> of score 0 per clip) with fill launches only."""
+
+    def __init__(self, N, W, maxlen, sos_id, device):
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)      # noqa: E731
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)    # noqa: E731
+        self.N, self.W, self.maxlen, self.sos_id = N, W, maxlen, sos_id
+        self.score, self.last_tok = f32(N, W), i32(N, W)
+        self.anc = i32(2, N * W, maxlen)
+        self.hist_tok, self.hist_par, self.hist_flag = i32(N, maxlen, W), i32(N, maxlen, W), i32(N, maxlen, W)
+        self.hist_score = f32(N, maxlen, W)
+        self.end_score, self.end_ref, self.end_count = f32(N, W * maxlen), i32(N, W * maxlen), i32(N)
+        self.reset()
+
+    def reset(self):
+        self.score.fill_(float("-inf"))
+        self.score[:, 0] = 0.0
+        self.last_tok.fill_(self.sos_id)
+
+    def history(self):
+        return self.hist_tok, self.hist_par, self.hist_score, self.hist_flag
+
+
+def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None):
+    """Tail of beam step `step` in one launch (sbl_beam_tail) on the rows y (N*W, 512): the best W candidates of every clip
+    into the BeamState `st` (ancestry buffer step % 2 is read, the other one written), x_next = the next input rows."""
+    S, D = y.shape
+    V = w.size(0)
+    assert S == st.N * st.W and y.stride(1) == 1 and w.is_contiguous()
+    assert log_prior is None or (log_prior.dtype == torch.float32 and log_prior.shape == (V, V) and log_prior.is_contiguous())
+    assert x_next is None or (x_next.is_contiguous() and x_next.shape == (S, D) and pe.is_contiguous() and emb.is_contiguous())
+    call("sbl_beam_tail", _p(y), y.stride(0), _p(w), _p(log_prior), _p(st.score), _p(st.last_tok), _p(st.anc[step % 2]),
+         _p(st.anc[1 - step % 2]), st.anc.stride(1), _p(st.hist_tok), _p(st.hist_par), _p(st.hist_score), _p(st.hist_flag),
+         _p(st.end_score), _p(st.end_ref), _p(st.end_count), int(step), st.maxlen, int(eos_id), _p(emb), _p(pe), pe.size(0),
+         emb_scale, _p(x_next), st.N, st.W, V, D, _s())
+
+
+def beam_finish(st, nbest, eos_id):
+    """(yseq (N, nbest, maxlen+2) int64, lengths (N, nbest) int32, scores (N, nbest), n_hyps (N) int32): sbl_beam_finish."""
+    dev = st.score.device
+    yseq = torch.empty(st.N, nbest, st.maxlen + 2, dtype=torch.int64, device=dev)
+    lengths = torch.empty(st.N, nbest, dtype=torch.int32, device=dev)
+    scores = torch.empty(st.N, nbest, dtype=torch.float32, device=dev)
+    n_hyps = torch.empty(st.N, dtype=torch.int32, device=dev)
+    call("sbl_beam_finish", _p(st.end_score), _p(st.end_ref), _p(st.end_count), _p(st.hist_tok), _p(st.hist_par), _p(yseq),
+         _p(lengths), _p(scores), _p(n_hyps), st.N, st.W, st.maxlen, int(nbest), int(st.sos_id), int(eos_id), _s())
+    return yseq, lengths, scores, n_hyps

@@ -7,6 +7,8 @@ entry points the SBL model uses; the greedy decode keeps a K/V cache per layer a
 (csrc/decode_step.hip; the GEMM / LayerNorm launches around that one-row attention core are the shared sub-layer functions
 of ops.py) instead of re-running the whole prefix at every step as LRW/transformer/decoder.py:146-164 does: every
 layer of this decoder is causal, so row i of every sub-layer depends on rows <= i only."""
+import collections
+
 import torch
 import torch.nn as nn
 
@@ -19,6 +21,12 @@ from .video_frontend import Lipreading
 IGNORE_ID = config.IGNORE_ID
 MAX_TGT_LEN = 14          # pad_list's fixed max_len (LRW/transformer/utils.py:5): <sos> + at most 13 tokens
 MAX_KEYS = 64             # one key per lane in the decode-step attention; the teacher-forced kernels share the bound
+MAX_BEAM = 16             # slots per clip in the beam tail (csrc/beam_step.hip); nbest has the same bound
+
+# beam_search's result: yseq (N, nbest, maxlen+2) int64 (<sos>, tokens, eos-filled behind the end), lengths (N, nbest) int32,
+# scores (N, nbest) fp32, n_hyps (N) int32 (ranks beyond it: length 0, score -inf), history = the per-(clip, step, rank)
+# kept (token, parent rank, score, flag) tensors, each (N, maxlen, W)
+BeamResult = collections.namedtuple("BeamResult", ("yseq", "lengths", "scores", "n_hyps", "history"))
 
 
 class Seq2SeqDecoder(nn.Module):
@@ -216,6 +224,75 @@ class Seq2SeqDecoder(nn.Module):
             ops.decode_tail(cur, w, ys, i, emb, pe, scale, x_next=x if i + 1 < T else None)
         return ys
 
+    # ------------------------------------------------------------------ beam search
+    def beam_search(self, encoder_outputs, beam_size, nbest=1, decode_max_len=0, log_prior=None):
+        """Beam search of LRW1000/transformer/decoder.py:131-245 for all N clips at once: each clip keeps beam_size
+        hypotheses, every step adds log_softmax(logits) + log_prior[last token] (log_prior: None or the (V, V) fp32 table
+        torch.log(bigram_freq), -inf allowed) in fp32, hypotheses that emit <eos> move to the ended list, at step
+        maxlen - 1 (maxlen = decode_max_len or Ti) every kept hypothesis ends with an appended <eos>, and the nbest best
+        ended hypotheses come back, best first, without length normalisation -> BeamResult.  Exact ties, which the
+        reference leaves to torch.topk: the lower parent slot first, then the lower token id.  A candidate of score -inf
+        is never kept.  The step is KV-cached like the greedy decode (one new row per slot and step; the slots' caches are
+        followed through an ancestry table, never copied), eval-only, with no host read: capturable as one hipGraph."""
+        enc = encoder_outputs
+        self._check_encoder(enc)
+        N, T, D = enc.shape
+        W, nbest = int(beam_size), int(nbest)
+        maxlen = int(decode_max_len) or T
+        V = self.n_tgt_vocab
+        if not 1 <= W <= min(MAX_BEAM, V):
+            raise _lib.SblHipError("Seq2SeqDecoder.beam_search: beam_size = %d outside 1..min(%d, V = %d)" % (W, MAX_BEAM, V))
+        if not 1 <= nbest <= MAX_BEAM:
+            raise _lib.SblHipError("Seq2SeqDecoder.beam_search: nbest = %d outside 1..%d" % (nbest, MAX_BEAM))
+        if not 1 <= maxlen <= min(MAX_KEYS, self.pe_maxlen):
+            raise _lib.SblHipError("Seq2SeqDecoder.beam_search: %d decode steps; the cache holds at most %d rows and the "
+                                   "positional table %d" % (maxlen, MAX_KEYS, self.pe_maxlen))
+        if log_prior is not None and (log_prior.dtype != torch.float32 or tuple(log_prior.shape) != (V, V)
+                                      or log_prior.device != enc.device):
+            raise _lib.SblHipError("Seq2SeqDecoder.beam_search: log_prior must be a (%d, %d) fp32 tensor on %s" % (V, V, enc.device))
+        if self.training and self.dropout.p > 0:
+            raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+        self._fuse()
+        with torch.no_grad():
+            return self._beam_cached(enc, W, nbest, maxlen, None if log_prior is None else log_prior.contiguous())
+
+    def _beam_cached(self, enc, W, nbest, maxlen, log_prior):
+        N, T, D = enc.shape
+        dev = enc.device
+        S = N * W
+        layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
+        nl, H = len(layers), self.n_head
+        HD, F_ = H * 64, self.d_inner
+        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+
+        # cross-attention K / V of all layers: one GEMM over the N clips; the W slots of a clip read the same rows
+        kv = [blk.view(N, T, 2 * HD) for blk in ops.project_kv_block(enc.contiguous().view(N * T, D), self.cross_attention_modules())[2]]
+        cache = new(nl, 2, S, maxlen, HD)     # row i of slot b is written at step i by whatever hypothesis lives in b then
+        st = ops.BeamState(N, W, maxlen, self.sos_id, dev)
+        emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
+        V, scale = emb.size(0), float(self.x_logit_scale)
+        x = new(S, D)
+        tok0 = torch.full((S, 1), self.sos_id, dtype=torch.long, device=dev)
+        ops.call("sbl_embed_scale_pe_fwd", ops._p(tok0), 1, ops._p(emb), ops._p(pe), ops._p(x), S, 1, D, V, scale, 0, ops._s())
+        qkv, q, att, o, h = new(S, 3 * HD), new(S, HD), new(S, HD), new(S, D), new(S, F_)
+        ya, yb, yc = new(S, D), new(S, D), new(S, D)
+        mean, rstd = new(S), new(S)
+
+        for i in range(maxlen):
+            cur = x
+            anc = st.anc[i % 2]
+            for l, (sa, ca, ff) in enumerate(layers):
+                ops.lin_fwd(sa.inp, cur, qkv)
+                ops.beam_attn_step(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], maxlen, anc, att, W, H, i, True)
+                ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
+                ops.lin_fwd(ca.inp, ya, q)
+                ops.beam_attn_step(q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, None, att, W, H, T, False)
+                ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
+                ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
+                cur = yc
+            ops.beam_tail(cur, w, log_prior, st, i, self.eos_id, emb, pe, scale, x_next=x if i + 1 < maxlen else None)
+        return BeamResult(*ops.beam_finish(st, nbest, self.eos_id), st.history())
+
 
 class Seq2SeqTransformer(nn.Module):
     """Lip crops -> visual frontend -> encoder -> single-direction decoder (LRW/transformer/transformer.py:4-75).  Submodule
@@ -259,12 +336,30 @@ class Seq2SeqTransformer(nn.Module):
         enc, _ = self._encode(input)
         return self.decoder.recognize_beam(enc, char_list, args, cached=cached)
 
-    def validate(self, padded_input, padded_target, meter, valid_rows=None):
+    def recognize_nbest(self, input, char_list, args, log_prior=None):
+        """The beam search of LRW1000/transformer/transformer.py:46-72 for every clip of a batch: args.beam_size, args.nbest and
+        args.decode_max_len as there (char_list is unused there too).  Returns, per clip, the reference's
+        [{'score': float, 'yseq': [ids]}], best first.  One synchronisation, the read of the result."""
+        enc, _ = self._encode(input)
+        res = self.decoder.beam_search(enc, args.beam_size, args.nbest, args.decode_max_len, log_prior)
+        host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in res[:4]]
+        torch.cuda.current_stream(res.yseq.device).synchronize()
+        yseq, lengths, scores, n_hyps = (t.tolist() for t in host)
+        return [[{'score': scores[n][k], 'yseq': yseq[n][k][:lengths[n][k]]} for k in range(n_hyps[n])] for n in range(len(yseq))]
+
+    def validate(self, padded_input, padded_target, meter, valid_rows=None, beam_size=None, log_prior=None):
         """One validation batch (the body of LRW/train.py:229-254): greedy decode, then score ys against the (N, To)
-        IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device; capturable like recognize.  Returns ys."""
+        IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device; capturable like recognize.  Returns ys.
+        With beam_size the decode is the beam search (log_prior as in Seq2SeqDecoder.beam_search) and ys its 1-best yseq
+        (N, T + 2), whose eos padding the scorer strips like the greedy rows' tail."""
+        if beam_size is not None:
+            enc, _ = self._encode(padded_input)
+            ys = self.decoder.beam_search(enc, beam_size, 1, 0, log_prior).yseq[:, 0]
+            meter.update_single(ys, padded_target, valid_rows=valid_rows)
+            return ys
         ys = self.recognize(padded_input)
         meter.update_single(ys, padded_target, valid_rows=valid_rows)
         return ys
 
 
-__all__ = ["Seq2SeqDecoder", "Seq2SeqTransformer", "MAX_TGT_LEN"]
+__all__ = ["Seq2SeqDecoder", "Seq2SeqTransformer", "BeamResult", "MAX_TGT_LEN"]
