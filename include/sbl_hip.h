@@ -338,6 +338,43 @@ int sbl_fusion_seg_bwd(const float* da2, const float* db2, float* da, float* db,
 int sbl_gather_last_fwd(const float* x, float* out, int B, const int* seg_L, int nseg, int D, sbl_stream_t stream);
 int sbl_gather_last_bwd(const float* dy, float* dx, int B, const int* seg_L, int nseg, int D, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- last decoder layer on its "ends" rows
+ * Of the last layer's output the step reads two rows per sequence: pred = prj(dec_output[:, -1]) after the last fusion
+ * (SBL/transformer/decoder.py:160-167), i.e. A'[L-1] = A[L-1] + B[0] and B'[L-1] = 2 B[L-1] + A[0].  Everything of that layer
+ * behind the self-attention core (attention.py:53-58 onwards, module.py:47-51) therefore runs on a compact batch: segment s
+ * (prefix length L = seg_L[s]) holds B sequences of Lc = min(2, L) rows in (b, k) order, k = 0 -> position 0, k = Lc-1 ->
+ * position L-1; compact row (s, b, k) stands for full row (sum_{t<s} B*seg_L[t]) + b*L + k*(L-1).  seg_L is always the list
+ * of FULL prefix lengths.  Dropout decisions are those of the full-layout kernels for the same element. */
+/* dst_t (compact rows, D) = the end rows of src_t (full rows, D) for up to four tensors in one launch (trailing ones NULL). */
+int sbl_ends_gather4(const float* src0, const float* src1, const float* src2, const float* src3, float* dst0, float* dst1,
+                     float* dst2, float* dst3, int B, const int* seg_L, int nseg, int D, sbl_stream_t stream);
+/* dst_t (full rows, D) = src_t (compact rows) at the end rows and zero elsewhere (every row is written: no zero fill needed);
+ * one or two tensors (src1 / dst1 NULL). */
+int sbl_ends_scatter2(const float* src0, const float* src1, float* dst0, float* dst1, int B, const int* seg_L, int nseg, int D,
+                      sbl_stream_t stream);
+/* Adjoint of the stage tail's fusion (decoder.py:160-167) into the compact layout: dy_d(s, b, last) = kf_d * dlast_d[s*B + b]
+ * (kf = 1 for l2r, 2 for r2l), dy_d(s, b, first) = dlast_{1-d}[s*B + b], the L = 1 row gets both; a NULL dlast is zero. */
+int sbl_ends_tail_bwd(const float* dlast0, const float* dlast1, float* dy0, float* dy1, int B, const int* seg_L, int nseg, int D,
+                      sbl_stream_t stream);
+/* sbl_add_layernorm2_fwd / sbl_add_layernorm_bwd (module.py:50-51, attention.py:57-58) on the compact rows. */
+int sbl_add_layernorm2_ends_fwd(const float* x0, const float* x1, const float* res0, const float* res1, const float* gamma0,
+                                const float* gamma1, const float* beta0, const float* beta1, float* y0, float* y1, float* mean0,
+                                float* mean1, float* rstd0, float* rstd1, int B, const int* seg_L, int nseg, int D, float eps,
+                                float drop_p, const uint64_t* seed, uint64_t offset0, uint64_t offset1, sbl_stream_t stream);
+int sbl_add_layernorm_ends_bwd(const float* dy, const float* x, const float* res, const float* gamma, const float* mean,
+                               const float* rstd, float* dz, float* dx_drop, float* dgamma, float* dbeta, int B, const int* seg_L,
+                               int nseg, int D, float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream);
+/* Cross-attention (attention.py:63-83 with the encoder's keys, Lk_fixed <= 32 rows per sequence) of the compact queries, both
+ * directions in one launch / one direction's adjoint; p holds the compact (H*B, Lc, Lk) probability blocks back to back. */
+int sbl_attention_ends2_fwd(const float* q0, const float* q1, long ldq, const float* k0, const float* k1, long ldk, const float* v0,
+                            const float* v1, long ldv, float* o0, float* o1, long ldo, float* p_out0, float* p_out1, int B, int H,
+                            const int* seg_L, int nseg, int Lk_fixed, float scale, float drop_p, const uint64_t* seed,
+                            uint64_t offset0, uint64_t offset1, sbl_stream_t stream);
+int sbl_attention_ends_bwd(const float* dout, long lddo, const float* q, long ldq, const float* k, long ldk, const float* v,
+                           long ldv, const float* p, float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, int B, int H,
+                           const int* seg_L, int nseg, int Lk_fixed, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
+                           sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- SBL decoder pieces
  * Decoder.preprocess (decoder.py:62-77): strip IGNORE_ID, <sos> + ids (input form) / ids (label form), both padded with <eos>
    to maxlen; int64 (N,To) -> two int64 (N,maxlen).  padded1 != NULL: a second target set (the r2l direction) in the same launch. */

@@ -59,6 +59,13 @@ SIGNATURES = {
     "sbl_fusion_seg_bwd": [P, P, P, P, I, P, I, I, P],
     "sbl_gather_last_fwd": [P, P, I, P, I, I, P],
     "sbl_gather_last_bwd": [P, P, I, P, I, I, P],
+    "sbl_ends_gather4": [P, P, P, P, P, P, P, P, I, P, I, I, P],
+    "sbl_ends_scatter2": [P, P, P, P, I, P, I, I, P],
+    "sbl_ends_tail_bwd": [P, P, P, P, I, P, I, I, P],
+    "sbl_add_layernorm2_ends_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, I, F, F, P, U64, U64, P],
+    "sbl_add_layernorm_ends_bwd": [P, P, P, P, P, P, P, P, P, P, I, P, I, I, F, P, U64, P],
+    "sbl_attention_ends2_fwd": [P, P, L, P, P, L, P, P, L, P, P, L, P, P, I, I, P, I, I, F, F, P, U64, U64, P],
+    "sbl_attention_ends_bwd": [P, L, P, L, P, L, P, L, P, P, L, P, L, P, L, I, I, P, I, I, F, F, P, U64, P],
     "sbl_argmax_select": [P, L, P, L, P, L, I, I, P, I, I, P],
     "sbl_decoder_preprocess": [P, P, P, P, P, P, I, I, I, L, L, L, P],
     "sbl_seq_score": [P, P, I, P, P, I, I, L, L, L, P, I, P, P, P, P],

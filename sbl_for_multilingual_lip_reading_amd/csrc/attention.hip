@@ -276,8 +276,13 @@ __device__ __forceinline__ float grp_sum_lo(float v) {   // across n inside a 16
 struct SmallProb {
     int Lq, Lk, b, h, qoff;      // qoff: index of the tile's first query inside its sequence (query-tile mode), else 0
     long qrow, krow, pbase;
+    long mbase;                  // dropout mask index of probability (i, j): mbase + (i * mstep) * Lk + j  (= its place in the
+    int mstep;                   // probability buffer, except in the "ends" mode below)
 };
-__device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const SegDesc& segs, int Lk_fixed) {
+// ENDS (cross-attention of the last decoder layer's compact "ends" rows, sbl_common.h): `segs` describes the compact batch - the
+// Lq <= 2 queries of a sequence are its positions 0 and L-1 - and `full` the full one, whose probability layout indexes the masks.
+template <bool ENDS = false>
+__device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const SegDesc& segs, int Lk_fixed, const SegDesc* full = nullptr) {
     SmallProb P;
     const int sidx = prob / (B * H);
     P.b = (prob / H) % B;
@@ -297,21 +302,32 @@ __device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const Se
         P.qrow = (long)P.b * segs.qtile + ro;
         P.pbase = ((long)P.h * B + P.b) * segs.qtile * P.Lk + po;
     }
+    P.mbase = P.pbase;
+    P.mstep = 1;
+    if constexpr (ENDS) {
+        int Lf = full->L[0], pf = full->p_off[0];
+#pragma unroll
+        for (int t = 1; t < SBL_MAX_SEG; ++t)
+            if (t == sidx) { Lf = full->L[t]; pf = full->p_off[t]; }
+        P.mbase = pf + ((long)P.h * B + P.b) * Lf * P.Lk;
+        P.mstep = Lf - 1;
+    }
     return P;
 }
 
+template <bool ENDS = false>
 __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict__ q, long ldq, const float* __restrict__ k,
                                                          long ldk, const float* __restrict__ v, long ldv,
                                                          float* __restrict__ o, long ldo, float* __restrict__ p_out,
                                                          int causal, int B, int H, const SegDesc& segs, int Lk_fixed,
                                                          float scale, uint32_t thresh, float keep_scale,
                                                          const uint64_t* __restrict__ seed, uint64_t offset, int nprob,
-                                                         unsigned long long* stamp = nullptr) {
+                                                         unsigned long long* stamp = nullptr, const SegDesc* full = nullptr) {
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
     const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
     sbl_stamp_begin(stamp);      // (thread 0 = wavefront 0 of the workgroup, which always has a problem)
     if (prob >= nprob) return;   // whole wavefront; the kernel has no barrier
-    const SmallProb P = small_prob(prob, B, H, segs, Lk_fixed);
+    const SmallProb P = small_prob<ENDS>(prob, B, H, segs, Lk_fixed, full);
     const int Lq = P.Lq, Lk = P.Lk;
     const int NT = Lk > 16 ? 2 : 1;
     const float* qb = q + P.qrow * ldq + P.h * 64;
@@ -361,7 +377,7 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
             float pv = s[t][r] * inv;
             if (n < Lq && j < Lk) {
                 pg[(long)n * Lk + j] = pv;
-                if (thresh) pv = sbl_keep(sd, offset, (uint64_t)P.pbase + (uint64_t)n * Lk + j, thresh) ? pv * keep_scale : 0.f;
+                if (thresh) pv = sbl_keep(sd, offset, (uint64_t)P.mbase + (uint64_t)(n * P.mstep) * Lk + j, thresh) ? pv * keep_scale : 0.f;
             } else {
                 pv = 0.f;
             }
@@ -419,20 +435,28 @@ __global__ __launch_bounds__(256) void attention_small2_fwd_kernel(AttFwdSet a0,
     attention_small_fwd_body(a.q, ldq, a.k, ldk, a.v, ldv, a.o, ldo, a.p_out, causal, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
                              a.offset, nprob);
 }
+__global__ __launch_bounds__(256) void attention_small2_ends_fwd_kernel(AttFwdSet a0, AttFwdSet a1, long ldq, long ldk, long ldv, long ldo, int B,
+                                                                        int H, SegDesc segs, SegDesc full, int Lk_fixed, float scale,
+                                                                        uint32_t thresh, float keep_scale,
+                                                                        const uint64_t* __restrict__ seed, int nprob) {
+    const AttFwdSet& a = blockIdx.y ? a1 : a0;
+    attention_small_fwd_body<true>(a.q, ldq, a.k, ldk, a.v, ldv, a.o, ldo, a.p_out, 0, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
+                                   a.offset, nprob, nullptr, &full);
+}
 
 // SHARED_KV: cross-attention of a run with several segments.  All segments of one (batch, head) share the key /
 // value rows, so they are the wavefronts of ONE workgroup (blockDim = 64 * nseg, grid = B * H): each adds its dK / dV
 // tile into a 16 KB LDS image (ds_add_f32) and the workgroup stores the sums with plain 16-byte stores - no global
 // atomics (they cost 33 / 70 us per launch at 2 / 5 segments against 12 us for one), no zero-filled output.
-template <bool SHARED_KV>
-__global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_kernel(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
+template <bool SHARED_KV, bool ENDS>
+__device__ __forceinline__ void attention_small_bwd_body(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
                                                                   long ldq, const float* __restrict__ k, long ldk,
                                                                   const float* __restrict__ v, long ldv, const float* __restrict__ p,
                                                                   float* __restrict__ dq, long lddq, float* __restrict__ dk, long lddk,
                                                                   float* __restrict__ dv, long lddv, int B, int H, SegDesc segs,
                                                                   int Lk_fixed, float scale, uint32_t thresh, float keep_scale,
                                                                   const uint64_t* __restrict__ seed, uint64_t offset, int nprob,
-                                                                  unsigned long long* stamp) {
+                                                                  unsigned long long* stamp, const SegDesc* full) {
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
     sbl_stamp_begin(stamp);
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];      // SHARED_KV: [wavefront][dV | dK][32][64] partial tiles
@@ -444,7 +468,7 @@ __global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_ker
   for (int sidx = (int)(threadIdx.x >> 6), pass = 0; pass == 0 || (SHARED_KV && sidx < segs.nseg); sidx += nwv, ++pass) {
     const int prob = SHARED_KV ? sidx * (B * H) + (int)blockIdx.x : (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (!SHARED_KV && prob >= nprob) return;
-    const SmallProb P = small_prob(prob, B, H, segs, Lk_fixed);
+    const SmallProb P = small_prob<ENDS>(prob, B, H, segs, Lk_fixed, full);
     const int Lq = P.Lq, Lk = P.Lk;
     const int NT = Lk > 16 ? 2 : 1;
     const float* qb = q + P.qrow * ldq + P.h * 64;
@@ -474,7 +498,7 @@ __global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_ker
                     if (n < Lq && j < Lk) {
                         pv = pg[(long)n * Lk + j];
                         dp = acc[r];
-                        if (thresh) dp = sbl_keep(sd, offset, (uint64_t)P.pbase + (uint64_t)n * Lk + j, thresh) ? dp * keep_scale : 0.f;
+                        if (thresh) dp = sbl_keep(sd, offset, (uint64_t)P.mbase + (uint64_t)(n * P.mstep) * Lk + j, thresh) ? dp * keep_scale : 0.f;
                     }
                     pT[t][r] = pv;
                     dpT[t][r] = dp;
@@ -536,7 +560,7 @@ __global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_ker
                         dp = acc[r];
                         pd = pv;
                         if (thresh) {
-                            const bool keep = sbl_keep(sd, offset, (uint64_t)P.pbase + (uint64_t)i * Lk + j, thresh);
+                            const bool keep = sbl_keep(sd, offset, (uint64_t)P.mbase + (uint64_t)(i * P.mstep) * Lk + j, thresh);
                             dp = keep ? dp * keep_scale : 0.f;
                             pd = keep ? pv * keep_scale : 0.f;
                         }
@@ -633,6 +657,29 @@ __global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_ker
         }
     }
     sbl_stamp_end(stamp);
+}
+template <bool SHARED_KV>
+__global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_bwd_kernel(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
+                                                                  long ldq, const float* __restrict__ k, long ldk,
+                                                                  const float* __restrict__ v, long ldv, const float* __restrict__ p,
+                                                                  float* __restrict__ dq, long lddq, float* __restrict__ dk, long lddk,
+                                                                  float* __restrict__ dv, long lddv, int B, int H, SegDesc segs,
+                                                                  int Lk_fixed, float scale, uint32_t thresh, float keep_scale,
+                                                                  const uint64_t* __restrict__ seed, uint64_t offset, int nprob,
+                                                                  unsigned long long* stamp) {
+    attention_small_bwd_body<SHARED_KV, false>(dout, lddo, q, ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, segs, Lk_fixed, scale,
+                                               thresh, keep_scale, seed, offset, nprob, stamp, nullptr);
+}
+template <bool SHARED_KV>
+__global__ __launch_bounds__(SHARED_KV ? 512 : 256) void attention_small_ends_bwd_kernel(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
+                                                                  long ldq, const float* __restrict__ k, long ldk,
+                                                                  const float* __restrict__ v, long ldv, const float* __restrict__ p,
+                                                                  float* __restrict__ dq, long lddq, float* __restrict__ dk, long lddk,
+                                                                  float* __restrict__ dv, long lddv, int B, int H, SegDesc segs, SegDesc full,
+                                                                  int Lk_fixed, float scale, uint32_t thresh, float keep_scale,
+                                                                  const uint64_t* __restrict__ seed, uint64_t offset, int nprob) {
+    attention_small_bwd_body<SHARED_KV, true>(dout, lddo, q, ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, segs, Lk_fixed, scale,
+                                              thresh, keep_scale, seed, offset, nprob, nullptr, &full);
 }
 
 // Self-attention over 17..32 rows (the encoder's 29 frames): two query tiles of <= 16 rows per (batch, head), each a
@@ -807,6 +854,67 @@ extern "C" int sbl_attention_seg_bwd(const float* dout, long lddo, const float* 
                        v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, d, Lk_fixed, scale,
                        drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, offset, sz, sbl_next_stamp_slot(SBL_KID_ATTENTION));
     SBL_LAUNCH_CHECK("sbl_attention_bwd");
+    return 0;
+}
+
+// ---- cross-attention of the last decoder layer's compact "ends" rows (sbl_common.h).  seg_L = the FULL prefix lengths of the
+// ragged batch; q / o (dout / dq) hold B * sum(min(2, seg_L)) rows - the queries at positions 0 and seg_L[s]-1 of every
+// sequence -, p the compact probability blocks (H*B, min(2, L), Lk) back to back, and every attention-dropout decision is the
+// one sbl_attention_seg2_fwd / sbl_attention_seg_bwd over the full batch draw for the same (segment, head, sequence, position,
+// key).  Keys / values as there (Lk_fixed rows per sequence, shared by the segments); built on the one-wavefront kernels, so
+// Lk_fixed <= 32.
+static int at_ends_check(const char* who, int B, int H, const int* seg_L, int nseg, int Lk_fixed, SegDesc& cs, SegDesc& fs) {
+    SBL_REQUIRE(B > 0 && H > 0 && Lk_fixed >= 1 && Lk_fixed <= 32, "%s: bad B=%d H=%d Lk=%d (1 <= Lk <= 32)", who, B, H, Lk_fixed);
+    SBL_REQUIRE(sbl_make_ends(cs, fs, seg_L, nseg, B, H, Lk_fixed) > 0, "%s: bad segment list (nseg=%d, 1..%d)", who, nseg, SBL_MAX_SEG);
+    for (int s = 0; s < nseg; ++s) SBL_REQUIRE(seg_L[s] <= 64, "%s: segment %d has L=%d (<= 64)", who, s, seg_L[s]);
+    SBL_REQUIRE((long)nseg * B * H < (1L << 30), "%s: too many problems", who);
+    return 0;
+}
+extern "C" int sbl_attention_ends2_fwd(const float* q0, const float* q1, long ldq, const float* k0, const float* k1, long ldk,
+                                       const float* v0, const float* v1, long ldv, float* o0, float* o1, long ldo, float* p_out0,
+                                       float* p_out1, int B, int H, const int* seg_L, int nseg, int Lk_fixed, float scale, float drop_p,
+                                       const uint64_t* seed, uint64_t offset0, uint64_t offset1, sbl_stream_t stream) {
+    SegDesc cs, fs;
+    if (int e = at_ends_check("sbl_attention_ends2_fwd", B, H, seg_L, nseg, Lk_fixed, cs, fs)) return e;
+    if (int e = at_check("sbl_attention_ends2_fwd", B, H, cs, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
+    SBL_REQUIRE(q0 && q1 && k0 && k1 && v0 && v1 && o0 && o1 && p_out0 && p_out1, "sbl_attention_ends2_fwd: null pointer");
+    SBL_REQUIRE(sbl_aligned16(q0) && sbl_aligned16(q1) && sbl_aligned16(k0) && sbl_aligned16(k1) && sbl_aligned16(v0) && sbl_aligned16(v1) &&
+                    sbl_aligned16(o0) && sbl_aligned16(o1), "sbl_attention_ends2_fwd: unaligned pointer");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_ends2_fwd: bad dropout args");
+    const int nprob = nseg * B * H;
+    AttFwdSet a0{q0, k0, v0, o0, p_out0, offset0}, a1{q1, k1, v1, o1, p_out1, offset1};
+    hipLaunchKernelGGL(attention_small2_ends_fwd_kernel, dim3(sbl_cdiv(nprob, 4), 2), dim3(256), 0, (hipStream_t)stream, a0, a1, ldq, ldk, ldv,
+                       ldo, B, H, cs, fs, Lk_fixed, scale, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed, nprob);
+    SBL_LAUNCH_CHECK("sbl_attention_ends2_fwd");
+    return 0;
+}
+extern "C" int sbl_attention_ends_bwd(const float* dout, long lddo, const float* q, long ldq, const float* k, long ldk, const float* v,
+                                      long ldv, const float* p, float* dq, long lddq, float* dk, long lddk, float* dv, long lddv, int B,
+                                      int H, const int* seg_L, int nseg, int Lk_fixed, float scale, float drop_p, const uint64_t* seed,
+                                      uint64_t offset, sbl_stream_t stream) {
+    SegDesc cs, fs;
+    if (int e = at_ends_check("sbl_attention_ends_bwd", B, H, seg_L, nseg, Lk_fixed, cs, fs)) return e;
+    if (int e = at_check("sbl_attention_ends_bwd", B, H, cs, Lk_fixed, ldq, ldk, ldv, lddo)) return e;
+    SBL_REQUIRE(lddq >= H * 64 && lddk >= H * 64 && lddv >= H * 64 && lddq % 4 == 0 && lddk % 4 == 0 && lddv % 4 == 0,
+                "sbl_attention_ends_bwd: gradient row strides must be multiples of 4 floats and at least H*64");
+    SBL_REQUIRE(dout && q && k && v && p && dq && dk && dv && sbl_aligned16(dout) && sbl_aligned16(q) && sbl_aligned16(k) && sbl_aligned16(v) &&
+                    sbl_aligned16(dq) && sbl_aligned16(dk) && sbl_aligned16(dv), "sbl_attention_ends_bwd: null/unaligned pointer");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_ends_bwd: bad dropout args");
+    const int nprob = nseg * B * H;
+    const uint32_t thresh = drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u;
+    if (nseg > 1) {      // shared keys: one workgroup per (batch, head) sums the segments' dK / dV in LDS
+        const int nwv = nseg < 8 ? nseg : 8;
+        static bool set[64] = {false};
+        SBL_HIP(sbl_raise_lds_cap((const void*)attention_small_ends_bwd_kernel<true>, 8 * 16384, set));
+        hipLaunchKernelGGL(attention_small_ends_bwd_kernel<true>, dim3(B * H), dim3(64 * nwv), (size_t)nwv * 16384, (hipStream_t)stream, dout, lddo,
+                           q, ldq, k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, cs, fs, Lk_fixed, scale, thresh, 1.f / (1.f - drop_p),
+                           seed, offset, nprob);
+    } else {
+        hipLaunchKernelGGL(attention_small_ends_bwd_kernel<false>, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, dout, lddo, q, ldq,
+                           k, ldk, v, ldv, p, dq, lddq, dk, lddk, dv, lddv, B, H, cs, fs, Lk_fixed, scale, thresh, 1.f / (1.f - drop_p), seed,
+                           offset, nprob);
+    }
+    SBL_LAUNCH_CHECK("sbl_attention_ends_bwd");
     return 0;
 }
 

@@ -375,6 +375,123 @@ extern "C" int sbl_decoder_tail_fwd(const float* yf0, const float* yf1, const fl
     return 0;
 }
 
+// ------------------------------------------------------------------ last decoder layer: the two rows per sequence the tail reads
+// The stage tail above reads, of the last layer's output, only position L-1 of a direction and position 0 of the other one
+// (decoder.py:160-167), so everything of that layer behind the self-attention core runs on the compact "ends" batch of
+// sbl_common.h.  Three small movers: gather the end rows of full-layout tensors, put compact gradient rows back into a
+// full-layout tensor (all other rows zero), and the adjoint of the tail's fusion straight into the compact layout.
+struct EndsPair {
+    const float* src;
+    float* dst;
+};
+// dst_t (compact rows) = the end rows of src_t (full rows), t = blockIdx.y < 4
+__global__ __launch_bounds__(256) void ends_gather_kernel(EndsPair t0, EndsPair t1, EndsPair t2, EndsPair t3, int B, SegDesc cs, SegDesc fs,
+                                                          long crows, int D4) {
+    const EndsPair t = blockIdx.y == 0 ? t0 : (blockIdx.y == 1 ? t1 : (blockIdx.y == 2 ? t2 : t3));
+    const long n4 = crows * D4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % D4);
+        const long fr = sbl_ends_full_row(cs, fs, (int)(i / D4), B);
+        reinterpret_cast<float4*>(t.dst)[i] = reinterpret_cast<const float4*>(t.src)[fr * D4 + c];
+    }
+}
+extern "C" int sbl_ends_gather4(const float* src0, const float* src1, const float* src2, const float* src3, float* dst0, float* dst1,
+                                float* dst2, float* dst3, int B, const int* seg_L, int nseg, int D, sbl_stream_t stream) {
+    SegDesc cs, fs;
+    SBL_REQUIRE(B > 0 && D > 0 && D % 4 == 0, "sbl_ends_gather4: bad B=%d D=%d", B, D);
+    const long crows = sbl_make_ends(cs, fs, seg_L, nseg, B, 1, 1);
+    SBL_REQUIRE(crows > 0, "sbl_ends_gather4: bad segment list");
+    const float* src[4] = {src0, src1, src2, src3};
+    float* dst[4] = {dst0, dst1, dst2, dst3};
+    int nt = 0;
+    while (nt < 4 && src[nt]) ++nt;
+    SBL_REQUIRE(nt >= 1, "sbl_ends_gather4: no tensor");
+    for (int t = 0; t < 4; ++t) {
+        SBL_REQUIRE((t < nt) == (src[t] != nullptr) && (src[t] != nullptr) == (dst[t] != nullptr), "sbl_ends_gather4: tensors must be the first ones, each with its output");
+        SBL_REQUIRE(!src[t] || (sbl_aligned16(src[t]) && sbl_aligned16(dst[t]) && src[t] != dst[t]), "sbl_ends_gather4: unaligned or aliased");
+    }
+    hipLaunchKernelGGL(ends_gather_kernel, dim3(ew_grid(crows * D / 4), nt), dim3(256), 0, (hipStream_t)stream, EndsPair{src0, dst0},
+                       EndsPair{src1, dst1}, EndsPair{src2, dst2}, EndsPair{src3, dst3}, B, cs, fs, crows, D / 4);
+    SBL_LAUNCH_CHECK("sbl_ends_gather4");
+    return 0;
+}
+// dst_t (full rows) = src_t (compact rows) at the end rows, zero everywhere else: every full row is written once, so dst needs no
+// zero fill of its own.  t = blockIdx.y < 2
+__global__ __launch_bounds__(256) void ends_scatter_kernel(EndsPair t0, EndsPair t1, int B, SegDesc cs, SegDesc fs, long frows, int D4) {
+    const EndsPair t = blockIdx.y ? t1 : t0;
+    const long n4 = frows * D4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % D4);
+        const int r = (int)(i / D4);
+        const int s = sbl_seg_of_row(fs, r, B);
+        const int L = fs.L[s], Lc = cs.L[s], rr = r - fs.row_off[s];
+        const int b = rr / L, l = rr - b * L;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (l == 0 || l == L - 1) v = reinterpret_cast<const float4*>(t.src)[(cs.row_off[s] + (long)b * Lc + (l == 0 ? 0 : Lc - 1)) * D4 + c];
+        reinterpret_cast<float4*>(t.dst)[i] = v;
+    }
+}
+extern "C" int sbl_ends_scatter2(const float* src0, const float* src1, float* dst0, float* dst1, int B, const int* seg_L, int nseg, int D,
+                                 sbl_stream_t stream) {
+    SegDesc cs, fs;
+    SBL_REQUIRE(B > 0 && D > 0 && D % 4 == 0, "sbl_ends_scatter2: bad B=%d D=%d", B, D);
+    SBL_REQUIRE(sbl_make_ends(cs, fs, seg_L, nseg, B, 1, 1) > 0, "sbl_ends_scatter2: bad segment list");
+    long frows = 0;
+    for (int s = 0; s < nseg; ++s) frows += (long)B * seg_L[s];
+    SBL_REQUIRE(src0 && dst0 && (!src1 == !dst1), "sbl_ends_scatter2: null operand");
+    SBL_REQUIRE(sbl_aligned16(src0) && sbl_aligned16(dst0) && (!src1 || (sbl_aligned16(src1) && sbl_aligned16(dst1))) && src0 != dst0 && (!src1 || src1 != dst1),
+                "sbl_ends_scatter2: unaligned or aliased");
+    hipLaunchKernelGGL(ends_scatter_kernel, dim3(ew_grid(frows * D / 4), src1 ? 2 : 1), dim3(256), 0, (hipStream_t)stream, EndsPair{src0, dst0},
+                       EndsPair{src1, dst1}, B, cs, fs, frows, D / 4);
+    SBL_LAUNCH_CHECK("sbl_ends_scatter2");
+    return 0;
+}
+// Adjoint of the tail's fusion (A'[L-1] = A[L-1] + B[0], B'[L-1] = 2 B[L-1] + A[0]) from the heads' input gradients dlast_d
+// (nseg * B rows, step-major; either may be null = zero) to the compact gradients of the last layer's outputs:
+// dy_d(s, b, last) gets kf_d * dlast_d(s, b) with kf = 1 / 2 for l2r / r2l, dy_d(s, b, first) gets dlast_{1-d}(s, b); at L = 1
+// the one row is both.  Replaces a zero-filled full-layout buffer, sbl_gather_last_bwd and a full-row sbl_fusion_seg_bwd.
+__global__ __launch_bounds__(256) void ends_tail_bwd_kernel(const float* __restrict__ dlast0, const float* __restrict__ dlast1,
+                                                            float* __restrict__ dy0, float* __restrict__ dy1, int B, SegDesc cs, long crows,
+                                                            int D4) {
+    const int dir = blockIdx.y;
+    const float* own = dir ? dlast1 : dlast0;
+    const float* oth = dir ? dlast0 : dlast1;
+    float* dy = dir ? dy1 : dy0;
+    const float kf = dir ? 2.f : 1.f;
+    const long n4 = crows * D4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % D4);
+        const int r = (int)(i / D4);
+        const int s = sbl_seg_of_row(cs, r, B);
+        const int Lc = cs.L[s], rr = r - cs.row_off[s];
+        const int b = rr / Lc, k = rr - b * Lc;
+        const long sb = ((long)s * B + b) * D4 + c;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (k == Lc - 1 && own) {
+            const float4 a = reinterpret_cast<const float4*>(own)[sb];
+            v = make_float4(kf * a.x, kf * a.y, kf * a.z, kf * a.w);
+        }
+        if (k == 0 && oth) {
+            const float4 a = reinterpret_cast<const float4*>(oth)[sb];
+            v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+        }
+        reinterpret_cast<float4*>(dy)[i] = v;
+    }
+}
+extern "C" int sbl_ends_tail_bwd(const float* dlast0, const float* dlast1, float* dy0, float* dy1, int B, const int* seg_L, int nseg, int D,
+                                 sbl_stream_t stream) {
+    SegDesc cs, fs;
+    SBL_REQUIRE(B > 0 && D > 0 && D % 4 == 0, "sbl_ends_tail_bwd: bad B=%d D=%d", B, D);
+    const long crows = sbl_make_ends(cs, fs, seg_L, nseg, B, 1, 1);
+    SBL_REQUIRE(crows > 0, "sbl_ends_tail_bwd: bad segment list");
+    SBL_REQUIRE((dlast0 || dlast1) && dy0 && dy1 && dy0 != dy1, "sbl_ends_tail_bwd: null operand");
+    SBL_REQUIRE((!dlast0 || sbl_aligned16(dlast0)) && (!dlast1 || sbl_aligned16(dlast1)) && sbl_aligned16(dy0) && sbl_aligned16(dy1), "sbl_ends_tail_bwd: unaligned");
+    hipLaunchKernelGGL(ends_tail_bwd_kernel, dim3(ew_grid(crows * D / 4), 2), dim3(256), 0, (hipStream_t)stream, dlast0, dlast1, dy0, dy1, B, cs,
+                       crows, D / 4);
+    SBL_LAUNCH_CHECK("sbl_ends_tail_bwd");
+    return 0;
+}
+
 // ------------------------------------------------------------------ Decoder.preprocess, decoder.py:62-77
 // One thread per target row: strip IGNORE_ID keeping the order, <sos> in front of the input form, <eos> padding to maxlen in
 // both forms.  set = 0 / 1: the l2r / r2l targets of one step in one launch (torch's argsort + gather + where + fills were

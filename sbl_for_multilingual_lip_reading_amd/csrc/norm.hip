@@ -372,11 +372,10 @@ __device__ __forceinline__ void add_layernorm_fwd_rows(const float* __restrict__
                                                        float* __restrict__ y, float* __restrict__ mean,
                                                        float* __restrict__ rstd, int M, float eps, uint32_t thresh,
                                                        float keep_scale, const uint64_t* __restrict__ seed,
-                                                       uint64_t offset) {
+                                                       uint64_t offset, int row, long mask_row) {
     const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
-    const long o = (long)row * 512;
+    const long o = (long)row * 512, mo = mask_row * 512;      // mo: the row's place in the buffer the dropout mask is indexed by
     float v[8];
     *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(x + o + lane * 4);
     *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(x + o + 256 + lane * 4);
@@ -384,7 +383,7 @@ __device__ __forceinline__ void add_layernorm_fwd_rows(const float* __restrict__
         const uint64_t sd = *seed;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint64_t idx = (uint64_t)o + (k < 4 ? 0 : 256) + lane * 4 + (k & 3);
+            const uint64_t idx = (uint64_t)mo + (k < 4 ? 0 : 256) + lane * 4 + (k & 3);
             v[k] = sbl_keep(sd, offset, idx, thresh) ? v[k] * keep_scale : 0.f;
         }
     }
@@ -423,7 +422,8 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __r
                                                                 float* __restrict__ rstd, int M, float eps, uint32_t thresh,
                                                                 float keep_scale, const uint64_t* __restrict__ seed,
                                                                 uint64_t offset) {
-    add_layernorm_fwd_rows(x, res, gamma, beta, y, mean, rstd, M, eps, thresh, keep_scale, seed, offset);
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    add_layernorm_fwd_rows(x, res, gamma, beta, y, mean, rstd, M, eps, thresh, keep_scale, seed, offset, row, row);
 }
 // Two same-shape problems in one launch (the two decoder directions; blockIdx.y picks the operand set).
 struct LnFwdSet {
@@ -439,7 +439,18 @@ struct LnFwdSet {
 __global__ __launch_bounds__(256) void add_layernorm2_fwd_kernel(LnFwdSet a0, LnFwdSet a1, int M, float eps, uint32_t thresh,
                                                                  float keep_scale, const uint64_t* __restrict__ seed) {
     const LnFwdSet& a = blockIdx.y ? a1 : a0;
-    add_layernorm_fwd_rows(a.x, a.res, a.gamma, a.beta, a.y, a.mean, a.rstd, M, eps, thresh, keep_scale, seed, a.offset);
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    add_layernorm_fwd_rows(a.x, a.res, a.gamma, a.beta, a.y, a.mean, a.rstd, M, eps, thresh, keep_scale, seed, a.offset, row, row);
+}
+// The same on the compact "ends" rows of the last decoder layer (sbl_common.h): the mask of compact row r is the one the
+// full-layout launch draws for the row it stands for.
+__global__ __launch_bounds__(256) void add_layernorm2_ends_fwd_kernel(LnFwdSet a0, LnFwdSet a1, int M, int B, SegDesc cs, SegDesc fs, float eps,
+                                                                      uint32_t thresh, float keep_scale, const uint64_t* __restrict__ seed) {
+    const LnFwdSet& a = blockIdx.y ? a1 : a0;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;      // whole wavefront; no barrier in this kernel
+    add_layernorm_fwd_rows(a.x, a.res, a.gamma, a.beta, a.y, a.mean, a.rstd, M, eps, thresh, keep_scale, seed, a.offset, row,
+                           thresh ? sbl_ends_full_row(cs, fs, row, B) : (long)row);
 }
 
 // ------------------------------------------------------------------ last LayerNorm of a decoder layer + SBL fusion
@@ -511,13 +522,17 @@ __global__ __launch_bounds__(256) void add_layernorm2_fusion_fwd_kernel(LnFwdSet
 // dz = rstd*(gamma*dy - mean(gamma*dy) - xhat*mean(gamma*dy*xhat)); dgamma += dy*xhat, dbeta += dy (column sums:
 // each wave walks its rows keeping 8 per-lane partials, LDS-combined per block, then float atomics)
 #define SBL_LN_BWD_WAVES 8       // 512-thread workgroups: 8 waves x RW rows in flight per workgroup
-__global__ __launch_bounds__(64 * SBL_LN_BWD_WAVES) void add_layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                const float* __restrict__ res, const float* __restrict__ gamma,
-                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                float* __restrict__ dz, float* __restrict__ dx_drop,
-                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, int M,
-                                                                int rows_per_block, uint32_t thresh, float keep_scale,
-                                                                const uint64_t* __restrict__ seed, uint64_t offset) {
+// ENDS: the rows are the compact "ends" rows of the last decoder layer (sbl_common.h); the dropout mask of a row is indexed by
+// the full-layout row it stands for.
+template <bool ENDS>
+__device__ __forceinline__ void add_layernorm_bwd_body(const float* __restrict__ dy, const float* __restrict__ x,
+                                                       const float* __restrict__ res, const float* __restrict__ gamma,
+                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                       float* __restrict__ dz, float* __restrict__ dx_drop,
+                                                       float* __restrict__ dgamma, float* __restrict__ dbeta, int M,
+                                                       int rows_per_block, uint32_t thresh, float keep_scale,
+                                                       const uint64_t* __restrict__ seed, uint64_t offset, int B, const SegDesc* cs,
+                                                       const SegDesc* fs) {
     __shared__ float red[SBL_LN_BWD_WAVES][2][512];
     const uint64_t sd = thresh ? *seed : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -547,12 +562,15 @@ __global__ __launch_bounds__(64 * SBL_LN_BWD_WAVES) void add_layernorm_bwd_kerne
             const int row = rb + j;
             if (row >= r1) break;
             const long o = (long)row * 512;
+            long mo = o;
+            if constexpr (ENDS)
+                if (thresh) mo = sbl_ends_full_row(*cs, *fs, row, B) * 512;
             bool keep[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 keep[k] = true;
                 if (thresh) {
-                    keep[k] = sbl_keep(sd, offset, (uint64_t)o + (k < 4 ? 0 : 256) + lane * 4 + (k & 3), thresh);
+                    keep[k] = sbl_keep(sd, offset, (uint64_t)mo + (k < 4 ? 0 : 256) + lane * 4 + (k & 3), thresh);
                     v[j][k] = keep[k] ? v[j][k] * keep_scale : 0.f;
                 }
             }
@@ -602,6 +620,27 @@ __global__ __launch_bounds__(64 * SBL_LN_BWD_WAVES) void add_layernorm_bwd_kerne
         atomicAdd((which ? dbeta : dgamma) + c, t);
     }
 }
+__global__ __launch_bounds__(64 * SBL_LN_BWD_WAVES) void add_layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                const float* __restrict__ res, const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                float* __restrict__ dz, float* __restrict__ dx_drop,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, int M,
+                                                                int rows_per_block, uint32_t thresh, float keep_scale,
+                                                                const uint64_t* __restrict__ seed, uint64_t offset) {
+    add_layernorm_bwd_body<false>(dy, x, res, gamma, mean, rstd, dz, dx_drop, dgamma, dbeta, M, rows_per_block, thresh, keep_scale, seed,
+                                  offset, 0, nullptr, nullptr);
+}
+__global__ __launch_bounds__(64 * SBL_LN_BWD_WAVES) void add_layernorm_ends_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                const float* __restrict__ res, const float* __restrict__ gamma,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                                float* __restrict__ dz, float* __restrict__ dx_drop,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta, int M,
+                                                                int rows_per_block, uint32_t thresh, float keep_scale,
+                                                                const uint64_t* __restrict__ seed, uint64_t offset, int B, SegDesc cs,
+                                                                SegDesc fs) {
+    add_layernorm_bwd_body<true>(dy, x, res, gamma, mean, rstd, dz, dx_drop, dgamma, dbeta, M, rows_per_block, thresh, keep_scale, seed,
+                                 offset, B, &cs, &fs);
+}
 
 extern "C" int sbl_add_layernorm_fwd(const float* x, const float* res, const float* gamma, const float* beta, float* y,
                                      float* mean, float* rstd, int M, int D, float eps, float drop_p,
@@ -631,6 +670,31 @@ extern "C" int sbl_add_layernorm2_fwd(const float* x0, const float* x1, const fl
     hipLaunchKernelGGL(add_layernorm2_fwd_kernel, dim3(sbl_cdiv(M, 4), 2), dim3(256), 0, (hipStream_t)stream, a0, a1, M, eps,
                        drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed);
     SBL_LAUNCH_CHECK("sbl_add_layernorm2_fwd");
+    return 0;
+}
+
+/* sbl_add_layernorm2_fwd on the compact "ends" rows of the ragged stage seg_L (B sequences per segment, min(2, seg_L[s]) rows
+ * each: positions 0 and seg_L[s]-1); the dropout mask of every element is the one the full-layout launch over the stage's
+ * B * sum(seg_L) rows draws for it. */
+extern "C" int sbl_add_layernorm2_ends_fwd(const float* x0, const float* x1, const float* res0, const float* res1, const float* gamma0,
+                                           const float* gamma1, const float* beta0, const float* beta1, float* y0, float* y1,
+                                           float* mean0, float* mean1, float* rstd0, float* rstd1, int B, const int* seg_L, int nseg,
+                                           int D, float eps, float drop_p, const uint64_t* seed, uint64_t offset0, uint64_t offset1,
+                                           sbl_stream_t stream) {
+    SegDesc cs, fs;
+    SBL_REQUIRE(B > 0, "sbl_add_layernorm2_ends_fwd: B=%d", B);
+    const long M = sbl_make_ends(cs, fs, seg_L, nseg, B, 1, 1);
+    SBL_REQUIRE(M > 0 && M < (1L << 30), "sbl_add_layernorm2_ends_fwd: bad segment list");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_add_layernorm2_ends_fwd: bad dropout args");
+    SBL_REQUIRE(D == 512, "sbl_add_layernorm2_ends_fwd: D=%d (this build is specialised for d_model=512)", D);
+    SBL_REQUIRE(x0 && x1 && gamma0 && gamma1 && beta0 && beta1 && y0 && y1 && mean0 && mean1 && rstd0 && rstd1 && (!res0 == !res1),
+                "sbl_add_layernorm2_ends_fwd: bad args");
+    SBL_REQUIRE(sbl_aligned16(x0) && sbl_aligned16(x1) && sbl_aligned16(y0) && sbl_aligned16(y1) && (!res0 || (sbl_aligned16(res0) && sbl_aligned16(res1))) &&
+                    sbl_aligned16(gamma0) && sbl_aligned16(gamma1) && sbl_aligned16(beta0) && sbl_aligned16(beta1), "sbl_add_layernorm2_ends_fwd: unaligned");
+    LnFwdSet a0{x0, res0, gamma0, beta0, y0, mean0, rstd0, offset0}, a1{x1, res1, gamma1, beta1, y1, mean1, rstd1, offset1};
+    hipLaunchKernelGGL(add_layernorm2_ends_fwd_kernel, dim3(sbl_cdiv(M, 4), 2), dim3(256), 0, (hipStream_t)stream, a0, a1, (int)M, B, cs, fs,
+                       eps, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u, 1.f / (1.f - drop_p), seed);
+    SBL_LAUNCH_CHECK("sbl_add_layernorm2_ends_fwd");
     return 0;
 }
 
@@ -682,6 +746,33 @@ extern "C" int sbl_add_layernorm_bwd(const float* dy, const float* x, const floa
                        gamma, mean, rstd, dz, dx_drop, dgamma, dbeta, M, rpb, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u,
                        1.f / (1.f - drop_p), seed, offset);
     SBL_LAUNCH_CHECK("sbl_add_layernorm_bwd");
+    return 0;
+}
+
+/* sbl_add_layernorm_bwd on the compact "ends" rows of the ragged batch seg_L (see sbl_add_layernorm2_ends_fwd): same launch
+ * shape rule, the masks of the full layout. */
+extern "C" int sbl_add_layernorm_ends_bwd(const float* dy, const float* x, const float* res, const float* gamma, const float* mean,
+                                          const float* rstd, float* dz, float* dx_drop, float* dgamma, float* dbeta, int B,
+                                          const int* seg_L, int nseg, int D, float drop_p, const uint64_t* seed, uint64_t offset,
+                                          sbl_stream_t stream) {
+    SegDesc cs, fs;
+    SBL_REQUIRE(B > 0, "sbl_add_layernorm_ends_bwd: B=%d", B);
+    const long M = sbl_make_ends(cs, fs, seg_L, nseg, B, 1, 1);
+    SBL_REQUIRE(M > 0 && M < (1L << 30), "sbl_add_layernorm_ends_bwd: bad segment list");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_add_layernorm_ends_bwd: bad dropout args");
+    SBL_REQUIRE(!dx_drop || sbl_aligned16(dx_drop), "sbl_add_layernorm_ends_bwd: dx_drop unaligned");
+    SBL_REQUIRE(D == 512, "sbl_add_layernorm_ends_bwd: D=%d", D);
+    SBL_REQUIRE(dy && x && gamma && mean && rstd && dz && dgamma && dbeta, "sbl_add_layernorm_ends_bwd: bad args");
+    SBL_REQUIRE(sbl_aligned16(dy) && sbl_aligned16(x) && sbl_aligned16(dz) && (!res || sbl_aligned16(res)) && sbl_aligned16(gamma), "sbl_add_layernorm_ends_bwd: unaligned");
+    constexpr int rows_trip = SBL_LN_BWD_WAVES * 2;
+    int blocks = sbl_cdiv(M, 2 * rows_trip);
+    if (blocks > 256) blocks = 256;
+    if (blocks < 1) blocks = 1;
+    const int rpb = sbl_cdiv(sbl_cdiv(M, blocks), rows_trip) * rows_trip;
+    hipLaunchKernelGGL(add_layernorm_ends_bwd_kernel, dim3(sbl_cdiv(M, rpb)), dim3(64 * SBL_LN_BWD_WAVES), 0, (hipStream_t)stream, dy, x, res,
+                       gamma, mean, rstd, dz, dx_drop, dgamma, dbeta, (int)M, rpb, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u,
+                       1.f / (1.f - drop_p), seed, offset, B, cs, fs);
+    SBL_LAUNCH_CHECK("sbl_add_layernorm_ends_bwd");
     return 0;
 }
 

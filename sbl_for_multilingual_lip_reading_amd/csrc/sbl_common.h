@@ -96,6 +96,26 @@ __device__ __forceinline__ int sbl_seg_of_row(const SegDesc& d, int r, int B) {
     return s;
 }
 
+// ---- "ends" layout of the last decoder layer: after its self-attention only two rows per sequence are ever read (position 0
+// and position L-1: the stage tail's A'[L-1] = A[L-1] + B[0], decoder.py:160-167), so the sub-layers behind the attention core
+// run on a compact batch.  Segment s holds B sequences of Lc = min(2, L[s]) rows in (b, k) order, k = 0 -> position 0,
+// k = Lc-1 -> position L-1; compact row (s, b, k) stands for full row full.row_off[s] + b*L + k*(L-1).  Dropout masks stay
+// functions of the FULL-layout element index, so the compact kernels carry both descriptors.
+// host: compact descriptor `c` (lengths min(2, L)) and full descriptor `f` of the same segments; returns the compact rows
+static inline long sbl_make_ends(SegDesc& c, SegDesc& f, const int* seg_L, int nseg, int B, int H, int Lk_fixed) {
+    if (sbl_make_segs(f, seg_L, nseg, B, H, Lk_fixed) < 0) return -1;
+    int lc[SBL_MAX_SEG];
+    for (int s = 0; s < nseg; ++s) lc[s] = seg_L[s] < 2 ? seg_L[s] : 2;
+    return sbl_make_segs(c, lc, nseg, B, H, Lk_fixed);
+}
+// device: the full-layout row that compact row r stands for
+__device__ __forceinline__ long sbl_ends_full_row(const SegDesc& c, const SegDesc& f, int r, int B) {
+    const int s = sbl_seg_of_row(c, r, B);
+    const int Lc = c.L[s], L = f.L[s], j = r - c.row_off[s];
+    const int b = j / Lc, k = j - b * Lc;
+    return f.row_off[s] + (long)b * L + (long)k * (L - 1);
+}
+
 static inline int sbl_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool sbl_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 

@@ -810,25 +810,30 @@ def project_kv_block(x, mods):
     return lin, kv, kv.split(lin.N // len(mods), 1)
 
 
-def ln_bwd(dy, o, res, ln, mean, rstd, drop_p, seed, off, separate_do):
+def ln_bwd(dy, o, res, ln, mean, rstd, drop_p, seed, off, separate_do, ends=None):
     """Adjoint of y = LayerNorm(dropout(o) + res) -> (dz, do): dz = gradient of the residual `res` (of the sum when res is
     None), do = gradient of the pre-dropout o; dgamma / dbeta accumulate into ln[2] / ln[3].  do is a buffer of its own with
     dropout, and whenever the caller says so (`separate_do`): callers go on to accumulate the sub-layer's input gradient
     into dz in place, so a weight-gradient GEMM that is issued later (a deferring sink) must not find do aliased to it.
-    Otherwise do IS dz."""
+    Otherwise do IS dz.  ends = (B, segL): the rows are the compact "ends" rows of that ragged batch (include/sbl_hip.h) and
+    the masks those of its full layout."""
     M, D = dy.shape
     dz = _new(dy, M, D)
     do = _new(dy, M, D) if separate_do or drop_p > 0 else None
-    call("sbl_add_layernorm_bwd", _p(dy), _p(o), _p(res), _p(ln[0]), _p(mean), _p(rstd), _p(dz), _p(do), _p(ln[2]), _p(ln[3]),
-         M, D, drop_p, _p(seed) if drop_p > 0 else None, off, _s())
+    if ends is None:
+        call("sbl_add_layernorm_bwd", _p(dy), _p(o), _p(res), _p(ln[0]), _p(mean), _p(rstd), _p(dz), _p(do), _p(ln[2]), _p(ln[3]),
+             M, D, drop_p, _p(seed) if drop_p > 0 else None, off, _s())
+    else:
+        call("sbl_add_layernorm_ends_bwd", _p(dy), _p(o), _p(res), _p(ln[0]), _p(mean), _p(rstd), _p(dz), _p(do), _p(ln[2]), _p(ln[3]),
+             ends[0], *_segs(ends[1]), D, drop_p, _p(seed) if drop_p > 0 else None, off, _s())
     return dz, (dz if do is None else do)
 
 
-def _out_ln_bwd(h, dy, a, o, res, mean, rstd, seed, off, separate_do, sink, relu_mask=None):
+def _out_ln_bwd(h, dy, a, o, res, mean, rstd, seed, off, separate_do, sink, relu_mask=None, ends=None):
     """Adjoint of out_ln_fwd -> (dz = gradient of res, da = gradient of a; `relu_mask` = a when a is a ReLU's output: its
     adjoint is fused into the GEMM epilogue)."""
     lin = h.out
-    dz, do = ln_bwd(dy, o, res, h.ln, mean, rstd, h.drop_p, seed, off, separate_do)
+    dz, do = ln_bwd(dy, o, res, h.ln, mean, rstd, h.drop_p, seed, off, separate_do, ends)
     sink(lin, do, a)
     M = dy.size(0)
     da = _new(dy, M, lin.K)
@@ -842,29 +847,39 @@ def _lin_bwd(lin, dY, x, dx, sink):
     gemm(0, 0, x.size(0), lin.K, lin.N, dY, lin.N, lin.w, lin.K, dx, lin.K, accumulate=1)
 
 
-def attn_bwd(a, dy, x, acts, B, segL, kv, seed, off_a, off_o, separate_do, sink, dkv=None):
-    """Adjoint of attn_fwd (acts = what it returned) -> (dx, dkv).  Cross-attention: dkv (B * Lk, 2 * H * 64) is written,
-    not accumulated (several segments share the keys / values: their dK / dV contributions are summed inside the call);
-    allocated when not given, a column block of a wider buffer is fine."""
-    qkv, att, p, o, mean, rstd = acts
+def attn_core_bwd(a, dx, datt, x, qkv, p, B, segL, kv, seed, off_a, sink, dkv=None, ends=False):
+    """The attention core and input projection half of attn_bwd: datt = gradient of the core's output, dx = the residual
+    gradient of x, which the input projection's adjoint is accumulated into -> (dx, dkv).  ends: cross-attention of the compact
+    "ends" queries of the ragged batch segL (include/sbl_hip.h)."""
     HD = a.H * 64
-    dx, datt = _out_ln_bwd(a, dy, att, o, x, mean, rstd, seed, off_o, separate_do, sink)
-    dq = _new(dy, x.size(0), a.inp.N)                  # self-attention: [dQ | dK | dV]
+    dq = _new(datt, x.size(0), a.inp.N)                  # self-attention: [dQ | dK | dV]
     if kv is None:
+        assert not ends
         k, v, ldk, dk, dv, ldd, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, dq[:, HD:], dq[:, 2 * HD:], 3 * HD, 0
     else:
-        dkv = _new(dy, kv.size(0), 2 * HD) if dkv is None else dkv
+        dkv = _new(datt, kv.size(0), 2 * HD) if dkv is None else dkv
         k, v, ldk, dk, dv, ldd, Lk = kv, kv[:, HD:], _rows(kv)[1], dkv, dkv[:, HD:], _rows(dkv)[1], kv.size(0) // B
-    call("sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(p), _p(dq), a.inp.N, _p(dk), ldd,
-         _p(dv), ldd, B, a.H, *_segs(segL), Lk, 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+    call("sbl_attention_ends_bwd" if ends else "sbl_attention_seg_bwd", _p(datt), HD, _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(p),
+         _p(dq), a.inp.N, _p(dk), ldd, _p(dv), ldd, B, a.H, *_segs(segL), Lk, 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None,
+         off_a, _s())
     _lin_bwd(a.inp, dq, x, dx, sink)
     return dx, dkv
 
 
-def ffn_bwd(f, dy, x, acts, seed, off, separate_do, sink):
-    """Adjoint of ffn_fwd (acts = what it returned) -> dx."""
+def attn_bwd(a, dy, x, acts, B, segL, kv, seed, off_a, off_o, separate_do, sink, dkv=None, ends=False):
+    """Adjoint of attn_fwd (acts = what it returned) -> (dx, dkv).  Cross-attention: dkv (B * Lk, 2 * H * 64) is written,
+    not accumulated (several segments share the keys / values: their dK / dV contributions are summed inside the call);
+    allocated when not given, a column block of a wider buffer is fine.  ends: cross-attention whose rows (dy, x, acts) are
+    the compact "ends" rows of the ragged batch segL."""
+    qkv, att, p, o, mean, rstd = acts
+    dx, datt = _out_ln_bwd(a, dy, att, o, x, mean, rstd, seed, off_o, separate_do, sink, ends=(B, segL) if ends else None)
+    return attn_core_bwd(a, dx, datt, x, qkv, p, B, segL, kv, seed, off_a, sink, dkv, ends)
+
+
+def ffn_bwd(f, dy, x, acts, seed, off, separate_do, sink, ends=None):
+    """Adjoint of ffn_fwd (acts = what it returned) -> dx.  ends = (B, segL): compact "ends" rows (ln_bwd)."""
     h, o, mean, rstd = acts
-    dx, dh = _out_ln_bwd(f, dy, h, o, x, mean, rstd, seed, off, separate_do, sink, relu_mask=h)
+    dx, dh = _out_ln_bwd(f, dy, h, o, x, mean, rstd, seed, off, separate_do, sink, relu_mask=h, ends=ends)
     _lin_bwd(f.inp, dh, x, dx, sink)
     return dx
 

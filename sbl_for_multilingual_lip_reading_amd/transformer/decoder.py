@@ -26,6 +26,19 @@ def stages_of(coins, maxlen):
     return stages
 
 
+def ends_rows(n_seq, seg_lens, row0=0):
+    """Compact-to-full row map of the last decoder layer's "ends" layout (decoder_stages.py): for the ragged batch whose
+    segment s holds n_seq sequences of length seg_lens[s] (full rows from row0 on, (b, l) order) the full row of every compact
+    row.  Segment s keeps min(2, L) rows per sequence in (b, k) order: k = 0 is position 0, k = 1 is position L-1 - the two
+    rows the heads read after the last fusion - and the L = 1 row is both."""
+    rows = []
+    for L in seg_lens:
+        for b in range(n_seq):
+            rows.extend(row0 + b * L + k * (L - 1) for k in range(min(2, L)))
+        row0 += n_seq * L
+    return rows
+
+
 class Decoder(nn.Module):
     ''' Two n_layers-deep decoders, left-to-right and right-to-left, that attend to the same encoder output and swap
     information after every layer; 16 greedy / teacher-forced steps each (decoder.py:16-191, 301-385).
@@ -90,6 +103,7 @@ class Decoder(nn.Module):
         self.tgt_word_prj_r2l = nn.Linear(512, 58, bias=False)
 
         self.batched_backward = True     # one stage-batched backward over all 16 steps (decoder_stages.py) when possible
+        self.last_layer_ends_only = True # the last layer computes, behind its self-attention, only the two rows per sequence the heads read
         self.two_streams = True          # run the two directions' layers on two HIP streams (joined before each fusion)
         self.batch_teacher_runs = True   # batch the steps of a teacher-forced run (see class docstring)
         self.coins_dev = None            # optional device int32[16]: 1 = feed own argmax (graph replay, per-step schedule)

@@ -3,7 +3,8 @@
 Forward has to run stage by stage: a stage (a maximal run of teacher-forced steps, decoder.stages_of) needs the
 previous stage's argmax token (decoder.py:173-186).  Backward has no such dependency - tokens are not differentiable -
 so the backward of ALL 16 steps is one ragged batch: per layer and direction one LayerNorm / attention / GEMM launch
-over the N*136 rows of every step, instead of one per stage.  The dependent chain shrinks from
+over the N*136 rows of every step (the N*31 end rows behind the last layer's self-attention, see below), instead of one per
+stage.  The dependent chain shrinks from
 11 kernels x 6 layers x (1 + #own-argmax coins) to 11 x 6, and its GEMMs are 4352-row products instead of 100-1500.
 
 To make that possible every stage's forward writes its activations into row ranges of per-layer buffers laid out
@@ -17,6 +18,19 @@ regenerates exactly the masks of the forward with plain whole-buffer indices.
 
 The backward of a layer is ops.ffn_bwd / ops.attn_bwd (what the per-stage tape's MHAFn / FFNFn run) over these buffers, with a
 sink that collects the weight gradients for one grouped launch; only the paired forward is a launch sequence of this file.
+
+The last layer runs on its "ends" rows (Decoder.last_layer_ends_only).  Of its output a step reads two rows per sequence:
+the stage tail forms A'[L-1] = A[L-1] + B[0] and B'[L-1] = 2 B[L-1] + A[0] (decoder.py:160-167), so every other row has a
+gradient of exactly zero.  Its QKV product and self-attention core still cover all rows (the two surviving queries attend to
+every key); one gather then takes positions 0 and L-1 of att and of the residual x into a compact layout - segment t keeps
+min(2, t+1) rows per sequence in (b, k) order, N*31 rows instead of N*136 (decoder.ends_rows is the map) - and the
+out-projection, the cross-attention sub-layer and the feed-forward sub-layer run on those rows through the same entry points
+with a smaller M (sbl_*_ends_* for the LayerNorm and attention kernels, which draw every dropout decision from the element's
+place in the FULL layout: masks, and so results, are those of the full-row computation).  Backward mirrors it: a tail adjoint
+writes the compact dy from the heads' gradients, the sub-layer adjoints run compact, one scatter writes the full-size datt and residual
+gradient (their end rows, zero everywhere else: no separate zero fill), and the self-attention core and QKV adjoints run on all rows.
+Off, or with more than 32 encoder frames (the compact cross-attention is built on the one-wavefront kernels) = every launch of
+the last layer covers all rows, as in the other layers.
 
 Used by Decoder.forward when gradients accumulate into persistent buffers (dp.FlatModel) and the coins are known on
 the host (supported() has the full list); every other case keeps the per-stage tape (Decoder._run).  Same numbers as that
@@ -94,15 +108,27 @@ class DecoderStagesFn(torch.autograd.Function):
         training = dec.training
         p_emb = dec.dropout.p if training else 0.0
 
+        # the last layer's "ends" layout: behind its self-attention core only positions 0 and L-1 of every sequence are computed
+        # (module docstring); segment t keeps min(2, t+1) rows per sequence.  (The compact cross-attention is built on the
+        # one-wavefront kernels: at most 32 key rows.)
+        ends = bool(dec.last_layer_ends_only) and T <= 32
+        crow = [len(_decoder.ends_rows(N, range(1, t + 1))) for t in range(ML + 1)]    # compact row offsets
+        pec_off = [H * T * c for c in crow]                                            # compact cross-attention probabilities
+        Rc = crow[ML]
+
         E = lambda *shape: ops._new(enc_out, *shape)      # noqa: E731
         # ---- all-stage buffers
         B_ = [[None] * nl for _ in (0, 1)]
         for d in (0, 1):
             for n in range(nl):
-                B_[d][n] = dict(x=E(R, D), qkv=E(R, 3 * HD), att=E(R, HD), ps=E(ps_off[ML]), o_s=E(R, D), mu_s=E(R), rs_s=E(R), y_s=E(R, D),
-                                q=E(R, HD), att2=E(R, HD), pe=E(pe_off[ML]), o_e=E(R, D), mu_e=E(R), rs_e=E(R), y_e=E(R, D),
-                                h=E(R, F_), o_f=E(R, D), mu_f=E(R), rs_f=E(R), y_f=E(R, D), kv=None,
+                e = ends and n == nl - 1
+                Z, Zp = (Rc, pec_off[ML]) if e else (R, pe_off[ML])      # rows behind the self-attention core
+                B_[d][n] = dict(x=E(R, D), qkv=E(R, 3 * HD), att=E(R, HD), ps=E(ps_off[ML]), o_s=E(Z, D), mu_s=E(Z), rs_s=E(Z), y_s=E(Z, D),
+                                q=E(Z, HD), att2=E(Z, HD), pe=E(Zp), o_e=E(Z, D), mu_e=E(Z), rs_e=E(Z), y_e=E(Z, D),
+                                h=E(Z, F_), o_f=E(Z, D), mu_f=E(Z), rs_f=E(Z), y_f=E(Z, D), kv=None,
                                 off=[st.next_offset() for _ in range(5)] if training else [0] * 5)
+                if e:
+                    B_[d][n].update(x_c=E(Rc, D), att_c=E(Rc, HD))      # the end rows of x and att
         off_emb = [st.next_offset() if p_emb > 0 else 0 for _ in (0, 1)]
         last = [E(ML * N, D), E(ML * N, D)]
         pred = [E(ML * N, V), E(ML * N, V)]
@@ -140,21 +166,40 @@ class DecoderStagesFn(torch.autograd.Function):
                  3 * HD, _p(sl(b0, "att")), _p(sl(b1, "att")), HD, b0["ps"].data_ptr() + 4 * ps_off[i0], b1["ps"].data_ptr() + 4 * ps_off[i0],
                  1 if n == 0 else 0, N, H, seg_arr, nseg, 0, 0.125, s0.drop_p, sp if s0.drop_p > 0 else None,
                  _fold(b0["off"][0], ps_off[i0]), _fold(b1["off"][0], ps_off[i0]), ops._s())
-            ops.gemm2(M, D, HD, sl(b0, "att"), sl(b1, "att"), HD, s0.out.w, s1.out.w, HD, sl(b0, "o_s"), sl(b1, "o_s"), D, s0.out.b, s1.out.b)
+            # from here on the last layer runs on its end rows: one gather of att and of the residual x, both directions
+            e = ends and n == nl - 1
+            att_k, x_k = "att", "x"
+            if e:
+                c0, c1 = crow[i0], crow[i0 + nseg]
+                M = c1 - c0
+                call("sbl_ends_gather4", _p(sl(b0, "att")), _p(sl(b1, "att")), _p(sl(b0, "x")), _p(sl(b1, "x")), _p(b0["att_c"][c0:c1]),
+                     _p(b1["att_c"][c0:c1]), _p(b0["x_c"][c0:c1]), _p(b1["x_c"][c0:c1]), N, seg_arr, nseg, D, ops._s())
+                sl = lambda b, k: b[k][c0:c1]      # noqa: E731
+                att_k, x_k = "att_c", "x_c"
+            ops.gemm2(M, D, HD, sl(b0, att_k), sl(b1, att_k), HD, s0.out.w, s1.out.w, HD, sl(b0, "o_s"), sl(b1, "o_s"), D, s0.out.b, s1.out.b)
 
             def ln2(o, res, y, mu, rs, ln0, ln1, drop_p, k):
-                call("sbl_add_layernorm2_fwd", _p(sl(b0, o)), _p(sl(b1, o)), _p(sl(b0, res)), _p(sl(b1, res)), _p(ln0[0]), _p(ln1[0]),
+                # (masks are indexed by the full layout either way: the ends kernel maps its rows back, same folded offset)
+                call("sbl_add_layernorm2_ends_fwd" if e else "sbl_add_layernorm2_fwd",
+                     _p(sl(b0, o)), _p(sl(b1, o)), _p(sl(b0, res)), _p(sl(b1, res)), _p(ln0[0]), _p(ln1[0]),
                      _p(ln0[1]), _p(ln1[1]), _p(sl(b0, y)), _p(sl(b1, y)), _p(sl(b0, mu)), _p(sl(b1, mu)), _p(sl(b0, rs)), _p(sl(b1, rs)),
-                     M, D, ln0[4], drop_p, sp if drop_p > 0 else None, _fold(b0["off"][k], r0 * D), _fold(b1["off"][k], r0 * D), ops._s())
+                     *((N, seg_arr, nseg) if e else (M,)), D, ln0[4], drop_p, sp if drop_p > 0 else None, _fold(b0["off"][k], r0 * D),
+                     _fold(b1["off"][k], r0 * D), ops._s())
 
-            ln2("o_s", "x", "y_s", "mu_s", "rs_s", s0.ln, s1.ln, s0.drop_p, 1)
+            ln2("o_s", x_k, "y_s", "mu_s", "rs_s", s0.ln, s1.ln, s0.drop_p, 1)
             # cross-attention sub-layer
             ops.gemm2(M, HD, D, sl(b0, "y_s"), sl(b1, "y_s"), D, e0.inp.w, e1.inp.w, D, sl(b0, "q"), sl(b1, "q"), HD, e0.inp.b, e1.inp.b)
             kv0, kv1 = b0["kv"], b1["kv"]
-            call("sbl_attention_seg2_fwd", _p(sl(b0, "q")), _p(sl(b1, "q")), HD, _p(kv0), _p(kv1), ldkv, _p(kv0[:, HD:]), _p(kv1[:, HD:]), ldkv,
-                 _p(sl(b0, "att2")), _p(sl(b1, "att2")), HD, b0["pe"].data_ptr() + 4 * pe_off[i0], b1["pe"].data_ptr() + 4 * pe_off[i0],
-                 0, N, H, seg_arr, nseg, T, 0.125, e0.drop_p, sp if e0.drop_p > 0 else None,
-                 _fold(b0["off"][2], pe_off[i0]), _fold(b1["off"][2], pe_off[i0]), ops._s())
+            if e:
+                call("sbl_attention_ends2_fwd", _p(sl(b0, "q")), _p(sl(b1, "q")), HD, _p(kv0), _p(kv1), ldkv, _p(kv0[:, HD:]), _p(kv1[:, HD:]), ldkv,
+                     _p(sl(b0, "att2")), _p(sl(b1, "att2")), HD, b0["pe"].data_ptr() + 4 * pec_off[i0], b1["pe"].data_ptr() + 4 * pec_off[i0],
+                     N, H, seg_arr, nseg, T, 0.125, e0.drop_p, sp if e0.drop_p > 0 else None,
+                     _fold(b0["off"][2], pe_off[i0]), _fold(b1["off"][2], pe_off[i0]), ops._s())
+            else:
+                call("sbl_attention_seg2_fwd", _p(sl(b0, "q")), _p(sl(b1, "q")), HD, _p(kv0), _p(kv1), ldkv, _p(kv0[:, HD:]), _p(kv1[:, HD:]), ldkv,
+                     _p(sl(b0, "att2")), _p(sl(b1, "att2")), HD, b0["pe"].data_ptr() + 4 * pe_off[i0], b1["pe"].data_ptr() + 4 * pe_off[i0],
+                     0, N, H, seg_arr, nseg, T, 0.125, e0.drop_p, sp if e0.drop_p > 0 else None,
+                     _fold(b0["off"][2], pe_off[i0]), _fold(b1["off"][2], pe_off[i0]), ops._s())
             ops.gemm2(M, D, HD, sl(b0, "att2"), sl(b1, "att2"), HD, e0.out.w, e1.out.w, HD, sl(b0, "o_e"), sl(b1, "o_e"), D, e0.out.b, e1.out.b)
             ln2("o_e", "y_s", "y_e", "mu_e", "rs_e", e0.ln, e1.ln, e0.drop_p, 3)
             # position-wise feed-forward sub-layer
@@ -168,7 +213,7 @@ class DecoderStagesFn(torch.autograd.Function):
                      _p(sl(b0, "rs_f")), _p(sl(b1, "rs_f")), N, seg_arr, nseg, D, f0.ln[4], f0.drop_p, sp if f0.drop_p > 0 else None,
                      _fold(b0["off"][4], r0 * D), _fold(b1["off"][4], r0 * D), ops._s())
             else:
-                # (the last fusion is only ever read at the last positions: stage tail)
+                # (the last fusion is only ever read at the last positions: stage tail, which is why this layer ran on its end rows)
                 ln2("o_f", "y_e", "y_f", "mu_f", "rs_f", f0.ln, f1.ln, f0.drop_p, 4)
 
         for (i0, i1) in _decoder.stages_of(coins, ML):
@@ -184,6 +229,9 @@ class DecoderStagesFn(torch.autograd.Function):
                 layer_fwd(n, r0, r1, i0, segL)
             # stage tail: last fusion at the last positions + both heads + the token fed to the next stage, one launch
             lrows = slice(i0 * N, (i1 + 1) * N)
+            if ends:      # the compact y_f IS a ragged batch of min(2, L)-row sequences whose first / last rows the tail wants
+                seg_arr, nseg = segs(tuple(min(2, L) for L in segL))
+                r0, r1 = crow[i0], crow[i1 + 1]
             call("sbl_decoder_tail_fwd", _p(B_[0][nl - 1]["y_f"][r0:r1]), _p(B_[1][nl - 1]["y_f"][r0:r1]), _p(heads[0]), _p(heads[1]),
                  _p(last[0][lrows]), _p(last[1][lrows]), _p(pred[0][lrows]), _p(pred[1][lrows]), V, _p(ys[0]), _p(ys[1]),
                  ys[0].stride(0), i1, int(bool(coins[i1])), N, seg_arr, nseg, D, V, ops._s())
@@ -191,7 +239,7 @@ class DecoderStagesFn(torch.autograd.Function):
         ctx.state = dict(N=N, T=T, D=D, HD=HD, V=V, ML=ML, nl=nl, R=R, layers=layers, B=B_, last=last, ys=ys,
                          heads=heads, g_heads=(ops._gbuf(heads[0]), ops._gbuf(heads[1])), g_emb=ops._gbuf(emb), seed=seed,
                          p_emb=p_emb, off_emb=off_emb, streams=streams, two=side is not None, enc2=enc2, training=training,
-                         kv_lin=kv_lin)
+                         kv_lin=kv_lin, ends=ends, Rc=Rc)
         ctx.set_materialize_grads(False)
         dec.last_ys = ys
         # (ML*N, V) step-major -> (N, ML, V) views
@@ -203,7 +251,7 @@ class DecoderStagesFn(torch.autograd.Function):
         S = ctx.state
         call, gemm, segs, _p = ops.call, ops.gemm, ops._segs, ops._p
         N, T, D, HD, V, ML, nl, R = (S[k] for k in ("N", "T", "D", "HD", "V", "ML", "nl", "R"))
-        layers, B_, streams = S["layers"], S["B"], S["streams"]
+        layers, B_, streams, ends, Rc = S["layers"], S["B"], S["streams"], S["ends"], S["Rc"]
         main, side = streams[0], (streams[1] if S["two"] else None)
         dev = S["enc2"].device
         seed = S["seed"]
@@ -220,24 +268,37 @@ class DecoderStagesFn(torch.autograd.Function):
         if side is not None:
             side.wait_stream(main)
         # ---- heads and the gather of the last positions
-        dx = [None, None]
+        dx, dlasts = [None, None], [None, None]
         for d, dp in ((0, dpl), (1, dpr)):
             with torch.cuda.stream(streams[d]):
                 if dp is None:
-                    dx[d] = torch.zeros(R, D, device=dev, dtype=torch.float32)
+                    if not ends:
+                        dx[d] = torch.zeros(R, D, device=dev, dtype=torch.float32)
                     continue
                 dpred = dp.transpose(0, 1).contiguous().view(ML * N, V)
-                dlast = E(ML * N, D)
+                dlast = dlasts[d] = E(ML * N, D)
                 gemm(0, 0, ML * N, D, V, dpred, V, S["heads"][d], D, dlast, D)
                 gemm(1, 0, V, D, ML * N, dpred, V, S["last"][d], D, S["g_heads"][d], D, accumulate=1)
-                dx[d] = E(R, D)
-                call("sbl_gather_last_bwd", _p(dlast), _p(dx[d]), N, seg_arr, nseg, D, ops._s())
+                if not ends:      # (ends: the tail adjoint below goes from dlast straight to the compact rows)
+                    dx[d] = E(R, D)
+                    call("sbl_gather_last_bwd", _p(dlast), _p(dx[d]), N, seg_arr, nseg, D, ops._s())
 
         def layer_bwd(d, n, dy):
             """The sub-layers' adjoints over the rows of all steps, with the forward's offsets; always a separate pre-dropout
             gradient (the grouped launch below reads it after the input gradient has been accumulated into dz)."""
             (slf, enc, ffn), b = layers[d][n], B_[d][n]
             off = b["off"]
+            if ends and n == nl - 1:
+                # compact rows down to the self-attention's out-projection, then its two results go back to their end rows of
+                # full-size buffers (zero elsewhere) for the core, which needs every key and value row
+                en = (N, segL)
+                dy = ops.ffn_bwd(ffn, dy, b["y_e"], (b["h"], b["o_f"], b["mu_f"], b["rs_f"]), seed, off[4], True, dW, ends=en)
+                dy, _ = ops.attn_bwd(enc, dy, b["y_s"], (b["q"], b["att2"], b["pe"], b["o_e"], b["mu_e"], b["rs_e"]), N, segL, b["kv"],
+                                     seed, off[2], off[3], True, dW, dkv=dkv_blocks[d * nl + n], ends=True)
+                dz_c, datt_c = ops._out_ln_bwd(slf, dy, b["att_c"], b["o_s"], b["x_c"], b["mu_s"], b["rs_s"], seed, off[1], True, dW, ends=en)
+                dz, datt = E(R, D), E(R, HD)
+                call("sbl_ends_scatter2", _p(dz_c), _p(datt_c), _p(dz), _p(datt), N, seg_arr, nseg, D, ops._s())
+                return ops.attn_core_bwd(slf, dz, datt, b["x"], b["qkv"], b["ps"], N, segL, None, seed, off[0], dW)[0]
             dy = ops.ffn_bwd(ffn, dy, b["y_e"], (b["h"], b["o_f"], b["mu_f"], b["rs_f"]), seed, off[4], True, dW)
             dy, _ = ops.attn_bwd(enc, dy, b["y_s"], (b["q"], b["att2"], b["pe"], b["o_e"], b["mu_e"], b["rs_e"]), N, segL, b["kv"],
                                  seed, off[2], off[3], True, dW, dkv=dkv_blocks[d * nl + n])
@@ -252,8 +313,14 @@ class DecoderStagesFn(torch.autograd.Function):
         for n in range(nl - 1, -1, -1):
             if side is not None:
                 main.wait_stream(side)
-            dy = [E(R, D), E(R, D)]
-            call("sbl_fusion_seg_bwd", _p(dx[0]), _p(dx[1]), _p(dy[0]), _p(dy[1]), N, seg_arr, nseg, D, ops._s())
+            if ends and n == nl - 1:
+                dy = [E(Rc, D), E(Rc, D)]
+                call("sbl_ends_tail_bwd", _p(dlasts[0]), _p(dlasts[1]), _p(dy[0]), _p(dy[1]), N, seg_arr, nseg, D, ops._s())
+                if side is not None and dlasts[1] is not None:
+                    dlasts[1].record_stream(main)
+            else:
+                dy = [E(R, D), E(R, D)]
+                call("sbl_fusion_seg_bwd", _p(dx[0]), _p(dx[1]), _p(dy[0]), _p(dy[1]), N, seg_arr, nseg, D, ops._s())
             if side is not None:
                 side.wait_stream(main)
             for d in (0, 1):
