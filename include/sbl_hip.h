@@ -312,6 +312,15 @@ int sbl_attention_seg_bwd(const float* dout, long lddo, const float* q, long ldq
                           long ldv, const float* p, float* dq, long lddq, float* dk, long lddk, float* dv, long lddv,
                           int B, int H, const int* seg_L, int nseg, int Lk_fixed, float scale, float drop_p,
                           const uint64_t* seed, uint64_t offset, sbl_stream_t stream);
+/* Grouped cross-attention forward, inference only (the beam search of the SBL decoder, sbl_pair_beam_tail): as
+ * sbl_attention_seg_fwd with Lk_fixed >= 1 and no mask, but sequence b of the B reads the key / value rows of entry
+ * b / kv_group - k / v hold B / kv_group entries of Lk_fixed rows, the W slots of a clip share the clip's hoisted K/V - and no
+ * probabilities are written.  B must be a multiple of kv_group.  Per sequence the kernels, the size dispatch and the
+ * arithmetic are those of sbl_attention_seg_fwd on K/V repeated kv_group-fold (bit-identical output); the dropout mask
+ * index is the element's place in the probability layout of that call. */
+int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                                  long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group, float scale,
+                                  float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream);
 /* Stage head of the SBL decoder for BOTH directions in one launch: out_d = dropout(emb[tok_d] + pe[:L]) for every segment
  * of the stage (SBL/transformer/decoder.py:116-120); mask = f(seed, offset_d, element index inside the stage's rows), the
  * indexing of sbl_dropout, which regenerates it in backward.  drop_p == 0: plain embedding + PE. */
@@ -498,6 +507,30 @@ int sbl_beam_tail(const float* y, long ldy, const float* w, const float* log_pri
 int sbl_beam_finish(const float* end_score, const int32_t* end_ref, const int32_t* end_count, const int32_t* hist_tok,
                     const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N, int W,
                     int maxlen, int nbest, int sos, int eos, sbl_stream_t stream);
+
+/* ---------------------------------------------------------------- beam search of the bidirectional SBL decoder
+ * The reference's recognize_beam (SBL/transformer/decoder.py:301-385) is greedy; this is the search its beam_size / nbest
+ * arguments name.  A hypothesis is a PAIR of an l2r and an r2l prefix that are fused with each other as row b of the two
+ * directions is in the greedy decode; clip n owns the W slots n*W .. n*W + W-1, a dead slot carries the total score -inf, and
+ * nothing ends early (16 positions are always decoded, <eos> is fed and predicted behind the end).
+ *
+ * Tail of step `step` in one launch, one workgroup per clip: y_l / y_r (S = N*W, ldy) are the rows the two heads read,
+ * w_l / w_r the (V, 512) bias-free heads (plain fp32 FMA in every sbl_set_matmul_precision mode; V <= 64, 1 <= W <= min(16, V)).
+ * lpL / lpR = log_softmax of the logits.  Candidates of a live slot s: every (a, b) in V x V, total = score[s] + (lpL[s][a] +
+ * lpR[s][b]) added in fp32 in that order, per-direction scores score_dir[s][0] + lpL[s][a] and score_dir[s][1] + lpR[s][b].  The
+ * best W candidates of the clip are kept in descending total and the candidate of rank r moves to slot r.  Exact ties: the
+ * lower parent slot, then the lower rank of a in its slot's l2r ordering (log-prob descending, token id ascending), then the
+ * lower rank of b.  A candidate of total -inf is never kept; a rank without one gets the scores -inf, eos tokens and its own
+ * rank as parent.  Written:
+ *   score (S) and score_dir (S, 2), in place;
+ *   ys_new_d[rank] = ys_old_d[parent][0 .. step] || token || eos ..., (S, ldys >= maxlen+1) int64 (ys_old and ys_new must
+ *     differ: the kernel reads the parents' rows);
+ *   hist_tok_l / hist_tok_r / hist_par / hist_score (N, maxlen, W) at [n][step][rank]: the two tokens, the parent's rank at
+ *     the previous step, the total score. */
+int sbl_pair_beam_tail(const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r, float* score,
+                       float* score_dir, const int64_t* ys_old_l, const int64_t* ys_old_r, int64_t* ys_new_l, int64_t* ys_new_r,
+                       long ldys, int32_t* hist_tok_l, int32_t* hist_tok_r, int32_t* hist_par, float* hist_score, int step,
+                       int maxlen, int eos, int N, int W, int V, int D, sbl_stream_t stream);
 
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)

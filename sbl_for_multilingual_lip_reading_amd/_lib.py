@@ -47,6 +47,7 @@ SIGNATURES = {
     "sbl_attention_bwd": [P, L, P, L, P, L, P, L, P, P, L, P, L, P, L, I, I, I, I, F, F, P, U64, P],
     "sbl_attention_seg_fwd": [P, L, P, L, P, L, P, L, P, I, P, I, I, P, I, I, F, F, P, U64, P],
     "sbl_attention_seg2_fwd": [P, P, L, P, P, L, P, P, L, P, P, L, P, P, I, I, I, P, I, I, F, F, P, U64, U64, P],
+    "sbl_attention_seg_grouped_fwd": [P, L, P, L, P, L, P, L, I, I, P, I, I, I, F, F, P, U64, P],
     "sbl_gemm2_f32": [I, I, I, P, P, L, P, P, L, P, P, L, P, P, I, P, L, P],
     "sbl_add_layernorm2_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, F, F, P, U64, U64, P],
     "sbl_add_layernorm2_fusion_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, P, I, I, F, F, P, U64, U64, P],
@@ -77,6 +78,7 @@ SIGNATURES = {
     "sbl_beam_attn_step": [P, L, P, P, L, P, P, L, I, P, L, P, L, I, I, I, I, I, F, P],
     "sbl_beam_tail": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P],
     "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "sbl_pair_beam_tail": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
     "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],

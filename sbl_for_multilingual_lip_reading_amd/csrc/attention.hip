@@ -42,13 +42,15 @@ __device__ __forceinline__ bool at_masked(int mask_kind, const uint8_t* mask, in
     return false;
 }
 
-__global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
-                                                            long ldk, const float* __restrict__ v, long ldv,
-                                                            float* __restrict__ o, long ldo, float* __restrict__ p_out,
-                                                            int mask_kind, const uint8_t* __restrict__ mask, int B, int H,
-                                                            SegDesc segs, int Lk_fixed, float scale, uint32_t thresh,
-                                                            float keep_scale, const uint64_t* __restrict__ seed,
-                                                            uint64_t offset, int sz, unsigned long long* stamp) {
+// kv_group > 1 (cross-attention only, Lk_fixed > 0): sequence b attends to the key / value rows of entry b / kv_group, of which
+// there are B / kv_group (the beam slots of a clip share the clip's hoisted K/V).  write_p = false: no probability output.
+__device__ __forceinline__ void attention_fwd_body(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                   long ldk, const float* __restrict__ v, long ldv,
+                                                   float* __restrict__ o, long ldo, float* __restrict__ p_out,
+                                                   int mask_kind, const uint8_t* __restrict__ mask, int B, int H,
+                                                   const SegDesc& segs, int Lk_fixed, float scale, uint32_t thresh,
+                                                   float keep_scale, const uint64_t* __restrict__ seed,
+                                                   uint64_t offset, int sz, unsigned long long* stamp, int kv_group, bool write_p) {
     sbl_stamp_begin(stamp);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Qs = smem, *Ks = smem + sz, *Vs = smem + 2 * sz, *Ss = smem + 3 * sz;      // sz = rows actually needed x AT_LD
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restr
     const int b = (blockIdx.x / H) % B, h = blockIdx.x % H;
     const int Lq = segs.L[sidx], Lk = Lk_fixed > 0 ? Lk_fixed : Lq;
     const long qrow = segs.row_off[sidx] + (long)b * Lq;
-    const long krow = Lk_fixed > 0 ? (long)b * Lk : qrow;
+    const long krow = Lk_fixed > 0 ? (long)(b / kv_group) * Lk : qrow;
     const int Lqp = (Lq + 31) & ~31, Lkp = (Lk + 31) & ~31;
     load_head(Qs, q + qrow * ldq + h * 64, ldq, Lq, Lqp, tid);
     load_head(Ks, k + krow * ldk + h * 64, ldk, Lk, Lkp, tid);
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restr
             const float e = valid ? __expf(s - m) : 0.f;
             const float sum = wave_sum(e);
             pv = sum > 0.f ? e / sum : 0.f;
-            if (lane < Lk) pg[(long)i * Lk + lane] = pv;
+            if (write_p && lane < Lk) pg[(long)i * Lk + lane] = pv;
             pd = pv;
             if (thresh)
                 pd = sbl_keep(sd, offset, (uint64_t)pbase + (uint64_t)i * Lk + lane, thresh) ? pv * keep_scale : 0.f;
@@ -108,6 +110,25 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restr
         }
     }
     sbl_stamp_end(stamp);
+}
+__global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                            long ldk, const float* __restrict__ v, long ldv,
+                                                            float* __restrict__ o, long ldo, float* __restrict__ p_out,
+                                                            int mask_kind, const uint8_t* __restrict__ mask, int B, int H,
+                                                            SegDesc segs, int Lk_fixed, float scale, uint32_t thresh,
+                                                            float keep_scale, const uint64_t* __restrict__ seed,
+                                                            uint64_t offset, int sz, unsigned long long* stamp) {
+    attention_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, p_out, mask_kind, mask, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
+                       offset, sz, stamp, 1, true);
+}
+__global__ __launch_bounds__(256) void attention_grouped_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                                    long ldk, const float* __restrict__ v, long ldv,
+                                                                    float* __restrict__ o, long ldo, int B, int H, SegDesc segs,
+                                                                    int Lk_fixed, int kv_group, float scale, uint32_t thresh,
+                                                                    float keep_scale, const uint64_t* __restrict__ seed,
+                                                                    uint64_t offset, int sz) {
+    attention_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, nullptr, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
+                       offset, sz, nullptr, kv_group, false);
 }
 
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
@@ -282,7 +303,8 @@ struct SmallProb {
 // ENDS (cross-attention of the last decoder layer's compact "ends" rows, sbl_common.h): `segs` describes the compact batch - the
 // Lq <= 2 queries of a sequence are its positions 0 and L-1 - and `full` the full one, whose probability layout indexes the masks.
 template <bool ENDS = false>
-__device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const SegDesc& segs, int Lk_fixed, const SegDesc* full = nullptr) {
+__device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const SegDesc& segs, int Lk_fixed, const SegDesc* full = nullptr,
+                                                int kv_group = 1) {
     SmallProb P;
     const int sidx = prob / (B * H);
     P.b = (prob / H) % B;
@@ -294,7 +316,7 @@ __device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const Se
     P.Lq = Lq;
     P.Lk = Lk_fixed > 0 ? Lk_fixed : Lq;
     P.qrow = ro + (long)P.b * Lq;
-    P.krow = Lk_fixed > 0 ? (long)P.b * P.Lk : P.qrow;
+    P.krow = Lk_fixed > 0 ? (long)(P.b / kv_group) * P.Lk : P.qrow;      // kv_group: see attention_fwd_body
     P.pbase = po + ((long)P.h * B + P.b) * Lq * P.Lk;
     P.qoff = 0;
     if (segs.qtile) {      // query tiles of one self-attention over qtile (= Lk_fixed) rows: all tiles read the sequence's own keys
@@ -322,12 +344,13 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
                                                          int causal, int B, int H, const SegDesc& segs, int Lk_fixed,
                                                          float scale, uint32_t thresh, float keep_scale,
                                                          const uint64_t* __restrict__ seed, uint64_t offset, int nprob,
-                                                         unsigned long long* stamp = nullptr, const SegDesc* full = nullptr) {
+                                                         unsigned long long* stamp = nullptr, const SegDesc* full = nullptr,
+                                                         int kv_group = 1, bool write_p = true) {
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
     const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
     sbl_stamp_begin(stamp);      // (thread 0 = wavefront 0 of the workgroup, which always has a problem)
     if (prob >= nprob) return;   // whole wavefront; the kernel has no barrier
-    const SmallProb P = small_prob<ENDS>(prob, B, H, segs, Lk_fixed, full);
+    const SmallProb P = small_prob<ENDS>(prob, B, H, segs, Lk_fixed, full, kv_group);
     const int Lq = P.Lq, Lk = P.Lk;
     const int NT = Lk > 16 ? 2 : 1;
     const float* qb = q + P.qrow * ldq + P.h * 64;
@@ -376,7 +399,7 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
             const int j = 16 * t + 4 * g + r;
             float pv = s[t][r] * inv;
             if (n < Lq && j < Lk) {
-                pg[(long)n * Lk + j] = pv;
+                if (write_p) pg[(long)n * Lk + j] = pv;
                 if (thresh) pv = sbl_keep(sd, offset, (uint64_t)P.mbase + (uint64_t)(n * P.mstep) * Lk + j, thresh) ? pv * keep_scale : 0.f;
             } else {
                 pv = 0.f;
@@ -417,6 +440,15 @@ __global__ __launch_bounds__(256) void attention_small_fwd_kernel(const float* _
                                                                   unsigned long long* stamp) {
     attention_small_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, p_out, causal, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed, offset,
                              nprob, stamp);
+}
+__global__ __launch_bounds__(256) void attention_small_grouped_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                                          long ldk, const float* __restrict__ v, long ldv,
+                                                                          float* __restrict__ o, long ldo, int B, int H, SegDesc segs,
+                                                                          int Lk_fixed, int kv_group, float scale, uint32_t thresh,
+                                                                          float keep_scale, const uint64_t* __restrict__ seed,
+                                                                          uint64_t offset, int nprob) {
+    attention_small_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed, offset,
+                             nprob, nullptr, nullptr, kv_group, false);
 }
 // Two same-shape problems in one launch (the two decoder directions; blockIdx.y picks the operand set).
 struct AttFwdSet {
@@ -773,6 +805,41 @@ extern "C" int sbl_attention_seg_fwd(const float* q, long ldq, const float* k, l
                        ldo, p_out, mask_kind, mask, B, H, d, Lk_fixed, scale, drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u,
                        1.f / (1.f - drop_p), seed, offset, sz, sbl_next_stamp_slot(SBL_KID_ATTENTION));
     SBL_LAUNCH_CHECK("sbl_attention_fwd");
+    return 0;
+}
+
+// Grouped cross-attention, inference only: sbl_attention_seg_fwd with Lk_fixed > 0 and no mask, where sequence b of the B reads
+// the key / value rows of entry b / kv_group (k / v hold B / kv_group entries of Lk_fixed rows) and no probabilities are
+// written.  Same kernels, same size dispatch and same arithmetic per sequence as sbl_attention_seg_fwd on K/V repeated
+// kv_group-fold, without the repeated copy.
+extern "C" int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                                             long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
+                                             float scale, float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream) {
+    SegDesc d;
+    SBL_REQUIRE(sbl_make_segs(d, seg_L, nseg, B, H, Lk_fixed) > 0, "sbl_attention_seg_grouped_fwd: bad segment list (nseg=%d, 1..%d)", nseg, SBL_MAX_SEG);
+    SBL_REQUIRE(Lk_fixed >= 1, "sbl_attention_seg_grouped_fwd: Lk=%d (cross-attention only)", Lk_fixed);
+    SBL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "sbl_attention_seg_grouped_fwd: B=%d is no multiple of the group size %d", B, kv_group);
+    if (int e = at_check("sbl_attention_seg_grouped_fwd", B, H, d, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
+    SBL_REQUIRE(q && k && v && o && sbl_aligned16(q) && sbl_aligned16(k) && sbl_aligned16(v) && sbl_aligned16(o),
+                "sbl_attention_seg_grouped_fwd: null/unaligned pointer");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_seg_grouped_fwd: bad dropout args");
+    const uint32_t thresh = drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u;
+    const float keep_scale = 1.f / (1.f - drop_p);
+    const bool small = at_small_ok(d, Lk_fixed, 0);
+    if (small || at_qtile_ok(d, Lk_fixed, 0)) {
+        const SegDesc t = small ? d : at_qtile_desc(d.L[0], Lk_fixed);
+        const int nprob = (small ? nseg : 2) * B * H;
+        hipLaunchKernelGGL(attention_small_grouped_fwd_kernel, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk,
+                           v, ldv, o, ldo, B, H, t, Lk_fixed, kv_group, scale, thresh, keep_scale, seed, offset, nprob);
+        SBL_LAUNCH_CHECK("sbl_attention_seg_grouped_fwd(small)");
+        return 0;
+    }
+    const int sz = at_rows_sz(d, nseg, Lk_fixed);
+    static bool attr_set[64] = {false};
+    SBL_HIP(sbl_raise_lds_cap((const void*)attention_grouped_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
+    hipLaunchKernelGGL(attention_grouped_fwd_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k,
+                       ldk, v, ldv, o, ldo, B, H, d, Lk_fixed, kv_group, scale, thresh, keep_scale, seed, offset, sz);
+    SBL_LAUNCH_CHECK("sbl_attention_seg_grouped_fwd");
     return 0;
 }
 

@@ -773,13 +773,23 @@ def out_ln_fwd(h, a, res, seed, off, bufs=None):
     return o, y, mean, rstd
 
 
-def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o):
+def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o, kv_group=None):
     """Attention sub-layer on the rows x (B * sum(segL), D) of a ragged batch: segment s has B sequences of length segL[s].
     kv = None: self-attention inside each segment; else cross-attention to the rows kv (B * Lk, 2 * H * 64) = [K|V] (a
     column block of a wider buffer is fine).  Returns (y, (qkv, att, p, o, mean, rstd)): the second is what attn_bwd wants
-    back; p = the segments' (H*B, L, Lk) probability blocks back to back."""
+    back; p = the segments' (H*B, L, Lk) probability blocks back to back.
+    kv_group = W (inference only, no mask): kv holds B / W entries and sequence b attends to entry b // W
+    (sbl_attention_seg_grouped_fwd); no probabilities are kept (p = None)."""
     HD = a.H * 64
     qkv = lin_fwd(a.inp, x)
+    if kv_group is not None:
+        assert kv is not None and mask_kind == 0 and B % kv_group == 0 and kv.size(0) % (B // kv_group) == 0
+        ldk = _rows(kv)[1]
+        att = _new(x, x.size(0), HD)
+        call("sbl_attention_seg_grouped_fwd", _p(qkv), a.inp.N, _p(kv), ldk, _p(kv[:, HD:]), ldk, _p(att), HD, B, a.H, *_segs(segL),
+             kv.size(0) // (B // kv_group), int(kv_group), 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+        o, y, mean, rstd = out_ln_fwd(a, att, x, seed, off_o)
+        return y, (qkv, att, None, o, mean, rstd)
     if kv is None:
         k, v, ldk, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, 0       # Lk = 0: keys = the segment's own rows
         psize = a.H * B * sum(l * l for l in segL)
@@ -2043,3 +2053,50 @@ def beam_finish(st, nbest, eos_id):
     call("sbl_beam_finish", _p(st.end_score), _p(st.end_ref), _p(st.end_count), _p(st.hist_tok), _p(st.hist_par), _p(yseq),
          _p(lengths), _p(scores), _p(n_hyps), st.N, st.W, st.maxlen, int(nbest), int(st.sos_id), int(eos_id), _s())
     return yseq, lengths, scores, n_hyps
+
+
+class PairBeamState(object):
+    """The device buffers of one beam search of the bidirectional SBL decoder over N clips with W slots each
+    (include/sbl_hip.h, sbl_pair_beam_tail): total and per-direction scores, the two double-buffered prefix tables
+    ys[d][k] (N*W, maxlen+1) int64 - step i reads k = i % 2 and writes the other - and the (N, maxlen, W) history.
+    Allocated once per call; reset() restores the start (every prefix <sos>, slot 0 of every clip at score 0, the other
+    slots dead) with fill launches only."""
+
+    def __init__(self, N, W, maxlen, sos_id, eos_id, device):
+        i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)      # noqa: E731
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)    # noqa: E731
+        self.N, self.W, self.maxlen, self.sos_id, self.eos_id = N, W, maxlen, sos_id, eos_id
+        self.score, self.score_dir = f32(N, W), f32(N, W, 2)
+        self.ys = torch.empty(2, 2, N * W, maxlen + 1, dtype=torch.int64, device=device)      # [direction][buffer]
+        self.hist_tok_l, self.hist_tok_r, self.hist_par = i32(N, maxlen, W), i32(N, maxlen, W), i32(N, maxlen, W)
+        self.hist_score = f32(N, maxlen, W)
+        self.reset()
+
+    def reset(self):
+        self.score.fill_(float("-inf"))
+        self.score[:, 0] = 0.0
+        self.score_dir.fill_(float("-inf"))
+        self.score_dir[:, 0] = 0.0
+        self.ys.fill_(self.eos_id)
+        self.ys[:, :, :, 0] = self.sos_id
+
+    def prefixes(self, step):
+        """(l2r, r2l) prefix tables that step `step` reads: what step - 1 wrote."""
+        return self.ys[0, step % 2], self.ys[1, step % 2]
+
+    def history(self):
+        return self.hist_tok_l, self.hist_tok_r, self.hist_par, self.hist_score
+
+
+def pair_beam_tail(y_l, y_r, w_l, w_r, st, step):
+    """Tail of beam step `step` in one launch (sbl_pair_beam_tail) on the rows y_l / y_r (N*W, 512) the two heads read: the
+    best W pair candidates of every clip into the PairBeamState `st` (prefix buffer step % 2 is read, the other written)."""
+    S, D = y_l.shape
+    V = w_l.size(0)
+    assert S == st.N * st.W and y_r.shape == y_l.shape and w_r.shape == w_l.shape
+    assert y_l.stride(1) == 1 and y_r.stride(1) == 1 and y_l.stride(0) == y_r.stride(0) and w_l.is_contiguous() and w_r.is_contiguous()
+    _need_cuda(y_l, y_r, w_l, w_r, st.score)
+    old, new = st.ys[:, step % 2], st.ys[:, 1 - step % 2]
+    call("sbl_pair_beam_tail", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
+         _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
+         _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _s())

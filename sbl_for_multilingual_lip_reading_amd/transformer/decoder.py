@@ -1,16 +1,20 @@
 """Decoder (the SBL bidirectional decoder) and DecoderLayer with the constructor / forward signatures and state-dict
 keys of the reference's transformer/decoder.py."""
+import collections
 import random
 
 import torch
 import torch.nn as nn
 
-from ._env import config, ops
+from ._env import _lib, config, ops
 from . import decoder_stages
 from .attention import MultiHeadAttention
 from .module import PositionalEncoding, PositionwiseFeedForward, mask_rows
 
 IGNORE_ID = config.IGNORE_ID
+MAX_PAIR_BEAM = 16          # slots per clip of Decoder.beam_search (csrc/pair_beam.hip)
+
+PairBeamResult = collections.namedtuple("PairBeamResult", ("ys_l2r", "ys_r2l", "scores", "scores_dir", "history"))
 
 
 def stages_of(coins, maxlen):
@@ -167,10 +171,9 @@ class Decoder(nn.Module):
         self.last_coins = coins
         return coins
 
-    def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode):
-        """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383)."""
-        maxlen = config.MAX_DECODE_LEN
-        N = encoder_outputs.size(0)
+    def _begin(self, encoder_outputs):
+        """What every decode loop starts with -> (layers[direction], main stream, side stream or None, kv[direction][layer]):
+        the parameters fused, the two streams, and the hoisted cross-attention K/V of the encoder output."""
         dev = encoder_outputs.device
         layers = (self._layers(0), self._layers(1))
         for d in (0, 1):            # parameter fusing (first call only) happens here, on the caller's stream
@@ -192,11 +195,41 @@ class Decoder(nn.Module):
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 kv[1] = [lay.enc_attn.project_kv(encoder_outputs) for lay in layers[1]]
+        return layers, main, side, kv
+
+    def _stage(self, ys, B, segL, layers, main, side, kv, kv_group=None):
+        """One stage on B sequences per segment: embedding + PE of the token tables ys[direction], the n_layers layers of
+        both directions with the fusion after each -> x[direction], the rows (B * sum(segL), d_model) behind the last
+        fusion.  kv_group = W: kv belongs to B / W clips whose W beam slots share it (DecoderLayer.forward_rows)."""
+        emb = self.tgt_word_emb.weight
+        pe = self.positional_encoding.pe[0]
+        x = [ops.dropout(ops.EmbedPEFn.apply(ys[d], B, segL, emb, pe), self.dropout.p, self.training) for d in (0, 1)]
+        for n in range(self.n_layers):
+            slf_mask = 'causal' if n == 0 else None       # decoder.py:123-125 vs :150,:157
+            if side is None:
+                for d in (0, 1):
+                    x[d] = layers[d][n].forward_rows(x[d], B, segL, slf_mask, kv[d][n], kv_group)
+            else:
+                # the l2r and r2l layers are independent until the fusion: run them on two HIP streams so their
+                # small kernels overlap on the 256 CUs (fork / join is captured as parallel hipGraph branches;
+                # autograd replays backward on the same two streams)
+                side.wait_stream(main)
+                x[0] = layers[0][n].forward_rows(x[0], B, segL, slf_mask, kv[0][n], kv_group)
+                with torch.cuda.stream(side):
+                    x[1] = layers[1][n].forward_rows(x[1], B, segL, slf_mask, kv[1][n], kv_group)
+                main.wait_stream(side)
+            x[0], x[1] = ops.FusionFn.apply(x[0], x[1], B, segL)
+        return x
+
+    def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode):
+        """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383)."""
+        maxlen = config.MAX_DECODE_LEN
+        N = encoder_outputs.size(0)
+        dev = encoder_outputs.device
+        layers, main, side, kv = self._begin(encoder_outputs)
         ys = [torch.full((N, maxlen + 1), self.eos_id, dtype=torch.long, device=dev) for _ in (0, 1)]
         for y in ys:
             y[:, 0] = self.sos_id
-        emb = self.tgt_word_emb.weight
-        pe = self.positional_encoding.pe[0]
         heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
         golds = (gold_l2r, gold_r2l)
         outs = ([None] * maxlen, [None] * maxlen)
@@ -219,22 +252,7 @@ class Decoder(nn.Module):
             encoder_outputs.register_hook(lambda g: ops.flush_deferred())
         for (i0, i1) in stages:
             segL = tuple(range(i0 + 1, i1 + 2))            # prefix lengths of the steps in this stage
-            x = [ops.dropout(ops.EmbedPEFn.apply(ys[d], N, segL, emb, pe), self.dropout.p, self.training) for d in (0, 1)]
-            for n in range(self.n_layers):
-                slf_mask = 'causal' if n == 0 else None       # decoder.py:123-125 vs :150,:157
-                if side is None:
-                    for d in (0, 1):
-                        x[d] = layers[d][n].forward_rows(x[d], N, segL, slf_mask, kv[d][n])
-                else:
-                    # the l2r and r2l layers are independent until the fusion: run them on two HIP streams so their
-                    # small kernels overlap on the 256 CUs (fork / join is captured as parallel hipGraph branches;
-                    # autograd replays backward on the same two streams)
-                    side.wait_stream(main)
-                    x[0] = layers[0][n].forward_rows(x[0], N, segL, slf_mask, kv[0][n])
-                    with torch.cuda.stream(side):
-                        x[1] = layers[1][n].forward_rows(x[1], N, segL, slf_mask, kv[1][n])
-                    main.wait_stream(side)
-                x[0], x[1] = ops.FusionFn.apply(x[0], x[1], N, segL)
+            x = self._stage(ys, N, segL, layers, main, side, kv)
             for d in (0, 1):
                 last = ops.GatherLastFn.apply(x[d], N, segL)           # (nseg*N, 512): position -1 of every prefix
                 pred = ops.linear(last, heads[d])                      # (nseg*N, 58)
@@ -280,6 +298,52 @@ class Decoder(nn.Module):
             _, ys = self._run(encoder_outputs, None, None, teacher_mode=False)
         return ys[0], ys[1]
 
+    def beam_search(self, encoder_outputs, beam_size, nbest=1):
+        """Beam search over PAIRS of an l2r and an r2l prefix - the search that recognize_beam's name and the reference's
+        beam_size / nbest arguments promise (decoder.py:301-385 is greedy).  A pair is fused exactly as row b of the two
+        directions is in `_run`; every clip keeps W = beam_size pairs, the batch is S = N * W rows, and because the upper
+        layers are not causal and the fusion flips positions the whole prefix is recomputed at every step with `_run`'s own
+        kernels (no KV cache).  After the stage of step i the tail kernel (ops.pair_beam_tail) adds, for every live slot s and
+        every (a, b) in V x V, score[s] + (log_softmax(head_l2r)[a] + log_softmax(head_r2l)[b]) in fp32 and keeps the clip's
+        best W in descending total (ties: lower parent slot, then lower rank of a in (log-prob descending, token ascending)
+        order, then lower rank of b).  Nothing ends early and there is no length penalty: all 16 positions are decoded, as
+        the model is trained (<eos> is fed and predicted behind the end), so the totals are sequence log-likelihoods and
+        the slots after step 15 are the n-best list in order.  beam_size = 1 is the greedy decode token for token.
+        The cross-attention K/V are hoisted once for the N clips and shared by a clip's W slots
+        (sbl_attention_seg_grouped_fwd); two streams as in `_run`; module mode is used as recognize_beam uses it; no host
+        read, so the call is capturable as one hipGraph.
+        Returns PairBeamResult(ys_l2r, ys_r2l (N, nbest, 17) int64, scores (N, nbest), scores_dir (N, nbest, 2), history =
+        (l2r token, r2l token, parent rank, total score), each (N, 16, W) at [n][step][rank])."""
+        enc = encoder_outputs
+        W, nbest = int(beam_size), int(nbest)
+        if not 1 <= W <= MAX_PAIR_BEAM:
+            raise _lib.SblHipError("Decoder.beam_search: beam_size = %d outside 1..%d" % (W, MAX_PAIR_BEAM))
+        if not 1 <= nbest <= W:
+            raise _lib.SblHipError("Decoder.beam_search: nbest = %d outside 1..beam_size = %d" % (nbest, W))
+        if not enc.is_cuda:
+            raise _lib.SblHipError("Decoder.beam_search needs the encoder output on the GPU (got a %s tensor); there is no "
+                                   "CPU path" % enc.device)
+        with torch.no_grad():
+            st = self._beam_run(enc, W)
+        N, L = enc.size(0), config.MAX_DECODE_LEN + 1
+        ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(config.MAX_DECODE_LEN))
+        return PairBeamResult(ys_l, ys_r, st.score[:, :nbest], st.score_dir[:, :nbest], st.history())
+
+    def _beam_run(self, encoder_outputs, W):
+        """The 16 steps of beam_search -> the final ops.PairBeamState.  The stage is `_run`'s, at batch N * W."""
+        maxlen = config.MAX_DECODE_LEN
+        N = encoder_outputs.size(0)
+        S = N * W
+        layers, main, side, kv = self._begin(encoder_outputs)
+        st = ops.PairBeamState(N, W, maxlen, self.sos_id, self.eos_id, encoder_outputs.device)
+        heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
+        for i in range(maxlen):
+            segL = (i + 1,)
+            x = self._stage(st.prefixes(i), S, segL, layers, main, side, kv, kv_group=W)
+            last = [ops.GatherLastFn.apply(x[d], S, segL) for d in (0, 1)]
+            ops.pair_beam_tail(last[0], last[1], heads[0], heads[1], st, i)
+        return st
+
 
 class DecoderLayer(nn.Module):
     ''' Causal self-attention, attention to the encoder output, position-wise FFN (decoder.py:387-408) '''
@@ -290,11 +354,11 @@ class DecoderLayer(nn.Module):
         self.enc_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=dropout)
 
-    def forward_rows(self, x2, B, segL, slf_attn_mask, enc_kv):
+    def forward_rows(self, x2, B, segL, slf_attn_mask, enc_kv, kv_group=None):
         """The layer on a ragged batch of rows (see MultiHeadAttention.forward_rows); non_pad_mask is all ones on
-        this path (decoder.py:109,112)."""
+        this path (decoder.py:109,112).  kv_group = W: enc_kv belongs to B / W clips whose W beam slots share it."""
         x2, _ = self.slf_attn.forward_rows(x2, B, segL, mask=slf_attn_mask)
-        x2, _ = self.enc_attn.forward_rows(x2, B, segL, mask=None, kv_proj=enc_kv)
+        x2, _ = self.enc_attn.forward_rows(x2, B, segL, mask=None, kv_proj=enc_kv, kv_group=kv_group)
         return self.pos_ffn(x2)
 
     def forward(self, dec_input, enc_output, non_pad_mask=None, slf_attn_mask=None, dec_enc_attn_mask=None,

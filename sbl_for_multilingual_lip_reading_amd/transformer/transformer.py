@@ -40,11 +40,22 @@ class Transformer(nn.Module):
         enc, _ = self._encode(input)
         return self.decoder.recognize_beam(enc)
 
-    def validate(self, padded_input, padded_target_l2r, padded_target_r2l, meter, valid_rows=None):
+    def recognize_nbest(self, input, beam_size, nbest=1):
+        """Beam-search decode of (N, T, H, W) crops (or ops.RawClips) over pairs of an l2r and an r2l hypothesis:
+        Decoder.beam_search on the encoder output -> PairBeamResult, the nbest best pairs of every clip, best first."""
+        enc, _ = self._encode(input)
+        return self.decoder.beam_search(enc, beam_size, nbest)
+
+    def validate(self, padded_input, padded_target_l2r, padded_target_r2l, meter, valid_rows=None, beam_size=None):
         """One validation batch (the body of valid_lrw's loop, train.py:236-276): greedy decode, then score both directions
         against the (N, To) IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device.  No host sync:
         in eval() under torch.no_grad() the whole call is capturable as one hipGraph, like recognize; `valid_rows` (device
-        int32[1]) then masks the tail of a short last batch.  Returns the token tensors of recognize."""
-        ys_l2r, ys_r2l = self.recognize(padded_input)
+        int32[1]) then masks the tail of a short last batch.  Returns the token tensors of recognize.
+        With beam_size the decode is the beam search (recognize_nbest) and the scored tokens are its best pair's."""
+        if beam_size is not None:
+            res = self.recognize_nbest(padded_input, beam_size, 1)
+            ys_l2r, ys_r2l = res.ys_l2r[:, 0].contiguous(), res.ys_r2l[:, 0].contiguous()
+        else:
+            ys_l2r, ys_r2l = self.recognize(padded_input)
         meter.update(ys_l2r, ys_r2l, padded_target_l2r, padded_target_r2l, valid_rows=valid_rows)
         return ys_l2r, ys_r2l
