@@ -532,6 +532,41 @@ int sbl_pair_beam_tail(const float* y_l, const float* y_r, long ldy, const float
                        long ldys, int32_t* hist_tok_l, int32_t* hist_tok_r, int32_t* hist_par, float* hist_score, int step,
                        int maxlen, int eos, int N, int W, int V, int D, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- closed-vocabulary word decode (lexicon shortlist, rescoring)
+ * LRW and LRW1000 are closed-vocabulary word benchmarks.  The reference scores "the joined phoneme string equals the gold
+ * string" (wer_compute, SBL/train.py:28-38, as the test loop uses it, SBL/test.py:185-218): a hypothesis one substitution away
+ * from a vocabulary word is a miss.  These two launches replace that comparison and extend it: the hypotheses are mapped onto
+ * the lexicon, and the model chooses between the close words.
+ *
+ * Lexicon: Wn >= 1 words; word w is a token row of length c_w in 1..15 with ids in [0, V), none equal to sos or eos;
+ *   duplicate rows are distinct entries.  Packed as `lex` (Wn, 16) uint8: bytes 0..14 the tokens (0 behind the end), byte 15
+ *   c_w; 16-byte aligned.  The caller validates the words when it packs them.
+ * Hypothesis h < H of clip n: the rows ys_l2r[n*ld_n + h*ld_h ..] and ys_r2l[...] of Ly = 17 entries, as recognize and
+ *   beam_search return them.  From each row: entries 1..16, cut before the first eos, without the entries equal to sos or
+ *   ignore -> p_l and p_r, of length 0..16.
+ * Distance: D(n, h, w) = lev(p_l, w) + lev(p_r, reversed(w)), unit costs, 0..32.
+ * Shortlist: the key of word w for clip n is the lexicographic minimum over h of (D(n,h,w), h); the shortlist is the K words
+ *   with the smallest (D, h, w), in that order, 1 <= K <= min(Wn, 16).  All integer: no float, no atomics.
+ * Written: cand / cand_dist / cand_hyp (N, K) int32 = w, D, h per rank; the candidates' token tables cand_ys_l2r (N*K, 17)
+ *   int64 = sos, w, eos fill and cand_ys_r2l = sos, reversed(w), eos fill; n_pos (N*K) int32 = c_w + 1, the trained positions
+ *   (the tokens and the one eos that preprocess puts in ys_out).  N == 0 is a successful no-op. */
+int sbl_lexicon_shortlist(const int64_t* ys_l2r, const int64_t* ys_r2l, long ld_n, long ld_h, int Ly, const uint8_t* lex, int Wn,
+                          int N, int H, int K, int64_t sos, int64_t eos, int64_t ignore, int32_t* cand, int32_t* cand_dist,
+                          int32_t* cand_hyp, int64_t* cand_ys_l2r, int64_t* cand_ys_r2l, int32_t* n_pos, sbl_stream_t stream);
+/* Pair score of S slots in groups of G <= 16 (G = K after a shortlist, G = W when a beam is rescored), one workgroup per group.
+ * y_l / y_r (16*S, ldy): row i*S + s is what the head reads at the last position of prefix length i+1 of slot s - the
+ * segment-major rows of sbl_gather_last_fwd for the 16 segments of lengths 1..16.  w_l / w_r: the (V, 512) bias-free heads,
+ * plain fp32 FMA in every sbl_set_matmul_precision mode, V <= 64: the arithmetic of sbl_pair_beam_tail.  ys_l2r / ys_r2l
+ * (S, ldys >= 17) int64 token tables; n_pos (S) int32, clamped to 0..16, NULL = 16 everywhere.
+ * With lpL_i / lpR_i the two heads' log-softmax at step i, taken at tokens ys_l2r[s][i+1] / ys_r2l[s][i+1] (-inf for a token
+ * outside [0, V)):  logp (S, 16, 2) = (lpL_i, lpR_i) for i < n_pos[s], else 0;  score_dir (S, 2) = their sums in ascending i,
+ * fp32;  score (S): starts at 0, then score += (lpL_i + lpR_i) in ascending i - the order of sbl_pair_beam_tail, so with
+ * n_pos = 16 it is the beam search's total.  No length penalty, no prior.  best (S/G) int32: the rank in the group with the
+ * largest score, the lower rank on an exact tie.  S == 0 is a successful no-op. */
+int sbl_pair_score_tail(const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r, const int64_t* ys_l2r,
+                        const int64_t* ys_r2l, long ldys, const int32_t* n_pos, float* logp, float* score_dir, float* score,
+                        int32_t* best, int S, int G, int V, int D, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
  * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.

@@ -79,6 +79,8 @@ SIGNATURES = {
     "sbl_beam_tail": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P],
     "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "sbl_pair_beam_tail": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P],
+    "sbl_lexicon_shortlist": [P, P, L, L, I, P, I, I, I, I, L, L, L, P, P, P, P, P, P, P],
+    "sbl_pair_score_tail": [P, P, L, P, P, P, P, L, P, P, P, P, P, I, I, I, I, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],
     "sbl_smoothed_ce_bwd": [P, P, P, P, P, I, I, F, I, P],
     "sbl_cls_head_fwd": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],

@@ -18,11 +18,9 @@
 //      the kernel reads the parents' rows), and the (step, rank) history.
 // A candidate of total -inf (or NaN) is never kept; a rank without a candidate gets the scores -inf, <eos> tokens and its own
 // rank as parent.
-#include "sbl_common.h"
+#include "pair_head.h"
 
-#define PB_D 512          // d_model of the decoder (host-checked)
 #define PB_MAX_W 16
-#define PB_MAX_V 64       // one class per lane
 #define PB_NONE 0x7fffffff
 
 // (value, index) maximum over the wave with the lower index on equal values; PB_NONE = nothing to offer.  Every lane ends
@@ -67,11 +65,7 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
         const float4 a = wr[lane], c = wr[64 + lane];
         const float* y = d ? y_r : y_l;
         for (int r = 0; r < W; ++r) {
-            const float4* yr = reinterpret_cast<const float4*>(y + (slot0 + r) * ldy);
-            const float4 y0 = yr[lane], y1 = yr[64 + lane];
-            float acc = y0.x * a.x + y0.y * a.y + y0.z * a.z + y0.w * a.w;
-            acc += y1.x * c.x + y1.y * c.y + y1.z * c.z + y1.w * c.w;
-            acc = wave_sum(acc);
+            const float acc = pb_row_dot(reinterpret_cast<const float4*>(y + (slot0 + r) * ldy), a, c, lane);
             if (lane == 0) s_lp[d][r][v] = acc;
         }
     }
@@ -80,10 +74,7 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
     for (int row = wave; row < 2 * W; row += 4) {
         const int d = row >= W, r = row - d * W;
         const float l = lane < V ? s_lp[d][r][lane] : -INFINITY;
-        const float m = wave_max(l);
-        const float lse = logf(wave_sum(lane < V ? expf(l - m) : 0.f));
-        float lp = (l - m) - lse;
-        if (!(lp > -INFINITY)) lp = -INFINITY;      // NaN too
+        const float lp = pb_log_softmax(l, lane < V);
         bool used = lane >= V;
         float top = -INFINITY;
         int ttok = eos;

@@ -2100,3 +2100,56 @@ def pair_beam_tail(y_l, y_r, w_l, w_r, st, step):
     call("sbl_pair_beam_tail", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
          _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
          _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _s())
+
+
+# --------------------------------------------------------------------------- #
+# closed-vocabulary word decode (sbl_lexicon_shortlist, sbl_pair_score_tail)
+# --------------------------------------------------------------------------- #
+LEXICON_MAX_WORD, LEXICON_MAX_WORDS, LEXICON_MAX_SHORTLIST = 15, 65536, 16
+
+Shortlist = _collections.namedtuple("Shortlist", ("cand", "cand_dist", "cand_hyp", "cand_ys_l2r", "cand_ys_r2l", "n_pos"))
+
+
+def lexicon_shortlist(ys_l2r, ys_r2l, lex, K, sos_id, eos_id, ignore_id):
+    """The K lexicon words nearest to the hypotheses of every clip, in one launch (include/sbl_hip.h, sbl_lexicon_shortlist).
+    ys_l2r / ys_r2l: int64 (N, 17) or (N, H, 17) rows of recognize / beam_search (views with any clip and hypothesis stride);
+    lex: the uint8 (Wn, 16) table of transformer.lexicon.Lexicon on the same device.  Returns Shortlist(cand, cand_dist,
+    cand_hyp (N, K) int32, cand_ys_l2r, cand_ys_r2l (N*K, 17) int64, n_pos (N*K) int32).  No sync."""
+    if ys_l2r.dim() == 2:
+        ys_l2r, ys_r2l = ys_l2r.unsqueeze(1), ys_r2l.unsqueeze(1)
+    N, H, Ly = ys_l2r.shape
+    K = int(K)
+    _need_cuda(ys_l2r, ys_r2l, lex)
+    if ys_r2l.shape != ys_l2r.shape or ys_l2r.dtype != torch.int64 or ys_r2l.dtype != torch.int64:
+        raise ValueError("lexicon_shortlist: hypothesis rows %s / %s must be int64 of one shape" % (tuple(ys_l2r.shape), tuple(ys_r2l.shape)))
+    if ys_l2r.stride() != ys_r2l.stride() or ys_l2r.stride(2) != 1:
+        ys_l2r, ys_r2l = ys_l2r.contiguous(), ys_r2l.contiguous()
+    if lex.dtype != torch.uint8 or lex.dim() != 2 or lex.size(1) != 16 or not lex.is_contiguous():
+        raise ValueError("lexicon_shortlist: lex must be the contiguous uint8 (Wn, 16) table of Lexicon")
+    Wn = lex.size(0)
+    if not 1 <= K <= min(Wn, LEXICON_MAX_SHORTLIST):
+        raise _lib.SblHipError("lexicon_shortlist: shortlist = %d outside 1..min(%d words, %d)" % (K, Wn, LEXICON_MAX_SHORTLIST))
+    dev = ys_l2r.device
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)      # noqa: E731
+    out = Shortlist(i32(N, K), i32(N, K), i32(N, K), torch.empty(N * K, Ly, dtype=torch.int64, device=dev),
+                    torch.empty(N * K, Ly, dtype=torch.int64, device=dev), i32(N * K))
+    call("sbl_lexicon_shortlist", _p(ys_l2r), _p(ys_r2l), ys_l2r.stride(0), ys_l2r.stride(1), Ly, _p(lex), Wn, N, H, K, int(sos_id),
+         int(eos_id), int(ignore_id), *(_p(t) for t in out), _s())
+    return out
+
+
+def pair_score_tail(y_l, y_r, w_l, w_r, ys_l2r, ys_r2l, n_pos, G, logp, score_dir, score, best):
+    """Pair scores of S slots in groups of G in one launch (sbl_pair_score_tail) on the rows y_l / y_r (16*S, 512) the two
+    heads read at the last position of every prefix (GatherLastFn of the 16 segments 1..16): fills logp (S, 16, 2), score_dir
+    (S, 2), score (S) and best (S/G) int32.  ys_l2r / ys_r2l: (S, 17) int64 token tables; n_pos: int32 (S) or None (16)."""
+    S = ys_l2r.size(0)
+    V, D = w_l.shape
+    _need_cuda(y_l, y_r, w_l, w_r, ys_l2r, ys_r2l, score)
+    assert y_l.shape == (16 * S, D) and y_r.shape == y_l.shape and w_r.shape == w_l.shape and ys_r2l.shape == ys_l2r.shape
+    assert y_l.stride(1) == 1 and y_r.stride(1) == 1 and y_l.stride(0) == y_r.stride(0) and w_l.is_contiguous() and w_r.is_contiguous()
+    assert ys_l2r.dtype == torch.int64 and ys_r2l.dtype == torch.int64 and ys_l2r.stride(1) == 1 and ys_l2r.stride() == ys_r2l.stride()
+    assert n_pos is None or (n_pos.dtype == torch.int32 and n_pos.shape == (S,) and n_pos.is_contiguous())
+    assert all(t.is_contiguous() for t in (logp, score_dir, score, best)) and best.dtype == torch.int32
+    assert logp.shape == (S, 16, 2) and score_dir.shape == (S, 2) and score.shape == (S,) and best.numel() * G == S
+    call("sbl_pair_score_tail", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(ys_l2r), _p(ys_r2l), ys_l2r.stride(0),
+         _p(n_pos), _p(logp), _p(score_dir), _p(score), _p(best), S, int(G), V, D, _s())

@@ -15,6 +15,9 @@ IGNORE_ID = config.IGNORE_ID
 MAX_PAIR_BEAM = 16          # slots per clip of Decoder.beam_search (csrc/pair_beam.hip)
 
 PairBeamResult = collections.namedtuple("PairBeamResult", ("ys_l2r", "ys_r2l", "scores", "scores_dir", "history"))
+PairScore = collections.namedtuple("PairScore", ("score", "score_dir", "logp", "best"))
+WordResult = collections.namedtuple("WordResult", ("word", "cand", "cand_dist", "cand_hyp", "score", "score_dir"))
+SCORE_PAIRS_MAX_ROWS = 1 << 16      # rows of one score_pairs stage (136 per slot): 128 MiB of activations per 512 columns
 
 
 def stages_of(coins, maxlen):
@@ -343,6 +346,79 @@ class Decoder(nn.Module):
             last = [ops.GatherLastFn.apply(x[d], S, segL) for d in (0, 1)]
             ops.pair_beam_tail(last[0], last[1], heads[0], heads[1], st, i)
         return st
+
+    def score_pairs(self, encoder_outputs, ys_l2r, ys_r2l, n_pos=None, group=1):
+        """Pair scores of S given token rows (include/sbl_hip.h, sbl_pair_score_tail): with lpL_i / lpR_i the two heads'
+        log-softmax at the last position of prefix length i + 1 of slot s - the pair fused exactly as `_run` and beam_search
+        fuse it - taken at ys_l2r[s][i+1] / ys_r2l[s][i+1]: logp[s, i] = (lpL_i, lpR_i) for i < n_pos[s], else 0; score_dir
+        their sums; score[s] = the sum of (lpL_i + lpR_i), both in ascending i in fp32 (the order of the beam search's totals:
+        with n_pos = 16 on beam_search's rows it is that search's score).  No length penalty, no prior.
+        ys_l2r / ys_r2l: int64 (S, 17) (or (N, group, 17)); encoder_outputs holds S / group clips and slot s belongs to clip
+        s // group; n_pos: None (16 positions) or int32 (S,).  All 16 prefixes of every slot go through ONE ragged stage
+        (segL = 1..16, 136 rows per slot and direction; cross-attention K/V shared by a clip's slots), then GatherLastFn, then
+        the tail kernel; beyond SCORE_PAIRS_MAX_ROWS rows the clips are taken in chunks of whole clips (the last one may be
+        shorter), whose size depends on the shapes alone.  Module mode is used as recognize_beam uses it; no host read, so the call is capturable as one hipGraph.
+        Returns PairScore(score (S,), score_dir (S, 2), logp (S, 16, 2), best (S / group,) int32 = the rank of the largest
+        score in every group, the lower rank on an exact tie)."""
+        enc = encoder_outputs
+        G = int(group)
+        if not enc.is_cuda:
+            raise _lib.SblHipError("Decoder.score_pairs needs the encoder output on the GPU (got a %s tensor); there is no "
+                                   "CPU path" % enc.device)
+        maxlen = config.MAX_DECODE_LEN
+        ys = [y.reshape(-1, maxlen + 1).contiguous() for y in (ys_l2r, ys_r2l)]
+        S, N = ys[0].size(0), enc.size(0)
+        if not 1 <= G <= MAX_PAIR_BEAM or S != N * G or ys[1].size(0) != S:
+            raise _lib.SblHipError("Decoder.score_pairs: %d and %d token rows for %d clips in groups of %d (1..%d)"
+                                   % (S, ys[1].size(0), N, G, MAX_PAIR_BEAM))
+        dev = enc.device
+        out = PairScore(torch.empty(S, device=dev), torch.empty(S, 2, device=dev), torch.empty(S, maxlen, 2, device=dev),
+                        torch.empty(N, dtype=torch.int32, device=dev))
+        segL = tuple(range(1, maxlen + 1))
+        clips = max(1, SCORE_PAIRS_MAX_ROWS // (sum(segL) * G))      # clips per chunk
+        heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
+        with torch.no_grad():
+            for c0 in range(0, N, clips):
+                c1 = min(N, c0 + clips)
+                s0, s1 = c0 * G, c1 * G
+                layers, main, side, kv = self._begin(enc[c0:c1])
+                tok = [y[s0:s1] for y in ys]
+                x = self._stage(tok, s1 - s0, segL, layers, main, side, kv, kv_group=G)
+                last = [ops.GatherLastFn.apply(x[d], s1 - s0, segL) for d in (0, 1)]
+                ops.pair_score_tail(last[0], last[1], heads[0], heads[1], tok[0], tok[1], None if n_pos is None else n_pos[s0:s1], G,
+                                    out.logp[s0:s1], out.score_dir[s0:s1], out.score[s0:s1], out.best[c0:c1])
+        return out
+
+    def recognize_words(self, encoder_outputs, lexicon, beam_size=None, nbest=1, shortlist=8):
+        """Closed-vocabulary decode: the word of `lexicon` (transformer.lexicon.Lexicon) for every clip, in two passes on the
+        device.  Hypotheses: the greedy pair of recognize_beam (beam_size = None, H = 1) or the nbest pairs of
+        beam_search(beam_size, nbest) (H = nbest).  Shortlist (sbl_lexicon_shortlist): D(h, w) = lev(p_l, w) +
+        lev(p_r, reversed(w)) with p_l / p_r the hypothesis rows cut before the first eos; a word's key is its smallest (D, h)
+        and the K = shortlist words with the smallest (D, h, w) are kept.  Rescoring: score_pairs(group = K) on the candidates'
+        token rows over their c_w + 1 trained positions; the word is the candidate with the largest score (the lower rank on
+        an exact tie).  No host read: capturable as one hipGraph.
+        Returns WordResult(word (N,) int64, cand, cand_dist, cand_hyp (N, K) int32, score (N, K), score_dir (N, K, 2))."""
+        enc = encoder_outputs
+        K = int(shortlist)
+        if not enc.is_cuda:
+            raise _lib.SblHipError("Decoder.recognize_words needs the encoder output on the GPU (got a %s tensor); there is no "
+                                   "CPU path" % enc.device)
+        if not 1 <= K <= min(len(lexicon), ops.LEXICON_MAX_SHORTLIST):
+            raise _lib.SblHipError("Decoder.recognize_words: shortlist = %d outside 1..min(%d words, %d)"
+                                   % (K, len(lexicon), ops.LEXICON_MAX_SHORTLIST))
+        if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
+            raise _lib.SblHipError("Decoder.recognize_words: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
+                                   % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+        if beam_size is None:
+            ys_l, ys_r = self.recognize_beam(enc)
+        else:
+            res = self.beam_search(enc, beam_size, nbest)
+            ys_l, ys_r = res.ys_l2r, res.ys_r2l
+        N = enc.size(0)
+        sl = ops.lexicon_shortlist(ys_l, ys_r, lexicon.packed, K, self.sos_id, self.eos_id, IGNORE_ID)
+        ps = self.score_pairs(enc, sl.cand_ys_l2r, sl.cand_ys_r2l, sl.n_pos, group=K)
+        word = sl.cand.gather(1, ps.best.long().unsqueeze(1)).squeeze(1).long()
+        return WordResult(word, sl.cand, sl.cand_dist, sl.cand_hyp, ps.score.view(N, K), ps.score_dir.view(N, K, 2))
 
 
 class DecoderLayer(nn.Module):

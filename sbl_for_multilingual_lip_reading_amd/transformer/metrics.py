@@ -78,6 +78,61 @@ class ErrorRateMeter:
         return out
 
 
+class WordAccuracyMeter:
+    """Word accuracy of closed-vocabulary decodes (Transformer.validate_words) over an epoch: int64 device counters
+    n (clips), n_correct (word == gold_word) and n_in_shortlist (gold_word is among the shortlisted candidates, the ceiling of
+    what rescoring can reach).  Integer torch ops on the device; update() does not synchronise and, after the first call of
+    a batch shape, allocates nothing (the work buffers of every batch shape seen are kept), so it can be captured with the
+    decode.  All state is integer: it sums exactly across calls, replays and ranks."""
+
+    def __init__(self, device=None):
+        self.device = torch.device(config.device if device is None else device)
+        self.acc = torch.zeros(3, dtype=torch.int64, device=self.device)      # n, n_correct, n_in_shortlist
+        self._bufs = {}      # (N, K) -> work buffers, never dropped: a captured graph keeps writing into the ones it saw
+
+    def _buffers(self, N, K):
+        if (N, K) not in self._bufs:
+            b = lambda *s: torch.empty(*s, dtype=torch.bool, device=self.device)      # noqa: E731
+            rows = torch.arange(N, dtype=torch.int32, device=self.device)
+            self._bufs[N, K] = (rows, b(N), b(N), b(N, K), b(N), torch.zeros(3, dtype=torch.int64, device=self.device))
+        return self._bufs[N, K]
+
+    def update(self, result, gold_word, valid_rows=None):
+        """Add one batch: result = the WordResult of recognize_words, gold_word int64 (N,) word indices on the device.
+        valid_rows: None or a device int32[1]; rows at or beyond it are ignored."""
+        N, K = result.cand.shape
+        if gold_word.shape != (N,) or gold_word.dtype != torch.int64:
+            raise ValueError("WordAccuracyMeter.update: gold_word must be int64 (%d,), got %s %s" % (N, gold_word.dtype, tuple(gold_word.shape)))
+        if valid_rows is not None and (valid_rows.dtype != torch.int32 or valid_rows.numel() != 1):
+            raise ValueError("WordAccuracyMeter.update: valid_rows must be an int32[1] tensor")
+        rows, live, hit, among, inside, add = self._buffers(N, K)
+        if valid_rows is None:
+            live.fill_(True)
+        else:
+            torch.lt(rows, valid_rows.view(1), out=live)
+        torch.eq(result.word, gold_word, out=hit)
+        hit.logical_and_(live)
+        torch.eq(result.cand, gold_word.unsqueeze(1), out=among)
+        torch.any(among, 1, out=inside)
+        inside.logical_and_(live)
+        for k, t in enumerate((live, hit, inside)):
+            torch.sum(t, 0, dtype=torch.int64, out=add[k])
+        self.acc.add_(add)
+
+    def all_reduce(self, group=None):
+        """Sum the counters over the ranks of a torch.distributed group, as ErrorRateMeter.all_reduce does."""
+        torch.distributed.all_reduce(self.acc, op=torch.distributed.ReduceOp.SUM, group=group)
+
+    def reset(self):
+        self.acc.zero_()
+
+    def result(self):
+        """The one synchronisation: {"n", "n_correct", "n_in_shortlist", "accuracy", "shortlist_recall"} (nan without clips)."""
+        n, ok, among = self.acc.cpu().tolist()
+        nan = float("nan")
+        return dict(n=n, n_correct=ok, n_in_shortlist=among, accuracy=ok / n if n else nan, shortlist_recall=among / n if n else nan)
+
+
 def wer_per(ys_l2r, ys_r2l, gold_l2r, gold_r2l, names=None):
     """One-shot scoring of a batch: (l2r_wer, l2r_per, r2l_wer, r2l_per), the order valid_lrw returns (train.py:286)."""
     meter = ErrorRateMeter(names, device=ys_l2r.device)

@@ -59,3 +59,18 @@ class Transformer(nn.Module):
             ys_l2r, ys_r2l = self.recognize(padded_input)
         meter.update(ys_l2r, ys_r2l, padded_target_l2r, padded_target_r2l, valid_rows=valid_rows)
         return ys_l2r, ys_r2l
+
+    def recognize_words(self, input, lexicon, beam_size=None, nbest=1, shortlist=8):
+        """Closed-vocabulary decode of (N, T, H, W) crops (or ops.RawClips): Decoder.recognize_words on the encoder output ->
+        WordResult, the lexicon word of every clip with its shortlist and the shortlist's pair scores."""
+        enc, _ = self._encode(input)
+        return self.decoder.recognize_words(enc, lexicon, beam_size=beam_size, nbest=nbest, shortlist=shortlist)
+
+    def validate_words(self, padded_input, gold_word, lexicon, meter, valid_rows=None, beam_size=None, nbest=1, shortlist=8):
+        """One validation batch of a closed-vocabulary benchmark: recognize_words, then `meter` (metrics.WordAccuracyMeter)
+        counts the clips whose word is gold_word (N,) int64 - word indices into `lexicon`, as Lexicon.from_targets returns
+        them - and those whose shortlist holds it.  No host sync: in eval() under torch.no_grad() the call is capturable as
+        one hipGraph; `valid_rows` (device int32[1]) masks the tail of a short last batch.  Returns the WordResult."""
+        res = self.recognize_words(padded_input, lexicon, beam_size=beam_size, nbest=nbest, shortlist=shortlist)
+        meter.update(res, gold_word, valid_rows=valid_rows)
+        return res
