@@ -283,6 +283,8 @@ int sbl_rowscale(const float* x, const float* s, float* y, long M, int D, sbl_st
  * contiguous 64-wide column blocks: attention.py:41-47); p_out is (H*B, Lq, Lk) head-major like
  * the reference's returned attn.  mask_kind: 0 none, 1 causal (key > query masked:
  * utils.py:116-124), 2 explicit uint8 (B,Lq,Lk), nonzero = masked.  Lq, Lk <= 64, d = 64.
+ * A query row whose keys are all masked gets p = 0 and o = 0 (the reference's softmax of such a row is NaN); in backward
+ * its dq row is 0 and it adds nothing to dk / dv.
  * Replaces attention.py:72-83. */
 int sbl_attention_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o, long ldo,
                       float* p_out, int mask_kind, const uint8_t* mask, int B, int H, int Lq, int Lk, float scale,
