@@ -14,9 +14,9 @@
 // dependence.
 //
 // sbl_pair_score_tail - one workgroup per group of G slots.  For every step the 2 G rows go through the heads and the
-// log-softmax of pair_head.h (the code of sbl_pair_beam_tail) and the log-probability of the slot's own token is kept; one lane
+// log-softmax of decode_head.h (the code of sbl_pair_beam_tail) and the log-probability of the slot's own token is kept; one lane
 // per slot then adds them in ascending step order, the order of the beam search's totals.
-#include "pair_head.h"
+#include "decode_head.h"
 
 #define LX_THREADS 1024
 #define LX_WAVES (LX_THREADS / 64)
@@ -206,12 +206,12 @@ __global__ __launch_bounds__(256) void pair_score_tail_kernel(
         // logits: each wave takes every fourth (direction, class) and keeps its weight row in registers
         for (int idx = wave; idx < 2 * V; idx += 4) {
             const int d = idx >= V, v = idx - d * V;
-            const float4* wr = reinterpret_cast<const float4*>((d ? w_r : w_l) + (long)v * PB_D);
+            const float4* wr = reinterpret_cast<const float4*>((d ? w_r : w_l) + (long)v * DH_D);
             const float4 a = wr[lane], c = wr[64 + lane];
             const float* y = d ? y_r : y_l;
             for (int r = 0; r < G; ++r) {
                 if (i >= s_np[r]) continue;      // (uniform)
-                const float acc = pb_row_dot(reinterpret_cast<const float4*>(y + ((long)i * S + slot0 + r) * ldy), a, c, lane);
+                const float acc = dh_row_dot(reinterpret_cast<const float4*>(y + ((long)i * S + slot0 + r) * ldy), a, c, lane);
                 if (lane == 0) s_lg[d][r][v] = acc;
             }
         }
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void pair_score_tail_kernel(
         for (int row = wave; row < 2 * G; row += 4) {
             const int d = row >= G, r = row - d * G;
             if (i >= s_np[r]) continue;          // (uniform)
-            const float lp = pb_log_softmax(lane < V ? s_lg[d][r][lane] : -INFINITY, lane < V);
+            const float lp = dh_log_softmax(lane < V ? s_lg[d][r][lane] : -INFINITY, lane < V);
             const int64_t tok = (d ? ys_r : ys_l)[(slot0 + r) * ldys + i + 1];
             const bool inside = tok >= 0 && tok < V;      // a token that is no class has no probability
             const float mine = __shfl(lp, inside ? (int)tok : 0, 64);
@@ -258,8 +258,8 @@ __global__ __launch_bounds__(256) void pair_score_tail_kernel(
 extern "C" int sbl_pair_score_tail(const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r,
                                    const int64_t* ys_l2r, const int64_t* ys_r2l, long ldys, const int32_t* n_pos, float* logp,
                                    float* score_dir, float* score, int32_t* best, int S, int G, int V, int D, sbl_stream_t stream) {
-    SBL_REQUIRE(D == PB_D, "sbl_pair_score_tail: D=%d (built for %d)", D, PB_D);
-    SBL_REQUIRE(V >= 1 && V <= PB_MAX_V, "sbl_pair_score_tail: V=%d (V <= %d)", V, PB_MAX_V);
+    SBL_REQUIRE(D == DH_D, "sbl_pair_score_tail: D=%d (built for %d)", D, DH_D);
+    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "sbl_pair_score_tail: V=%d (V <= %d)", V, DH_MAX_V);
     SBL_REQUIRE(G >= 1 && G <= PS_MAX_G, "sbl_pair_score_tail: group G=%d outside 1..%d", G, PS_MAX_G);
     SBL_REQUIRE(S >= 0 && S % G == 0, "sbl_pair_score_tail: S=%d slots are no multiple of the group size %d", S, G);
     SBL_REQUIRE((long)S * PS_STEPS <= (1L << 30), "sbl_pair_score_tail: S=%d", S);

@@ -158,6 +158,7 @@ extern "C" int sbl_gather_last_bwd(const float* dy, float* dx, int B, const int*
 
 // ------------------------------------------------------------------ token feedback: decoder.py:173-186
 // one wavefront per batch row; argmax returns the FIRST maximal index (torch.argmax tie-break on CPU)
+// (the butterfly is dh_wave_best of decode_head.h minus its NONE tests; kept apart: this kernel is on the training step)
 __global__ __launch_bounds__(256) void argmax_select_kernel(const float* __restrict__ pred, long ldp,
                                                             const int64_t* __restrict__ gold, long ldg,
                                                             int64_t* __restrict__ ys, long ldy, int step, int use_argmax,

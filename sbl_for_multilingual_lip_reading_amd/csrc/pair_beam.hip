@@ -18,24 +18,7 @@
 //      the kernel reads the parents' rows), and the (step, rank) history.
 // A candidate of total -inf (or NaN) is never kept; a rank without a candidate gets the scores -inf, <eos> tokens and its own
 // rank as parent.
-#include "pair_head.h"
-
-#define PB_MAX_W 16
-#define PB_NONE 0x7fffffff
-
-// (value, index) maximum over the wave with the lower index on equal values; PB_NONE = nothing to offer.  Every lane ends
-// with the same pair.
-__device__ __forceinline__ void pb_wave_best(float& best, int& bi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (oi != PB_NONE && (bi == PB_NONE || ov > best || (ov == best && oi < bi))) {
-            best = ov;
-            bi = oi;
-        }
-    }
-}
+#include "decode_head.h"
 
 // grid N, 256 threads.  Slot n*W + r is beam position r of clip n.
 __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
@@ -44,11 +27,11 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
     const int64_t* __restrict__ ys_old_r, int64_t* __restrict__ ys_new_l, int64_t* __restrict__ ys_new_r, long ldys,
     int32_t* __restrict__ hist_tok_l, int32_t* __restrict__ hist_tok_r, int32_t* __restrict__ hist_par,
     float* __restrict__ hist_score, int step, int maxlen, int eos, int W, int V) {
-    __shared__ float s_lp[2][PB_MAX_W][64];                  // [direction][slot][class]: logits
-    __shared__ float s_top[2][PB_MAX_W][PB_MAX_W];           // [direction][slot][rank]: log-prob of the slot's rank-th class
-    __shared__ int s_ttok[2][PB_MAX_W][PB_MAX_W];            // ... and the class
-    __shared__ float s_sc[PB_MAX_W], s_sd[2][PB_MAX_W];      // the slots' scores on entry
-    __shared__ int s_par[PB_MAX_W], s_tok[2][PB_MAX_W];
+    __shared__ float s_lp[2][DH_MAX_W][64];                  // [direction][slot][class]: logits
+    __shared__ float s_top[2][DH_MAX_W][DH_MAX_W];           // [direction][slot][rank]: log-prob of the slot's rank-th class
+    __shared__ int s_ttok[2][DH_MAX_W][DH_MAX_W];            // ... and the class
+    __shared__ float s_sc[DH_MAX_W], s_sd[2][DH_MAX_W];      // the slots' scores on entry
+    __shared__ int s_par[DH_MAX_W], s_tok[2][DH_MAX_W];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x;
     const long slot0 = (long)n * W;
@@ -61,11 +44,11 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
     // logits of the clip's 2 * W rows: each wave takes every fourth (direction, class) and keeps its weight row in registers
     for (int idx = wave; idx < 2 * V; idx += 4) {
         const int d = idx >= V, v = idx - d * V;
-        const float4* wr = reinterpret_cast<const float4*>((d ? w_r : w_l) + (long)v * PB_D);
+        const float4* wr = reinterpret_cast<const float4*>((d ? w_r : w_l) + (long)v * DH_D);
         const float4 a = wr[lane], c = wr[64 + lane];
         const float* y = d ? y_r : y_l;
         for (int r = 0; r < W; ++r) {
-            const float acc = pb_row_dot(reinterpret_cast<const float4*>(y + (slot0 + r) * ldy), a, c, lane);
+            const float acc = dh_row_dot(reinterpret_cast<const float4*>(y + (slot0 + r) * ldy), a, c, lane);
             if (lane == 0) s_lp[d][r][v] = acc;
         }
     }
@@ -74,16 +57,16 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
     for (int row = wave; row < 2 * W; row += 4) {
         const int d = row >= W, r = row - d * W;
         const float l = lane < V ? s_lp[d][r][lane] : -INFINITY;
-        const float lp = pb_log_softmax(l, lane < V);
+        const float lp = dh_log_softmax(l, lane < V);
         bool used = lane >= V;
         float top = -INFINITY;
         int ttok = eos;
         for (int k = 0; k < W; ++k) {
             float best = used ? -INFINITY : lp;
-            int bi = used ? PB_NONE : lane;
-            pb_wave_best(best, bi);
+            int bi = used ? DH_NONE : lane;
+            dh_wave_best(best, bi);
             if (bi == lane) used = true;
-            if (lane == k && bi != PB_NONE) {
+            if (lane == k && bi != DH_NONE) {
                 top = best;
                 ttok = bi;
             }
@@ -117,22 +100,22 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
             }
         }
         float my_sc = -INFINITY;
-        int my_idx = PB_NONE;
+        int my_idx = DH_NONE;
         for (int r = 0; r < W; ++r) {
             float best = -INFINITY;
-            int bi = PB_NONE;
+            int bi = DH_NONE;
 #pragma unroll
             for (int q = 0; q < 4; ++q)
                 if (head[q] > best) {
                     best = head[q];
                     bi = (lane + 64 * q) * W + ptr[q];
                 }
-            pb_wave_best(best, bi);
+            dh_wave_best(best, bi);
             if (lane == r) {
                 my_sc = best;
                 my_idx = bi;
             }
-            if (bi != PB_NONE) {
+            if (bi != DH_NONE) {
                 const int t = bi / W;
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
             }
         }
         if (lane < W) {
-            const bool kept = my_idx != PB_NONE;
+            const bool kept = my_idx != DH_NONE;
             int par = lane, tl = eos, tr = eos;
             float sl = -INFINITY, sr = -INFINITY;
             if (kept) {
@@ -193,9 +176,9 @@ extern "C" int sbl_pair_beam_tail(const float* y_l, const float* y_r, long ldy, 
                                   int64_t* ys_new_r, long ldys, int32_t* hist_tok_l, int32_t* hist_tok_r, int32_t* hist_par,
                                   float* hist_score, int step, int maxlen, int eos, int N, int W, int V, int D,
                                   sbl_stream_t stream) {
-    SBL_REQUIRE(D == PB_D, "sbl_pair_beam_tail: D=%d (built for %d)", D, PB_D);
-    SBL_REQUIRE(V >= 1 && V <= PB_MAX_V, "sbl_pair_beam_tail: V=%d (V <= %d)", V, PB_MAX_V);
-    SBL_REQUIRE(W >= 1 && W <= PB_MAX_W, "sbl_pair_beam_tail: beam W=%d outside 1..%d", W, PB_MAX_W);
+    SBL_REQUIRE(D == DH_D, "sbl_pair_beam_tail: D=%d (built for %d)", D, DH_D);
+    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "sbl_pair_beam_tail: V=%d (V <= %d)", V, DH_MAX_V);
+    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_pair_beam_tail: beam W=%d outside 1..%d", W, DH_MAX_W);
     SBL_REQUIRE(W <= V, "sbl_pair_beam_tail: beam W=%d above V=%d", W, V);
     SBL_REQUIRE(N > 0 && maxlen >= 1 && step >= 0 && step < maxlen, "sbl_pair_beam_tail: N=%d, step %d of %d", N, step, maxlen);
     SBL_REQUIRE(eos >= 0 && eos < V, "sbl_pair_beam_tail: eos=%d outside the %d classes", eos, V);

@@ -1959,20 +1959,33 @@ class EmbedScalePEFn(torch.autograd.Function):
         return None, demb_ret, None, None
 
 
+def _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale):
+    """The stride checks and the call behind decode_attn_step (W = None: every row owns its cache) and beam_attn_step."""
+    S = q.size(0)
+    ldc = k_cache.stride(-2)
+    nc = S if append or W is None else S // W
+    assert v_cache.stride(-2) == ldc and k_cache.stride(-1) == 1 and q.stride(1) == 1 and out.stride(1) == 1
+    assert k_cache.dim() == 3 and k_cache.size(0) == nc and k_cache.size(1) == Lcap and k_cache.stride(0) == Lcap * ldc
+    assert v_cache.shape == k_cache.shape and v_cache.stride(0) == Lcap * ldc and out.size(0) == S
+    if append:
+        assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
+    head = (_p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache), _p(v_cache), ldc, Lcap)
+    tail = (H, int(n_prev), int(bool(append)), scale, _s())
+    if W is None:
+        call("sbl_decode_attn_step", *head, _p(out), out.stride(0), S, *tail)
+    else:
+        if append:
+            assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.size(0) == S and anc.stride(1) == 1
+        call("sbl_beam_attn_step", *head, _p(anc) if append else None, anc.stride(0) if append else 0, _p(out), out.stride(0), S,
+             int(W), *tail)
+    return out
+
+
 def decode_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append, scale=0.125):
     """One (clip, head) wavefront each: the single new query row attends to the cache (include/sbl_hip.h,
     sbl_decode_attn_step).  q / k_new / v_new / out: (B, H*64) row views (column slices of wider buffers are fine);
     k_cache / v_cache: views whose first element is row 0 of clip 0, row stride .stride(-2), batch stride Lcap rows."""
-    B = q.size(0)
-    ldc = k_cache.stride(-2)
-    assert v_cache.stride(-2) == ldc and k_cache.stride(-1) == 1 and q.stride(1) == 1 and out.stride(1) == 1
-    assert k_cache.dim() == 3 and k_cache.size(0) == B and k_cache.size(1) == Lcap and k_cache.stride(0) == Lcap * ldc
-    assert v_cache.shape == k_cache.shape and v_cache.stride(0) == Lcap * ldc
-    if append:
-        assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
-    call("sbl_decode_attn_step", _p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache),
-         _p(v_cache), ldc, Lcap, _p(out), out.stride(0), B, H, int(n_prev), int(bool(append)), scale, _s())
-    return out
+    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, None, out, None, H, n_prev, append, scale)
 
 
 def decode_tail(y, w, ys, step, emb, pe, emb_scale, x_next=None, logits=None):
@@ -1990,19 +2003,7 @@ def beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_pr
     """decode_attn_step for beam slots (include/sbl_hip.h, sbl_beam_attn_step): q / k_new / v_new / out are (S, H*64) row views,
     S = clips * W.  append: k_cache / v_cache (S, Lcap, H*64) and anc (S, >= n_prev) int32 names the cache slot of every key;
     otherwise (cross-attention) k_cache / v_cache hold S / W clips and anc is None."""
-    S = q.size(0)
-    ldc = k_cache.stride(-2)
-    nc = S if append else S // W
-    assert v_cache.stride(-2) == ldc and k_cache.stride(-1) == 1 and q.stride(1) == 1 and out.stride(1) == 1
-    assert k_cache.dim() == 3 and k_cache.size(0) == nc and k_cache.size(1) == Lcap and k_cache.stride(0) == Lcap * ldc
-    assert v_cache.shape == k_cache.shape and v_cache.stride(0) == Lcap * ldc and out.size(0) == S
-    if append:
-        assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
-        assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.size(0) == S and anc.stride(1) == 1
-    call("sbl_beam_attn_step", _p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache),
-         _p(v_cache), ldc, Lcap, _p(anc) if append else None, anc.stride(0) if append else 0, _p(out), out.stride(0), S, int(W), H,
-         int(n_prev), int(bool(append)), scale, _s())
-    return out
+    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale)
 
 
 class BeamState(object):

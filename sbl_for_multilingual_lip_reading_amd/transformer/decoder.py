@@ -224,6 +224,11 @@ class Decoder(nn.Module):
             x[0], x[1] = ops.FusionFn.apply(x[0], x[1], B, segL)
         return x
 
+    def _stage_last(self, ys, B, segL, layers, main, side, kv, kv_group=None):
+        """`_stage`, then position -1 of every prefix: per direction the (len(segL) * B, d_model) rows the heads read."""
+        x = self._stage(ys, B, segL, layers, main, side, kv, kv_group)
+        return [ops.GatherLastFn.apply(x[d], B, segL) for d in (0, 1)]
+
     def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode):
         """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383)."""
         maxlen = config.MAX_DECODE_LEN
@@ -255,10 +260,9 @@ class Decoder(nn.Module):
             encoder_outputs.register_hook(lambda g: ops.flush_deferred())
         for (i0, i1) in stages:
             segL = tuple(range(i0 + 1, i1 + 2))            # prefix lengths of the steps in this stage
-            x = self._stage(ys, N, segL, layers, main, side, kv)
+            last = self._stage_last(ys, N, segL, layers, main, side, kv)     # (nseg*N, 512) per direction
             for d in (0, 1):
-                last = ops.GatherLastFn.apply(x[d], N, segL)           # (nseg*N, 512): position -1 of every prefix
-                pred = ops.linear(last, heads[d])                      # (nseg*N, 58)
+                pred = ops.linear(last[d], heads[d])                   # (nseg*N, 58)
                 # unbind (one stack in backward) instead of row slices (a zero-filled (nseg*N, 58) buffer, a copy and
                 # an add per step in backward)
                 for step, pr in zip(range(i0, i1 + 1), pred.view(len(segL), N, -1).unbind(0)):
@@ -341,9 +345,7 @@ class Decoder(nn.Module):
         st = ops.PairBeamState(N, W, maxlen, self.sos_id, self.eos_id, encoder_outputs.device)
         heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
         for i in range(maxlen):
-            segL = (i + 1,)
-            x = self._stage(st.prefixes(i), S, segL, layers, main, side, kv, kv_group=W)
-            last = [ops.GatherLastFn.apply(x[d], S, segL) for d in (0, 1)]
+            last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W)
             ops.pair_beam_tail(last[0], last[1], heads[0], heads[1], st, i)
         return st
 
@@ -383,8 +385,7 @@ class Decoder(nn.Module):
                 s0, s1 = c0 * G, c1 * G
                 layers, main, side, kv = self._begin(enc[c0:c1])
                 tok = [y[s0:s1] for y in ys]
-                x = self._stage(tok, s1 - s0, segL, layers, main, side, kv, kv_group=G)
-                last = [ops.GatherLastFn.apply(x[d], s1 - s0, segL) for d in (0, 1)]
+                last = self._stage_last(tok, s1 - s0, segL, layers, main, side, kv, kv_group=G)
                 ops.pair_score_tail(last[0], last[1], heads[0], heads[1], tok[0], tok[1], None if n_pos is None else n_pos[s0:s1], G,
                                     out.logp[s0:s1], out.score_dir[s0:s1], out.score[s0:s1], out.best[c0:c1])
         return out

@@ -21,7 +21,7 @@ from .video_frontend import Lipreading
 IGNORE_ID = config.IGNORE_ID
 MAX_TGT_LEN = 14          # pad_list's fixed max_len (LRW/transformer/utils.py:5): <sos> + at most 13 tokens
 MAX_KEYS = 64             # one key per lane in the decode-step attention; the teacher-forced kernels share the bound
-MAX_BEAM = 16             # slots per clip in the beam tail (csrc/beam_step.hip); nbest has the same bound
+MAX_BEAM = 16             # slots per clip in the beam tail (csrc/decode_head.h); nbest has the same bound
 
 # beam_search's result: yseq (N, nbest, maxlen+2) int64 (<sos>, tokens, eos-filled behind the end), lengths (N, nbest) int32,
 # scores (N, nbest) fp32, n_hyps (N) int32 (ranks beyond it: length 0, score -inf), history = the per-(clip, step, rank)
@@ -188,40 +188,48 @@ class Seq2SeqDecoder(nn.Module):
             ops.argmax_select(ops.linear(x[:, -1], w), None, ys, i, 1)
         return ys
 
-    def _greedy_cached(self, enc):
-        if self.training and self.dropout.p > 0:
-            raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+    def _cached_steps(self, enc, rows, steps, tok0, attn, tail):
+        """The KV-cached step loop under the greedy decode and the beam search: `rows` rows per step (the clips, or their
+        beam slots) for `steps` steps.  One GEMM for the cross-attention K / V of all layers, the first input row from the
+        (rows, >= 1) token table tok0, then per step and layer the 11 launches of DESIGN.md section 4.4 and the tail;
+        nothing is read back.  attn(step, ...) takes the arguments of ops.decode_attn_step; tail(y, w, step, emb, pe, scale,
+        x_next) ends a step (x_next: the next step's input rows, None at the last one)."""
         N, T, D = enc.shape
-        dev = enc.device
         layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
         nl, H = len(layers), self.n_head
         HD, F_ = H * 64, self.d_inner
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+        new = lambda *shape: torch.empty(*shape, device=enc.device, dtype=torch.float32)      # noqa: E731
 
-        # the K / V of the encoder output for all layers: one GEMM against the [K_0; V_0; K_1; ...] block
+        # the K / V of the encoder output for all layers: one GEMM against the [K_0; V_0; K_1; ...] block, over the N clips
         kv = [blk.view(N, T, 2 * HD) for blk in ops.project_kv_block(enc.contiguous().view(N * T, D), self.cross_attention_modules())[2]]
-        cache = new(nl, 2, N, T, HD)          # self-attention K / V rows of every layer; row i is written at step i
-        ys = self._new_ys(enc)
+        cache = new(nl, 2, rows, steps, HD)   # self-attention K / V rows of every layer; row i of a cache is written at step i
         emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
         V, scale = emb.size(0), float(self.x_logit_scale)
-        x = new(N, D)
-        ops.call("sbl_embed_scale_pe_fwd", ops._p(ys), ys.stride(0), ops._p(emb), ops._p(pe), ops._p(x), N, 1, D, V, scale, 0, ops._s())
-        qkv, q, att, o, h = new(N, 3 * HD), new(N, HD), new(N, HD), new(N, D), new(N, F_)
-        ya, yb, yc = new(N, D), new(N, D), new(N, D)
-        mean, rstd = new(N), new(N)
+        x = new(rows, D)
+        ops.call("sbl_embed_scale_pe_fwd", ops._p(tok0), tok0.stride(0), ops._p(emb), ops._p(pe), ops._p(x), rows, 1, D, V, scale, 0, ops._s())
+        qkv, q, att, o, h = new(rows, 3 * HD), new(rows, HD), new(rows, HD), new(rows, D), new(rows, F_)
+        ya, yb, yc = new(rows, D), new(rows, D), new(rows, D)
+        mean, rstd = new(rows), new(rows)
 
-        for i in range(T):
+        for i in range(steps):
             cur = x
             for l, (sa, ca, ff) in enumerate(layers):
                 ops.lin_fwd(sa.inp, cur, qkv)
-                ops.decode_attn_step(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], T, att, H, i, True)
+                attn(i, qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], steps, att, H, i, True)
                 ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
                 ops.lin_fwd(ca.inp, ya, q)
-                ops.decode_attn_step(q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
+                attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
                 ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
                 ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
                 cur = yc
-            ops.decode_tail(cur, w, ys, i, emb, pe, scale, x_next=x if i + 1 < T else None)
+            tail(cur, w, i, emb, pe, scale, x if i + 1 < steps else None)
+
+    def _greedy_cached(self, enc):
+        if self.training and self.dropout.p > 0:
+            raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+        ys = self._new_ys(enc)
+        self._cached_steps(enc, enc.size(0), enc.size(1), ys, lambda i, *a: ops.decode_attn_step(*a),
+                           lambda y, w, i, *head: ops.decode_tail(y, w, ys, i, *head))
         return ys
 
     # ------------------------------------------------------------------ beam search
@@ -257,40 +265,16 @@ class Seq2SeqDecoder(nn.Module):
             return self._beam_cached(enc, W, nbest, maxlen, None if log_prior is None else log_prior.contiguous())
 
     def _beam_cached(self, enc, W, nbest, maxlen, log_prior):
-        N, T, D = enc.shape
-        dev = enc.device
-        S = N * W
-        layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
-        nl, H = len(layers), self.n_head
-        HD, F_ = H * 64, self.d_inner
-        new = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float32)      # noqa: E731
+        S = enc.size(0) * W       # the W slots of a clip read the clip's cross-attention K / V
+        st = ops.BeamState(enc.size(0), W, maxlen, self.sos_id, enc.device)
+        tok0 = torch.full((S, 1), self.sos_id, dtype=torch.long, device=enc.device)
 
-        # cross-attention K / V of all layers: one GEMM over the N clips; the W slots of a clip read the same rows
-        kv = [blk.view(N, T, 2 * HD) for blk in ops.project_kv_block(enc.contiguous().view(N * T, D), self.cross_attention_modules())[2]]
-        cache = new(nl, 2, S, maxlen, HD)     # row i of slot b is written at step i by whatever hypothesis lives in b then
-        st = ops.BeamState(N, W, maxlen, self.sos_id, dev)
-        emb, pe, w = self.tgt_word_emb.weight, self.positional_encoding.pe[0], self.tgt_word_prj.weight
-        V, scale = emb.size(0), float(self.x_logit_scale)
-        x = new(S, D)
-        tok0 = torch.full((S, 1), self.sos_id, dtype=torch.long, device=dev)
-        ops.call("sbl_embed_scale_pe_fwd", ops._p(tok0), 1, ops._p(emb), ops._p(pe), ops._p(x), S, 1, D, V, scale, 0, ops._s())
-        qkv, q, att, o, h = new(S, 3 * HD), new(S, HD), new(S, HD), new(S, D), new(S, F_)
-        ya, yb, yc = new(S, D), new(S, D), new(S, D)
-        mean, rstd = new(S), new(S)
+        def attn(i, q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append):
+            # row i of slot b's cache is written at step i by whatever hypothesis lives in b then
+            ops.beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, st.anc[i % 2] if append else None, out, W, H, n_prev, append)
 
-        for i in range(maxlen):
-            cur = x
-            anc = st.anc[i % 2]
-            for l, (sa, ca, ff) in enumerate(layers):
-                ops.lin_fwd(sa.inp, cur, qkv)
-                ops.beam_attn_step(qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], maxlen, anc, att, W, H, i, True)
-                ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
-                ops.lin_fwd(ca.inp, ya, q)
-                ops.beam_attn_step(q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, None, att, W, H, T, False)
-                ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
-                ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
-                cur = yc
-            ops.beam_tail(cur, w, log_prior, st, i, self.eos_id, emb, pe, scale, x_next=x if i + 1 < maxlen else None)
+        self._cached_steps(enc, S, maxlen, tok0, attn,
+                           lambda y, w, i, *head: ops.beam_tail(y, w, log_prior, st, i, self.eos_id, *head))
         return BeamResult(*ops.beam_finish(st, nbest, self.eos_id), st.history())
 
 
@@ -352,12 +336,10 @@ class Seq2SeqTransformer(nn.Module):
         IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device; capturable like recognize.  Returns ys.
         With beam_size the decode is the beam search (log_prior as in Seq2SeqDecoder.beam_search) and ys its 1-best yseq
         (N, T + 2), whose eos padding the scorer strips like the greedy rows' tail."""
-        if beam_size is not None:
-            enc, _ = self._encode(padded_input)
-            ys = self.decoder.beam_search(enc, beam_size, 1, 0, log_prior).yseq[:, 0]
-            meter.update_single(ys, padded_target, valid_rows=valid_rows)
-            return ys
-        ys = self.recognize(padded_input)
+        if beam_size is None:
+            ys = self.recognize(padded_input)
+        else:
+            ys = self.decoder.beam_search(self._encode(padded_input)[0], beam_size, 1, 0, log_prior).yseq[:, 0]
         meter.update_single(ys, padded_target, valid_rows=valid_rows)
         return ys
 

@@ -1,4 +1,5 @@
-"""GPU checks of the batched beam search (csrc/beam_step.hip, Seq2SeqDecoder.beam_search): the three kernels alone against
+"""GPU checks of the batched beam search (csrc/beam_step.hip, the slot instantiation of the step attention in
+csrc/decode_step.hip, Seq2SeqDecoder.beam_search): the three kernels alone against
 float64 / host restatements, the whole search against the reference's fixtures (tests/golden/beam_*.npz) and against the
 plain-torch restatement (tests/beam_oracle.py) on unseen inputs, beam 1 against the greedy fixtures, hipGraph replay, and
 the validate / recognize_nbest surface."""
@@ -61,6 +62,34 @@ def test_beam_attn_step_kernel(W, n_prev, Lcap):
     torch.cuda.synchronize()
     rep = kv.repeat_interleave(W, 0)
     assert maxdiff(out, ref(q, rep[:, :, :512], rep[:, :, 512:])) <= 1e-5 and torch.equal(kvd.cpu(), kv)
+
+
+@pytest.mark.parametrize("n_prev,append", [(0, True), (1, True), (63, True), (64, False)])
+def test_beam_attn_step_with_one_slot_is_the_decode_attn_step(n_prev, append):
+    """ops.beam_attn_step at W = 1 with the identity ancestry table against ops.decode_attn_step on the same seeded q, new
+    K / V row and cache contents: outputs and caches bitwise equal.  The edges of Lcap = 64: an empty cache, one key, the
+    last lane, and a full row without an append."""
+    from sbl_for_multilingual_lip_reading_amd import ops
+    nb, H, Lcap = 3, 8, 64
+    gen = torch.Generator().manual_seed(64 * n_prev + append)
+    qkv = torch.randn(nb, 3 * H * 64, generator=gen).cuda()
+    kc, vc = (torch.randn(nb, Lcap, H * 64, generator=gen) for _ in range(2))
+    anc = torch.arange(nb, dtype=torch.int32).unsqueeze(1).repeat(1, Lcap).cuda() if append else None
+    new = (qkv[:, 512:1024], qkv[:, 1024:]) if append else (None, None)
+    got = []
+    for slots in (False, True):
+        kd, vd = kc.cuda(), vc.cuda()
+        out = torch.full((nb, H * 64), float("nan"), device="cuda")
+        if slots:
+            ops.beam_attn_step(qkv[:, :512], new[0], new[1], kd, vd, Lcap, anc, out, 1, H, n_prev, append)
+        else:
+            ops.decode_attn_step(qkv[:, :512], new[0], new[1], kd, vd, Lcap, out, H, n_prev, append)
+        got.append((out, kd, vd))
+    torch.cuda.synchronize()
+    assert not bool(torch.isnan(got[0][0]).any())
+    for a, b in zip(*got):
+        assert torch.equal(a, b)
+    assert append or (torch.equal(got[0][1].cpu(), kc) and torch.equal(got[0][2].cpu(), vc))
 
 
 # --------------------------------------------------------------------------- tail

@@ -222,6 +222,32 @@ def test_decode_tail_kernel():
     assert maxdiff(xn, emb[tok] * 0.25 + pe[4]) < 1e-6
 
 
+def test_cached_decode_launch_sequences(monkeypatch):
+    """The library calls of one recognize_beam and one beam_search(W = 2) on a 2-layer decoder, N = 2, T = 3, in order, as
+    DESIGN.md section 4.4 lists them: the K/V block GEMM, the first-row embedding, then per step and layer QKV GEMM, step
+    attention (append), fc GEMM, add + LayerNorm, Q GEMM, step attention over the hoisted K/V, fc GEMM, add + LayerNorm, the
+    two FFN GEMMs, add + LayerNorm (11), then the tail; the beam search ends with its finish."""
+    from sbl_for_multilingual_lip_reading_amd import _lib, ops
+    from sbl_for_multilingual_lip_reading_amd.transformer.seq2seq import Seq2SeqDecoder
+    n_layers, N, T = 2, 2, 3
+    torch.manual_seed(11)
+    dec = Seq2SeqDecoder(0, 1, 42, 512, n_layers, 8, 64, 64, 512, 2048, dropout=0.1).to("cuda:0").eval()
+    enc = torch.randn(N, T, 512, device="cuda")
+    names = []
+    monkeypatch.setattr(ops, "call", lambda name, *a: names.append(name) or _lib.call(name, *a))
+
+    def expected(attn, tail):
+        gemm, ln = "sbl_gemm_f32", "sbl_add_layernorm_fwd"
+        layer = [gemm, attn, gemm, ln, gemm, attn, gemm, ln, gemm, gemm, ln]
+        return [gemm, "sbl_embed_scale_pe_fwd"] + T * (n_layers * layer + [tail])
+
+    dec.recognize_beam(enc)
+    assert names == expected("sbl_decode_attn_step", "sbl_decode_tail")
+    del names[:]
+    dec.beam_search(enc, 2)
+    assert names == expected("sbl_beam_attn_step", "sbl_beam_tail") + ["sbl_beam_finish"]
+
+
 def test_flat_model_adam_step_keeps_the_tie():
     """One FlatModel + FusedAdam step: the tied weight is updated once, from the sum of the embedding scatter-add and the
     projection's weight gradient, and both modules read the same storage afterwards."""
