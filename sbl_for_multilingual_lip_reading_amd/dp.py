@@ -102,25 +102,22 @@ class FlatModel:
                 self.ranges[seg] = (start, off)
         self.numel = total
         self.device_index = dev.index if dev.type == "cuda" else None
-        self._in_backward = False
         _ops().register_flat_model(self)
 
     def zero_grad(self):
         self.flat_grad.zero_()
 
     def begin_backward(self):
-        """Called by the FIRST tape node of every backward (ops._backward_enter; every sbl autograd Function's backward
-        goes through it), i.e. before any kernel of that backward has accumulated into the flat gradient: this is the only
-        point where a dropped `.grad` may be turned into a zeroed slice.  The reference loop zeroes between forward and
-        backward (SBL/train.py:195-196: forward, optimizer.zero_grad(), loss.backward()), so the tape nodes' forward-time
-        view of the buffers must stay valid and nothing may be zeroed once accumulation is under way."""
-        self._in_backward = True
-        torch.autograd.Variable._execution_engine.queue_callback(self._end_backward)
+        """Called by the first tape node of every backward pass (ops._backward_enter; every sbl autograd Function's backward
+        goes through it, and tells passes apart by the engine's graph-task id), i.e. before any kernel of that pass has
+        accumulated into the flat gradient: this is the only point where a dropped `.grad` may be turned into a zeroed slice.
+        The reference loop zeroes between forward and backward (SBL/train.py:195-196: forward, optimizer.zero_grad(),
+        loss.backward()), so the tape nodes' forward-time view of the buffers must stay valid and nothing may be zeroed once
+        accumulation is under way.  A pass nested in a node (torch.utils.checkpoint, autograd.grad) brings a second call
+        within one training step; that is harmless, `reattach` only acts on detached gradients.  Nothing is left to reset
+        when a pass ends, so a backward that raised does not keep the next one from being repaired."""
         if any(p.grad is not p._sbl_grad for p, _, _ in self.slots):
             self.reattach()
-
-    def _end_backward(self):
-        self._in_backward = False
 
     def reattach(self):
         """Repair after a foreign `zero_grad(set_to_none=True)` (torch.optim's default) or an assignment to `p.grad`: the
@@ -259,9 +256,7 @@ class GradientExchange:
             # the finished segment's merged weight-gradient GEMMs (decoder and encoder layers defer theirs) must be
             # issued before its all-reduce; idempotent
             _ops().flush_deferred()
-            side = _ops()._side_streams.get(cur.device_index)
-            if side is not None:
-                self.stream.wait_stream(side)       # trunk / deferred weight gradients are accumulated there
+            self.stream.wait_stream(_ops().side_stream(cur.device))     # trunk / deferred weight gradients are accumulated there
             self.stream.wait_stream(cur)
             with torch.cuda.stream(self.stream):
                 self._all_reduce(seg, g)

@@ -10,6 +10,7 @@ All Functions are hipGraph-capturable: no host sync, no host read of device data
 dropout seeds and teacher-forcing coins live in device memory.
 """
 import collections as _collections
+import contextlib as _contextlib
 import copy as _copy
 import ctypes as _ct
 import functools as _functools
@@ -53,35 +54,63 @@ def _p(t):
     return None if t is None else t.data_ptr()
 
 
+# What this module keeps per GPU, one record per device index (nn.DataParallel drives one replica per device, each from its
+# own thread): `dropout` (DropoutState), `side` / `main` (the second HIP stream and the one it forks from / joins to),
+# `zero_buf` / `zero_off` (the zero pool), `collectors` / `collectors_pass` (what flush_deferred() issues), and as the
+# key of _first_in_pass the pass whose end-of-backward side-stream join is queued (_arm_side_join).
+_devices = {}
+
+
+def _dev(of=None):
+    """The record of a torch.device, of a stream's device, or (None, or a device without an index) of the current device."""
+    idx = of.device_index if isinstance(of, torch.cuda.Stream) else getattr(of, "index", None)
+    if idx is None:
+        idx = torch.cuda.current_device()
+    if idx not in _devices:
+        _devices[idx] = _types.SimpleNamespace(dropout=None, side=None, main=None, zero_buf=None, zero_off=0,
+                                               collectors=[], collectors_pass=-1)
+    return _devices[idx]
+
+
+def _first_in_pass(obj):
+    """Is this the first time `obj` is met in the backward pass that is running?  Passes are told apart by the autograd
+    engine's graph-task id (monotonic; -1 outside a backward, where the answer is always yes), kept on `obj`, so nothing
+    has to be reset when a pass ends - or fails to end: the engine runs no end-of-backward callback of a pass that raised."""
+    cur = torch._C._current_graph_task_id()
+    if cur != -1 and getattr(obj, "_pass", None) == cur:
+        return False
+    obj._pass = cur
+    return True
+
+
 # One pooled memset per training step instead of one per convolution: the packed weight-gradient buffers (split-K float atomics
 # start from zero) and the BatchNorm-backward sums that ride on input-gradient epilogues are carved from a per-device pool
 # that StemFn.forward - the first node of a step - zeroes with a single launch.  A region is handed out at most once per
 # reset, so it still holds zeros when its kernel runs; without a reset in this process, or when the pool is used up, the
 # takers fall back to a buffer the C call zeroes itself.
 ZERO_POOL_BYTES = 64 << 20        # ResNet-18 trunk weights: 44.7 MB of fp32, + 0.2 MB of fp64 sums
-_ZERO_POOL = {}
 
 
 def zero_pool_reset(dev):
-    st = _ZERO_POOL.get(dev.index)
-    if st is None:
-        st = _ZERO_POOL[dev.index] = {"buf": torch.empty(ZERO_POOL_BYTES, dtype=torch.uint8, device=dev), "off": 0, "armed": False}
-    st["buf"].zero_()
-    st["off"], st["armed"] = 0, True
+    d = _dev(dev)
+    if d.zero_buf is None:
+        d.zero_buf = torch.empty(ZERO_POOL_BYTES, dtype=torch.uint8, device=dev)
+    d.zero_buf.zero_()
+    d.zero_off = 0
 
 
 def zero_pool_take(dev, shape, dtype):
     """A zero-filled tensor from the pool, or None (the caller then allocates and lets the C call zero its buffer)."""
-    st = _ZERO_POOL.get(dev.index)
+    d = _dev(dev)
     n = 1
-    for d in shape:
-        n *= d
+    for k in shape:
+        n *= k
     nbytes = n * torch.empty((), dtype=dtype).element_size()
-    if st is None or not st["armed"] or st["off"] + nbytes > ZERO_POOL_BYTES:
+    if d.zero_buf is None or d.zero_off + nbytes > ZERO_POOL_BYTES:
         return None
-    off = st["off"]
-    st["off"] = (off + nbytes + 255) & ~255
-    return st["buf"][off:off + nbytes].view(dtype).view(*shape)
+    off = d.zero_off
+    d.zero_off = (off + nbytes + 255) & ~255
+    return d.zero_buf[off:off + nbytes].view(dtype).view(*shape)
 
 
 def _zeros_or_empty(dev, shape, dtype):
@@ -131,43 +160,32 @@ class DropoutState:
         call("sbl_seed_bump", _p(self.seed), _s())
 
 
-_dropout_states = {}
-
-
 def dropout_state(device):
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-    st = _dropout_states.get(key)
-    if st is None:
-        st = _dropout_states[key] = DropoutState(device)
-    return st
-
-
-_side_streams = {}
+    d = _dev(device)
+    if d.dropout is None:
+        d.dropout = DropoutState(device)
+    return d.dropout
 
 
 def side_stream(device):
     """The per-device second HIP stream used to overlap the two decoder directions."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    st = _side_streams.get(idx)
-    if st is None:
+    d = _dev(device)
+    if d.side is None:
         # (stream priorities were measured and dropped: a low-priority side stream changes nothing, a high-priority
         # main stream captured into the hipGraph runs the step at 79 ms instead of 45)
-        st = _side_streams[idx] = torch.cuda.Stream(device=idx)
-    return st
-
-
-_main_streams = {}
+        d.side = torch.cuda.Stream(device=device)
+    return d.side
 
 
 def set_main_stream(stream):
     """Remember which stream the side stream forks from / joins to (per device)."""
-    _main_streams[stream.device_index] = stream
+    _dev(stream).main = stream
 
 
 def _on_side_stream():
     """The current stream when it is this device's side stream, else None."""
     cur = torch.cuda.current_stream()
-    side = _side_streams.get(cur.device_index)
+    side = _dev(cur).side
     return cur if side is not None and cur == side else None
 
 
@@ -186,40 +204,32 @@ def _xs_in(*ts):
 def _xs_out(*ts):
     """...and what it hands back (allocated on the side stream) is consumed on the main stream."""
     cur = _on_side_stream()
-    main = _main_streams.get(cur.device_index) if cur is not None else None
+    main = _dev(cur).main if cur is not None else None
     if main is not None:
         for t in ts:
             if t is not None:
                 t.record_stream(main)
 
 
-_side_join_state = {}      # per device: nn.DataParallel drives one replica per device from its own thread
-
-
-def _side_join_for_current_device():
-    return _side_join_state.setdefault(torch.cuda.current_device(), {"armed": False})
+def join_side_streams():
+    """Make the current stream wait for everything enqueued on the side stream (end of a step)."""
+    cur = torch.cuda.current_stream()
+    side = _dev(cur).side
+    if side is not None:
+        cur.wait_stream(side)
 
 
 def _arm_side_join():
-    """Once per backward: make the stream that finishes backward wait for the side stream."""
-    _side_join = _side_join_for_current_device()
-    if not _side_join["armed"]:
-        _side_join["armed"] = True
-
-        def join():
-            _side_join["armed"] = False
-            cur = torch.cuda.current_stream()
-            side = _side_streams.get(cur.device_index)
-            if side is not None and side != cur:
-                cur.wait_stream(side)
-        torch.autograd.Variable._execution_engine.queue_callback(join)
+    """Once per (device, backward pass): make the stream that finishes backward wait for the side stream."""
+    if _first_in_pass(_dev()):
+        torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
 
 
 def _side_to_main():
     """Explicit fence when a side-stream tape node hands its result to the main stream (belt and braces next to the
     autograd engine's own producer/consumer event)."""
     cur = _on_side_stream()
-    main = _main_streams.get(cur.device_index) if cur is not None else None
+    main = _dev(cur).main if cur is not None else None
     if main is not None:
         main.wait_stream(cur)
 
@@ -232,10 +242,20 @@ class WgradCollector:
 
     def __init__(self):
         self.entries = {}
-        self.armed = False
-        self.flushes = 0
 
     def add(self, C, ldc, colsum, A, lda, B, ldb, rows, M, N):
+        if _first_in_pass(self):
+            self.entries = {}      # anything still here is of a pass over this graph that never finished
+            # flush_deferred() sees the collectors of the newest pass on this device only: arming under a newer pass
+            # drops those of a pass that raised, with the tensors they pin.  A pass nested in a node (checkpoint,
+            # autograd.grad) takes the list over too; the outer pass's collectors then lose the early flush only, the
+            # end-of-pass callback below still issues them.
+            d = _dev()
+            if self._pass > d.collectors_pass:
+                d.collectors, d.collectors_pass = [], self._pass
+            if self._pass == d.collectors_pass:
+                d.collectors.append(self)
+            torch.autograd.Variable._execution_engine.queue_callback(self.finish)
         e = self.entries.get(C.data_ptr())
         if e is None:
             e = self.entries[C.data_ptr()] = {"C": C, "ldc": ldc, "colsum": colsum, "lda": lda, "ldb": ldb, "M": M,
@@ -243,11 +263,6 @@ class WgradCollector:
         e["A"].append(A)
         e["B"].append(B)
         e["rows"].append(rows)
-        if not self.armed:
-            self.armed = True
-            self.device_index = torch.cuda.current_device()
-            _armed.setdefault(self.device_index, []).append(self)
-            torch.autograd.Variable._execution_engine.queue_callback(self.finish)
 
     def flush(self):
         """Issue the collected GEMMs.  Called from a hook on the decoder's encoder_outputs gradient (every decoder
@@ -257,7 +272,7 @@ class WgradCollector:
         if not self.entries:
             return
         cur = torch.cuda.current_stream()
-        side = _side_streams.get(cur.device_index)
+        side = _dev(cur).side
         run = cur
         if side is not None and cur != side:
             cur.wait_stream(side)              # operands produced by the other direction's stream
@@ -272,41 +287,33 @@ class WgradCollector:
             for seg_rows, problems in groups.items():
                 wgrad_group(problems, seg_rows, run, _wgrad_seg)
         self.entries = {}
-        self.flushes += 1
 
     def finish(self):
         """Engine end-of-backward callback: late entries, then the main stream waits for the side stream."""
         self.flush()
-        cur = torch.cuda.current_stream()
-        side = _side_streams.get(cur.device_index)
-        if side is not None and cur != side:
-            cur.wait_stream(side)
-        self.armed = False
-        lst = _armed.get(getattr(self, "device_index", -1), [])
-        if self in lst:
-            lst.remove(self)
-
-
-_armed = {}       # device index -> collectors with pending entries
+        join_side_streams()
 
 
 def flush_deferred():
-    """Issue every deferred weight-gradient GEMM collected so far (idempotent).  dp.GradientExchange calls this
-    before it all-reduces the decoder segment; the decoder calls it from its encoder_outputs gradient hook."""
-    for c in list(_armed.get(torch.cuda.current_device(), [])):
-        c.flush()
+    """Issue every deferred weight-gradient GEMM collected so far in the running pass (idempotent).  dp.GradientExchange
+    calls this before it all-reduces the decoder segment; the decoder calls it from its encoder_outputs gradient hook."""
+    d = _dev()
+    if d.collectors_pass == torch._C._current_graph_task_id():
+        for c in list(d.collectors):
+            c.flush()
 
 
 _tls = _threading.local()      # the collector of the forward pass running on THIS thread (nn.DataParallel: one per replica)
 
 
-def begin_defer():
-    """Decoder forward: tape nodes created from here on defer their weight gradients (if enabled)."""
+@_contextlib.contextmanager
+def deferring():
+    """Encoder / decoder forward: tape nodes created inside defer their weight gradients (if enabled) to one collector."""
     _tls.collector = WgradCollector()
-
-
-def end_defer():
-    _tls.collector = None
+    try:
+        yield
+    finally:
+        _tls.collector = None
 
 
 def wgrad_gemm(M, N, K, A, lda, B, ldb, C, ldc, acc, colsum, defer=None):
@@ -316,14 +323,6 @@ def wgrad_gemm(M, N, K, A, lda, B, ldb, C, ldc, acc, colsum, defer=None):
         defer.add(C, ldc, colsum, A, lda, B, ldb, K, M, N)
         return
     gemm(1, 0, M, N, K, A, lda, B, ldb, C, ldc, accumulate=acc, colsum=colsum)
-
-
-def join_side_streams():
-    """Make the current stream wait for everything enqueued on the side stream (end of a step)."""
-    cur = torch.cuda.current_stream()
-    side = _side_streams.get(cur.device_index)
-    if side is not None:
-        cur.wait_stream(side)
 
 
 # split-K workspace: int[4096] tile counters (kept zero by the kernel) + fp32 partial slabs, one per stream so
@@ -420,7 +419,8 @@ def _gbuf(p):
     allocating a gradient and having AccumulateGrad add it with a separate kernel (16x per decoder parameter).
     The buffer is the parameter's fixed slice of the flat gradient whatever `p.grad` currently says; a `.grad` the caller
     dropped or replaced (torch.optim's zero_grad(set_to_none=True) default, possibly BETWEEN forward and backward as in
-    SBL/train.py:195-196) is repaired once, at the root of the next backward (_backward_enter)."""
+    SBL/train.py:195-196) is repaired at the root of the next backward pass (_backward_enter), whether or not the
+    previous pass ran to its end."""
     if p is None:
         return None
     return getattr(p, "_sbl_grad", None)
@@ -440,7 +440,7 @@ def _backward_enter():
         return
     dev = torch.cuda.current_device() if torch.cuda.is_available() else None
     for fm in list(_flat_models):
-        if not fm._in_backward and fm.device_index in (None, dev):
+        if fm.device_index in (None, dev) and _first_in_pass(fm):
             fm.begin_backward()
 
 

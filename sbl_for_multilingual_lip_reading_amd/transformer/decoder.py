@@ -252,32 +252,31 @@ class Decoder(nn.Module):
                     for d in (0, 1):
                         ops.argmax_select(None, golds[d], ys[d], k, 0)
 
-        ops.begin_defer()      # decoder weights are used once per stage: their dW GEMMs are deferred and merged
         if encoder_outputs.requires_grad and torch.is_grad_enabled():
             # d(loss)/d(encoder_outputs) is complete only after every decoder tape node has run: issue the merged
             # weight-gradient GEMMs then (side stream), beside the encoder / frontend backward.  (Flushing when backward
             # reaches the encoder INPUT instead measured equal within noise: the chip is throughput-bound either way.)
             encoder_outputs.register_hook(lambda g: ops.flush_deferred())
-        for (i0, i1) in stages:
-            segL = tuple(range(i0 + 1, i1 + 2))            # prefix lengths of the steps in this stage
-            last = self._stage_last(ys, N, segL, layers, main, side, kv)     # (nseg*N, 512) per direction
-            for d in (0, 1):
-                pred = ops.linear(last[d], heads[d])                   # (nseg*N, 58)
-                # unbind (one stack in backward) instead of row slices (a zero-filled (nseg*N, 58) buffer, a copy and
-                # an add per step in backward)
-                for step, pr in zip(range(i0, i1 + 1), pred.view(len(segL), N, -1).unbind(0)):
-                    outs[d][step] = pr
-            # token fed to the next stage
-            if coins is None:
+        with ops.deferring():      # decoder weights are used once per stage: their dW GEMMs are deferred and merged
+            for (i0, i1) in stages:
+                segL = tuple(range(i0 + 1, i1 + 2))            # prefix lengths of the steps in this stage
+                last = self._stage_last(ys, N, segL, layers, main, side, kv)     # (nseg*N, 512) per direction
                 for d in (0, 1):
-                    ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 0, self.coins_dev)
-            elif coins[i1]:
-                for d in (0, 1):
-                    ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 1)
-            elif not self.batch_teacher_runs:
-                for d in (0, 1):
-                    ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 0)
-        ops.end_defer()
+                    pred = ops.linear(last[d], heads[d])                   # (nseg*N, 58)
+                    # unbind (one stack in backward) instead of row slices (a zero-filled (nseg*N, 58) buffer, a copy and
+                    # an add per step in backward)
+                    for step, pr in zip(range(i0, i1 + 1), pred.view(len(segL), N, -1).unbind(0)):
+                        outs[d][step] = pr
+                # token fed to the next stage
+                if coins is None:
+                    for d in (0, 1):
+                        ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 0, self.coins_dev)
+                elif coins[i1]:
+                    for d in (0, 1):
+                        ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 1)
+                elif not self.batch_teacher_runs:
+                    for d in (0, 1):
+                        ops.argmax_select(outs[d][i1].detach(), golds[d], ys[d], i1, 0)
         return outs, ys
 
     def forward(self, padded_input_l2r, padded_input_r2l, encoder_outputs,

@@ -47,24 +47,19 @@ class Encoder(nn.Module):
 
         # the layers' weight gradients are deferred and issued as one grouped launch when backward reaches the
         # encoder input (second stream, under the frontend backward) or at the end of backward, whichever is first
-        defer = torch.is_grad_enabled()
-        if defer:
-            ops.begin_defer()
-            if padded_input.requires_grad:
-                padded_input.register_hook(lambda g: ops.flush_deferred())
-        h = ops.linear(padded_input, self.linear_in.weight, self.linear_in.bias)
-        h = ops.add_layernorm(h, None, self.layer_norm_in.weight, self.layer_norm_in.bias, self.layer_norm_in.eps)
-        h = ops.AddPEFn.apply(h, self.positional_encoding.pe[0, :T])
-        h = ops.dropout(h, self.dropout.p, self.training)
+        if torch.is_grad_enabled() and padded_input.requires_grad:
+            padded_input.register_hook(lambda g: ops.flush_deferred())
+        with ops.deferring():
+            h = ops.linear(padded_input, self.linear_in.weight, self.linear_in.bias)
+            h = ops.add_layernorm(h, None, self.layer_norm_in.weight, self.layer_norm_in.bias, self.layer_norm_in.eps)
+            h = ops.AddPEFn.apply(h, self.positional_encoding.pe[0, :T])
+            h = ops.dropout(h, self.dropout.p, self.training)
 
-        attns = [] if return_attns else None
-        for layer in self.layer_stack:
-            h, attn = layer(h, non_pad_mask=non_pad_mask, slf_attn_mask=slf_attn_mask)
-            if attns is not None:
-                attns.append(attn)
-
-        if defer:
-            ops.end_defer()
+            attns = [] if return_attns else None
+            for layer in self.layer_stack:
+                h, attn = layer(h, non_pad_mask=non_pad_mask, slf_attn_mask=slf_attn_mask)
+                if attns is not None:
+                    attns.append(attn)
         return (h,) if attns is None else (h, attns)
 
 

@@ -1567,6 +1567,64 @@ def test_flat_model_reference_loop_order_zero_grad_between_forward_and_backward(
     assert float((grads[0] - grads[1]).abs().max()) > 0        # the second step really was a different gradient
 
 
+@pytest.mark.parametrize("order", ["flat_zero_grad_before_forward", "adam_zero_grad_between_forward_and_backward"])
+def test_flat_model_recovers_after_a_failed_backward(ops, order):
+    """A backward that raises half-way (a Python exception from a tensor hook on the output of encoder layer 0, caught by the
+    caller like an OOM-skip would) ends without the engine's end-of-backward callbacks.  By then the decoder node has run
+    (flat model entered, side-stream join queued) and encoder layer 1 has deferred its weight gradients, unflushed.  None of
+    that may reach the next step: its gradient must equal that of a twin that never saw the failure - `.grad` re-attached
+    (it stays None if the flat model still believes itself inside the dead pass) and layer 1's weight gradients counted once
+    (twice if the dead pass's collector is flushed into the live gradient).  Same 1e-3 bound as the test above: the
+    embedding gradient uses float atomics, so the twins are not bitwise equal."""
+    from sbl_for_multilingual_lip_reading_amd import dp
+    from sbl_for_multilingual_lip_reading_amd.transformer.loss import cal_performance_device
+    B, T, H, W = 2, 4, 24, 24
+    x, l2r, r2l = detfill.synthetic_batch(B, T, H, W, 52)
+    xd, ld, rd = torch.from_numpy(x).to(DEV), torch.from_numpy(l2r).to(DEV), torch.from_numpy(r2l).to(DEV)
+    mA, mB = build_model(2, 1).train(), build_model(2, 1).train()
+    mA.decoder.coins_host = mB.decoder.coins_host = [False] * 16
+    fA, fB = dp.FlatModel(mA), dp.FlatModel(mB)
+
+    def loss_of(m):
+        pl, gl, pr, gr = m(xd, ld, rd)
+        return 0.5 * (cal_performance_device(pl, gl, 0.1)[0] + cal_performance_device(pr, gr, 0.1)[0])
+
+    def fail(g):
+        raise RuntimeError("backward told to fail")
+
+    handles = []
+    handles.append(mA.encoder.layer_stack[0].register_forward_hook(
+        lambda mod, inp, out: handles.append(out[0].register_hook(fail))))
+    random.seed(400)
+    loss = loss_of(mA)
+    with pytest.raises(RuntimeError, match="told to fail"):
+        loss.backward()
+    for h in handles:
+        h.remove()
+    del loss
+    ops.join_side_streams()      # the failed step ends here: what it had put on the side stream is not joined by anyone else
+
+    for m, f in ((mA, fA), (mB, fB)):
+        opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+        random.seed(401)
+        if order == "flat_zero_grad_before_forward":
+            f.zero_grad()
+            loss = loss_of(m)
+        else:
+            loss = loss_of(m)
+            opt.zero_grad()                   # torch default set_to_none=True: every p.grad is None now
+            assert m.decoder.tgt_word_prj_l2r.weight.grad is None
+        loss.backward()
+        ops.join_side_streams()
+    assert all(p.grad is not None and p.grad.data_ptr() == p._sbl_grad.data_ptr() for p in mA.parameters() if p.requires_grad)
+    for name, (a, b) in (("decoder.", fA.ranges["decoder."]), ("encoder.", fA.ranges["encoder."]),
+                         ("visual_frontend.", fA.span("visual_frontend."))):
+        gA, gB = fA.flat_grad[a:b], fB.flat_grad[a:b]
+        err, ref = float((gA - gB).norm()), float(gB.norm())
+        print("failed-backward recovery %s %s: |gA-gB| %.3e  |gB| %.3e" % (order, name, err, ref))
+        assert ref > 0 and err <= 1e-3 * ref, (name, err, ref)
+
+
 def test_frozen_encoder_stage_is_honoured(ops):
     """README stage 2 (SBL/README.md:56-66, transformer.py:15-16): encoder parameters get requires_grad=False and the
     optimizer is built over filter(requires_grad).  The kernels may still write those gradients into the flat buffer;
