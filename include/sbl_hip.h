@@ -611,6 +611,52 @@ int sbl_preprocess_clips(const uint8_t* in, float* out, const float* lut256, con
 int sbl_adam_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
                   int step, float grad_scale, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- device-side optimizer step
+ * Global-norm / element clip, non-finite skip, Noam schedule and Adam with every per-step scalar in DEVICE memory, so
+ * that zero_grad + forward + backward + update replay as one hipGraph (sbl_adam_step takes lr and step from the host).
+ * The optimizer state is a caller-owned, 8-byte aligned double[SBL_OPT_STATE_SLOTS]; doubles hold the counters exactly:
+ *   [SBL_OPT_STEP]          t, the number of APPLIED steps (Adam's bias-correction exponent, the Noam step)
+ *   [SBL_OPT_SKIPPED]       number of skipped steps
+ *   [SBL_OPT_GRAD_NORM]     L2 norm of the last clamped, scaled gradient (inf / NaN when it held a non-finite element)
+ *   [SBL_OPT_CLIP_COEF]     last global-norm clip coefficient, min(1, max_norm / (norm + 1e-6)); 1 when max_norm <= 0
+ *   [SBL_OPT_LR]            current rate: written by sbl_opt_finalize under a Noam schedule, else by the host
+ *   [SBL_OPT_STEP_SIZE]     lr / (1 - beta1^t)
+ *   [SBL_OPT_INV_SQRT_BC2]  1 / sqrt(1 - beta2^t)
+ *   [SBL_OPT_SKIP]          1 when the last sbl_opt_finalize decided to skip the update, else 0
+ * One step = sbl_grad_sumsq per trainable range (increasing workspace offsets), one sbl_opt_finalize, sbl_adam_step_dev
+ * per range, all on one stream.  A launch of n elements uses min(SBL_OPT_MAX_BLOCKS, ceil(ceil(n / 4)
+ * / 256)) blocks (one partial sum each).  No float or double atomics anywhere: every sum is taken in an order that is a
+ * function of (n, number of partials) alone, so two runs give the same bits and data-parallel replicas that hold the same
+ * summed gradient derive the same coefficient. */
+#define SBL_OPT_STATE_SLOTS 8
+#define SBL_OPT_STEP 0
+#define SBL_OPT_SKIPPED 1
+#define SBL_OPT_GRAD_NORM 2
+#define SBL_OPT_CLIP_COEF 3
+#define SBL_OPT_LR 4
+#define SBL_OPT_STEP_SIZE 5
+#define SBL_OPT_INV_SQRT_BC2 6
+#define SBL_OPT_SKIP 7
+#define SBL_OPT_MAX_BLOCKS 2048
+/* partials[offset + b] = sum over block b's elements of clamp(g[i] * grad_scale, +-clip_value)^2, accumulated in double.
+ * The clamp is torch.clamp's (SBL/utils.py:10-19 clip_gradient): NaN stays NaN, +-inf becomes +-clip_value; clip_value
+ * <= 0: off.  Any n >= 1; 16-byte loads when g is 16-byte aligned.  capacity: doubles in `partials`. */
+int sbl_grad_sumsq(const float* g, long n, float grad_scale, float clip_value, double* partials, long capacity, long offset,
+                   sbl_stream_t stream);
+/* One block: sum = partials[0 .. nparts) in a fixed order, norm = sqrt(sum), coef as above (the rule of
+ * torch.nn.utils.clip_grad_norm_; max_norm <= 0: off).  If sum is finite, or skip_nonfinite == 0: t += 1, with noam_k > 0
+ * lr = noam_k * 512^-0.5 * min(t^-0.5, t * noam_warmup^-1.5) (SBL/transformer/optimizer.py:18-27), else lr is the slot as
+ * the host left it, and both bias-correction slots are recomputed from t; the skip flag is cleared.  Otherwise the skip
+ * flag is set, the skipped counter goes +1, and t, lr and the correction slots are untouched.  The sum of squares of
+ * finite floats cannot overflow a double, so a non-finite sum means exactly "some clamped element was inf or NaN". */
+int sbl_opt_finalize(double* state, const double* partials, long nparts, double max_norm, int skip_nonfinite, double noam_k,
+                     double noam_warmup, float beta1, float beta2, sbl_stream_t stream);
+/* Adam over one range with g' = clamp(g * grad_scale, +-clip_value) * state[SBL_OPT_CLIP_COEF], the step size and second
+ * bias factor from the state buffer, and sbl_adam_step's arithmetic otherwise.  With state[SBL_OPT_SKIP] set nothing is
+ * written: p, m, v keep their bits. */
+int sbl_adam_step_dev(float* p, const float* g, float* m, float* v, long n, const double* state, float beta1, float beta2,
+                      float eps, float grad_scale, float clip_value, sbl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,12 +2,12 @@
 CPU fallback: if the library is missing or a call fails, it raises."""
 import ctypes
 import os
-from ctypes import c_float, c_int, c_long, c_uint64, c_void_p
+from ctypes import c_double, c_float, c_int, c_long, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsbl_hip.so")
 
-P, I, L, F, U64 = c_void_p, c_int, c_long, c_float, c_uint64
+P, I, L, F, U64, D = c_void_p, c_int, c_long, c_float, c_uint64, c_double
 
 # name -> argtypes (all return int); mirrors include/sbl_hip.h one to one
 SIGNATURES = {
@@ -88,6 +88,9 @@ SIGNATURES = {
     "sbl_cls_loss_bwd": [P, P, P, P, P, P, P, P, I, I, I, F, I, P],
     "sbl_cls_head_bwd": [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_adam_step": [P, P, P, P, L, F, F, F, F, I, F, P],
+    "sbl_grad_sumsq": [P, L, F, F, P, L, L, P],
+    "sbl_opt_finalize": [P, P, L, D, I, D, D, F, F, P],
+    "sbl_adam_step_dev": [P, P, P, P, L, P, F, F, F, F, F, P],
     "sbl_preprocess_clips": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_set_matmul_precision": [I],
     "sbl_set_tuning": [I, I],

@@ -28,7 +28,8 @@ def _to_cpu(obj):
 
 
 def save_checkpoint(path, model, optimizer=None, **meta):
-    """model: Transformer (or any module of this package).  optimizer: TransformerOptimizer / FusedAdam / None."""
+    """model: Transformer (or any module of this package).  optimizer: TransformerOptimizer / DeviceNoamOptimizer / FusedAdam /
+    None.  A device-mode FusedAdam carries its device state buffer as the tensor `opt_state` of its state dict."""
     m = model.module if hasattr(model, "module") else model          # nn.DataParallel wrapper, SBL/train.py:246-250
     out = {"model_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}}
     if optimizer is not None:

@@ -1671,6 +1671,42 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, grad_scale=1.0):
     call("sbl_adam_step", _p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _s())
 
 
+# Device-side optimizer step (include/sbl_hip.h): slots of the double[8] state buffer, and the launch geometry
+OPT_STATE_SLOTS = 8
+OPT_STEP, OPT_SKIPPED, OPT_GRAD_NORM, OPT_CLIP_COEF, OPT_LR, OPT_STEP_SIZE, OPT_INV_SQRT_BC2, OPT_SKIP = range(8)
+OPT_MAX_BLOCKS = 2048
+
+
+def opt_blocks(n):
+    """Blocks (= partial sums) one sbl_grad_sumsq / sbl_adam_step_dev launch over n elements uses."""
+    return max(1, min(OPT_MAX_BLOCKS, ((n + 3) // 4 + 255) // 256))
+
+
+def grad_sumsq(g, partials, offset, grad_scale=1.0, clip_value=0.0):
+    """Per-block sums of clamp(g * grad_scale, +-clip_value)^2 into partials[offset:]; returns the number written."""
+    _need_cuda(g, partials)
+    assert g.dtype == torch.float32 and partials.dtype == torch.float64 and g.is_contiguous() and partials.is_contiguous()
+    call("sbl_grad_sumsq", _p(g), g.numel(), grad_scale, clip_value, _p(partials), partials.numel(), offset, _s())
+    return opt_blocks(g.numel())
+
+
+def opt_finalize(state, partials, nparts, max_norm=0.0, skip_nonfinite=False, noam=None, beta1=0.9, beta2=0.98):
+    """partials[:nparts] -> norm, clip coefficient, and (unless the step is skipped) t, lr and the bias corrections."""
+    _need_cuda(state, partials)
+    assert state.dtype == torch.float64 and state.numel() == OPT_STATE_SLOTS and state.is_contiguous()
+    assert partials.dtype == torch.float64 and 0 < nparts <= partials.numel()
+    k, warmup = noam if noam is not None else (0.0, 0.0)
+    call("sbl_opt_finalize", _p(state), _p(partials), nparts, max_norm, int(skip_nonfinite), k, warmup, beta1, beta2, _s())
+
+
+def adam_step_dev(p, g, m, v, state, beta1, beta2, eps, grad_scale=1.0, clip_value=0.0):
+    """Fused Adam over flat fp32 buffers with clip coefficient, step size, bias factor and skip flag read from `state`."""
+    _need_cuda(p, g, m, v, state)
+    assert state.dtype == torch.float64 and state.numel() == OPT_STATE_SLOTS
+    assert g.numel() == m.numel() == v.numel() == p.numel()
+    call("sbl_adam_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(state), beta1, beta2, eps, grad_scale, clip_value, _s())
+
+
 _LUT = {}
 
 
