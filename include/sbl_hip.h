@@ -52,6 +52,15 @@ int sbl_profile_end(void);
 int sbl_profile_used(void);
 int sbl_profile_last_slot(void);
 int sbl_profile_last_kernel(void);
+/* The launch leaf the last trunk convolution enqueued by this thread took (debug; 0 before the first one):
+ *   (family << 24) | (tile << 20) | (TR << 10) | G
+ *   family  1 per-tap gather, one plain launch         2 per-tap gather, tail split (two launches)
+ *           3 position-major forward / input gradient  4 patch-resident forward / input gradient
+ *           5 stride-2 parity classes (one launch)     6 patch-resident weight gradient
+ *           7 position-major weight gradient           8 plain implicit-GEMM weight gradient
+ *   tile    1 = 64x64, 2 = 128x64, 3 = 128x128; 0 for the patch-resident kernels (families 4 and 6), which report the tile
+ *           geometry they chose instead: TR rows of one image (G == 1) or G whole images (TR == H); TR = G = 0 elsewhere. */
+int sbl_profile_last_route(void);
 
 /* Precision of the matrix products of the tile engine (dense GEMMs and trunk convolutions), process-wide, default 0:
  *   0  exact fp32 MFMA (v_mfma_f32_32x32x2_f32), bitwise an fmaf chain — the reference's arithmetic;

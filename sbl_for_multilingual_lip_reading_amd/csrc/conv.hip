@@ -130,7 +130,11 @@ static auto with_dgrad_epi(float* dx, int N, const DgradFuse& f, F&& fn) {
 template <class AL, class BL, class EPI, int BM, int BN>
 static void launch_tailsplit_or_plain(const AL& al, const BL& bl, const EPI& e, int M, int N, int K, int kid, void* ws, long ws_bytes,
                                       hipStream_t s) {
-    if (sbl_launch_gemm_tailsplit<AL, BL, EPI, BM, BN, 1>(al, bl, e, M, N, K, s, kid, ws, ws_bytes, kConvWsCounters)) return;
+    if (sbl_launch_gemm_tailsplit<AL, BL, EPI, BM, BN, 1>(al, bl, e, M, N, K, s, kid, ws, ws_bytes, kConvWsCounters)) {
+        sbl_note_route(2, sbl_route_tile(BM, BN), 0, 0);
+        return;
+    }
+    sbl_note_route(1, sbl_route_tile(BM, BN), 0, 0);
     SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(kid)};
     sbl_launch_gemm<AL, BL, EPI, BM, BN, 1, 2>(al, bl, e, M, N, K, 1, s, sc);
 }
@@ -152,6 +156,7 @@ static void launch_conv_pm(const float* src, const float* wk, const ConvGeom& g,
     DenseKCTapList<64> bl{wk, (long)K, N, C, 0ull};
     SplitCtl sc{nullptr, nullptr, nullptr, sbl_next_stamp_slot(kid)};
     const dim3 grid(sbl_cdiv(N, 64), sbl_cdiv(M, 64), 1);
+    sbl_note_route(3, sbl_route_tile(64, 64), 0, 0);
     sbl_with_prec([&](auto p) {
         hipLaunchKernelGGL((sbl_conv_pm_kernel<ConvGatherPM<64, DGRAD>, DenseKCTapList<64>, EPI, 64, 64, DGRAD, decltype(p)::value>), grid, dim3(256), 0, s,
                            al, bl, e, sc, M, N);
@@ -269,6 +274,7 @@ static int conv2d_dgrad_impl(const float* dy, const float* wt, float* dx, int NI
                     cs.M[i] = c.M; cs.K[i] = c.K; cs.t0[i] = t0[i];
                 }
                 cs.t0[SBL_MAX_CLASSES] = t0[SBL_MAX_CLASSES];
+                sbl_note_route(5, sbl_route_tile(BM, BN), 0, 0);
                 sbl_with_prec([&](auto p) {
                     hipLaunchKernelGGL((sbl_conv_classes_kernel<AL, BL, EPI, BM, BN, decltype(p)::value>), dim3((unsigned)tt), dim3(256), 0, s, cs, sc, N);
                 });
@@ -369,6 +375,7 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
             const int splits = wgrad_splits(T == 128 ? wg_target : 2 * wg_target, (long)sbl_cdiv(M, T) * sbl_cdiv(N, T), K);
             DenseMCPM<T> al{dy, (long)Cout, M, NIMG, Ho, Wo, g.fdNIMG, PmRect{0, 0, 1, 0, 0, 1.f}};
             ConvGatherMCPM<T> bl{x, g, N, PmRect{0, 0, 1, 0, 0, 1.f}};
+            sbl_note_route(7, sbl_route_tile(T, T), 0, 0);
             sbl_with_prec([&](auto p) {
                 hipLaunchKernelGGL((sbl_conv_pm_wgrad_kernel<DenseMCPM<T>, ConvGatherMCPM<T>, EpiStore<2, false>, T, T, decltype(p)::value>),
                                    dim3(sbl_cdiv(M, T), sbl_cdiv(N, T), splits), dim3(256), 0, s, al, bl, e, sc, M, N);
@@ -383,6 +390,7 @@ extern "C" int sbl_conv2d_wgrad(const float* x, const float* dy, float* dw, int 
         constexpr int T = decltype(t)::value;
         DenseMC<T, true> al{dy, (long)Cout, M};
         ConvGatherMC<T> bl{x, g, N};
+        sbl_note_route(8, sbl_route_tile(T, T), 0, 0);
         sbl_launch_gemm<DenseMC<T, true>, ConvGatherMC<T>, EpiStore<2, false>, T, T>(al, bl, e, M, N, K, wgrad_splits(wg_target, (long)sbl_cdiv(M, T) * sbl_cdiv(N, T), K), s, sc);
     };
     if (big && M >= 128) plain(sbl_int<128>{});

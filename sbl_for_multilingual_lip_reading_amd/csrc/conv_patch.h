@@ -308,6 +308,7 @@ static inline bool sbl_launch_conv_patch(const float* src, const float* wk, cons
         if constexpr (NT == 0) return false;      // (excluded above: no fp32 instantiation of this kernel)
         else {
             if (!sbl_conv_patch_lds_cap<NT, DGRAD, STATS>()) return false;
+            sbl_note_route(4, 0, TR, G);
             hipLaunchKernelGGL((sbl_conv_patch_kernel<NT, DGRAD, STATS>), grid, dim3(256), lds, s, src, wk, epi, NIMG, H, W, C, Nout, TR, tpi, ntiles, G, stamp);
             return true;
         }

@@ -246,6 +246,7 @@ static inline bool sbl_launch_conv_patch_wgrad(const float* x, const float* dy, 
         if constexpr (NT == 0) return false;      // (excluded above: no fp32 instantiation of this kernel)
         else {
             if (!sbl_conv_patch_wgrad_lds_cap<NT>()) return false;
+            sbl_note_route(6, 0, gm.TR, gm.G);
             hipLaunchKernelGGL((sbl_conv_patch_wgrad_kernel<NT>), dim3(gx, combos), dim3(SBL_PWG_THREADS), lds, s, x, dy, dw, gm, stamp);
             return true;
         }

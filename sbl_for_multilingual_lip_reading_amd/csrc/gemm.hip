@@ -43,6 +43,9 @@ extern "C" int sbl_profile_end(void) {
 extern "C" int sbl_profile_last_slot(void) { return g_last_slot; }
 extern "C" int sbl_profile_used(void) { return g_stamp_used; }      // process-wide (last_slot is per calling thread)
 extern "C" int sbl_profile_last_kernel(void) { return g_last_kid; }
+static thread_local int g_last_route = 0;
+void sbl_note_route(int family, int tile, int tr, int g) { g_last_route = (family << 24) | (tile << 20) | (tr << 10) | g; }
+extern "C" int sbl_profile_last_route(void) { return g_last_route; }
 extern "C" int sbl_abi_version(void) { return SBL_ABI_VERSION; }
 
 // ------------------------------------------------------------------ matrix-product precision of the tile engine

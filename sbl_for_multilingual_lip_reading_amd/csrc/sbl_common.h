@@ -56,6 +56,12 @@ __device__ __forceinline__ void sbl_stamp_end(unsigned long long* slot) {
 #define SBL_KID_SEG_WGRAD 7
 #define SBL_KID_STEM 8
 #define SBL_KID_ATTENTION 9
+// Which launch leaf a trunk convolution took (debug, per calling thread; include/sbl_hip.h: sbl_profile_last_route).
+// family: 1 per-tap gather, 2 gather + tail split, 3 position-major, 4 patch-resident, 5 parity classes, 6 patch-resident
+// weight gradient, 7 position-major weight gradient, 8 plain weight gradient;  tile: 1 = 64x64, 2 = 128x64, 3 = 128x128, 0 for
+// the patch kernels, which carry their (TR, G) instead.
+void sbl_note_route(int family, int tile, int tr, int g);   // host side
+static inline int sbl_route_tile(int BM, int BN) { return BM == 64 ? 1 : BN == 64 ? 2 : 3; }
 
 // ---- ragged row batches: a "run" of decoder steps whose inputs are all known is processed as one batch of
 // segments; segment s holds B sequences of length L[s], rows [row_off[s], row_off[s] + B*L[s]) in (b, l) order.

@@ -224,7 +224,9 @@ def test_conv2d_fwd_dgrad_wgrad(ops, NIMG, H, W, Cin, Cout, k, stride):
     yd = torch.empty(NIMG, Ho, Wo, Cout, device=DEV)
     stats = torch.empty(2 * Cout, device=DEV, dtype=torch.float64)
     # with the stream workspace the launches whose tile count leaves a partial last round split that round along K
-    # (the (40, 22, 22, 64, 64) and (20, 22, 22, 128, 128) cases: 303 / 304 tiles -> 256 unsplit + 47 / 48 split 5 ways)
+    # (the (40, 22, 22, 64, 64) and (20, 22, 22, 128, 128) cases: 303 / 304 tiles -> 256 unsplit + 47 / 48 split 5 ways).
+    # That holds under "f32" only: in the split-bf16 modes these 22x22 maps run sbl_conv_patch_kernel and never reach the
+    # tail split - tests/test_conv_routes_gpu.py reaches it in every mode and asserts the route.
     ws = ops._workspace()
     ops.call("sbl_conv2d_fwd", xd.data_ptr(), w_ohwi.data_ptr(), yd.data_ptr(), stats.data_ptr(), 0, NIMG, H, W, Cin, Cout,
              k, k, stride, pad, ws.data_ptr(), ops.WS_BYTES, ops._s())
