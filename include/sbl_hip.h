@@ -52,7 +52,8 @@ int sbl_profile_end(void);
 int sbl_profile_used(void);
 int sbl_profile_last_slot(void);
 int sbl_profile_last_kernel(void);
-/* The launch leaf the last trunk convolution enqueued by this thread took (debug; 0 before the first one):
+/* The launch leaf the last trunk convolution - or sbl_gemm2_rows_f32 call, family 9, described there - enqueued by this
+ * thread took (debug; 0 before the first one):
  *   (family << 24) | (tile << 20) | (TR << 10) | G
  *   family  1 per-tap gather, one plain launch         2 per-tap gather, tail split (two launches)
  *           3 position-major forward / input gradient  4 patch-resident forward / input gradient
@@ -111,6 +112,16 @@ int sbl_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, lo
 int sbl_gemm2_f32(int M, int N, int K, const float* A0, const float* A1, long lda, const float* B0, const float* B1,
                   long ldb, float* C0, float* C1, long ldc, const float* bias0, const float* bias1, int relu, void* ws,
                   long ws_bytes, sbl_stream_t stream);
+/* The same call for the decoder forward, whose small stages (one or two decoding steps, M = 32...128 rows per direction)
+ * leave a 32x32 tiling with fewer workgroups than the GPU has CUs.  A launch that is row-starved,
+ * 2 * ceil(M/32) * ceil(N/32) < 256 and M <= 128, with K % 16 == 0, 16-byte aligned A and B and lda % 4 == ldb % 4 == 0 runs on 16x16
+ * output tiles (one workgroup each, its waves split K; exact fp32 in every precision mode like the skinny kernel, no
+ * workspace; sbl_profile_last_kernel() == 1).  Every other call is sbl_gemm2_f32 with the same arguments, bit for bit.
+ * sbl_profile_last_route() afterwards: family 9, tile 4 and (NW, U) in the TR / G fields for the 16x16 kernel, tile 0
+ * for a forwarded call. */
+int sbl_gemm2_rows_f32(int M, int N, int K, const float* A0, const float* A1, long lda, const float* B0, const float* B1,
+                       long ldb, float* C0, float* C1, long ldc, const float* bias0, const float* bias1, int relu, void* ws,
+                       long ws_bytes, sbl_stream_t stream);
 /* Deferred weight gradient of one decoder weight over all stages of a step:
  * C[M,N] += sum_s A_s^T B_s with A_s (seg_rows[s] x M, row stride lda) = dY of stage s and B_s (seg_rows[s] x N) = its
  * input; a_colsum[m] += column sums of the A_s (bias gradient).  A_ptrs / B_ptrs / seg_rows are HOST arrays of nseg

@@ -251,6 +251,39 @@ extern "C" int sbl_gemm2_f32(int M, int N, int K, const float* A0, const float* 
     return 0;
 }
 
+// ------------------------------------------------------------------ ... with 16x16 tiles where the rows are few
+// The decoder forward's entry point.  One or two decoding steps per stage give M = 32...128 rows per direction; on 32x32
+// tiles such a launch holds 32-128 workgroups for 256 CUs and takes 25-29 us at K = 2048 whatever M is.  Launches below
+// sbl_rows16_max_wgs32 workgroups and of at most sbl_rows16_max_m rows take sbl_skinny16_gemm_kernel (four times the
+// workgroups, no K slices across workgroups, no workspace, the sums of the 32x32 kernel); every other call goes to sbl_gemm2_f32 untouched.  Noted as route family 9: tile 4 = the 16x16 kernel
+// with its (NW, U), tile 0 = forwarded.
+static inline bool sbl_rows16_takes(int M, int N, int K, const float* A0, const float* A1, long lda, const float* B0,
+                                    const float* B1, long ldb) {
+    const bool starved = 2L * sbl_cdiv(M, 32) * sbl_cdiv(N, 32) < sbl_rows16_max_wgs32 && M <= sbl_rows16_max_m;
+    const bool al_ok = sbl_aligned16(A0) && sbl_aligned16(A1) && sbl_aligned16(B0) && sbl_aligned16(B1) && lda % 4 == 0 && ldb % 4 == 0;
+    return starved && K % 16 == 0 && al_ok;
+}
+
+extern "C" int sbl_gemm2_rows_f32(int M, int N, int K, const float* A0, const float* A1, long lda, const float* B0, const float* B1,
+                                  long ldb, float* C0, float* C1, long ldc, const float* bias0, const float* bias1, int relu,
+                                  void* ws, long ws_bytes, sbl_stream_t stream) {
+    SBL_REQUIRE(M > 0 && N > 0 && K > 0, "sbl_gemm2_rows_f32: non-positive dims M=%d N=%d K=%d", M, N, K);
+    SBL_REQUIRE(A0 && A1 && B0 && B1 && C0 && C1 && (!bias0 == !bias1), "sbl_gemm2_rows_f32: null operand / one-sided bias");
+    SBL_REQUIRE(lda >= K && ldb >= K && ldc >= N, "sbl_gemm2_rows_f32: leading dimension too small (lda=%ld ldb=%ld ldc=%ld)", lda, ldb, ldc);
+    SBL_REQUIRE(!ws || (sbl_aligned16(ws) && ws_bytes >= (long)sizeof(int) * SBL_WS_COUNTERS), "sbl_gemm2_rows_f32: workspace unaligned or < 16 KiB");
+    if (!sbl_rows16_takes(M, N, K, A0, A1, lda, B0, B1, ldb)) {
+        const int rc = sbl_gemm2_f32(M, N, K, A0, A1, lda, B0, B1, ldb, C0, C1, ldc, bias0, bias1, relu, ws, ws_bytes, stream);
+        sbl_note_route(SBL_ROUTE_GEMM2_ROWS, 0, 0, 0);
+        return rc;
+    }
+    SkinnyEpi e{C0, ldc, bias0, relu, nullptr, 0, 0, nullptr, sbl_next_stamp_slot(SBL_KID_SKINNY)};
+    SkinnyDual du{A1, B1, C1, bias1};
+    const int vu = sbl_launch_skinny16(A0, lda, B0, ldb, e, du, M, N, K, (hipStream_t)stream);
+    sbl_note_route(SBL_ROUTE_GEMM2_ROWS, SBL_ROUTE_TILE_16, vu >> 4, vu & 15);
+    SBL_LAUNCH_CHECK("sbl_gemm2_rows_f32");
+    return 0;
+}
+
 // ------------------------------------------------------------------ deferred weight gradient over all decoder stages
 // C[M,N] += sum_s A_s^T B_s  (A_s: rows_s x M, B_s: rows_s x N, row-major), a_colsum[m] += column sums of A.
 // One launch per weight per step; split-K with float atomics (C is the persistent gradient buffer).

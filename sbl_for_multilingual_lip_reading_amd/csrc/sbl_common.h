@@ -60,6 +60,10 @@ __device__ __forceinline__ void sbl_stamp_end(unsigned long long* slot) {
 // family: 1 per-tap gather, 2 gather + tail split, 3 position-major, 4 patch-resident, 5 parity classes, 6 patch-resident
 // weight gradient, 7 position-major weight gradient, 8 plain weight gradient;  tile: 1 = 64x64, 2 = 128x64, 3 = 128x128, 0 for
 // the patch kernels, which carry their (TR, G) instead.
+// Family 9 is not a convolution: sbl_gemm2_rows_f32 (gemm.hip) notes tile 4 = the 16x16-tile kernel with (tr, g) = its (NW, U),
+// tile 0 = the call went on to sbl_gemm2_f32.
+#define SBL_ROUTE_GEMM2_ROWS 9
+#define SBL_ROUTE_TILE_16 4
 void sbl_note_route(int family, int tile, int tr, int g);   // host side
 static inline int sbl_route_tile(int BM, int BN) { return BM == 64 ? 1 : BN == 64 ? 2 : 3; }
 

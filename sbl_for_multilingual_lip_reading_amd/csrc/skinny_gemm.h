@@ -162,6 +162,141 @@ __global__ __launch_bounds__(NW * 64) void sbl_skinny_gemm_kernel(SkinnyOperand<
     sbl_stamp_end(e.stamp);
 }
 
+// ------------------------------------------------------------------ row-starved dual products: 16x16 tiles
+// With M = 32...128 rows per direction the kernel above launches 32-128 workgroups on 256 CUs, and each walks its whole K
+// behind one CU's L1.  Same scheme on a quarter of the output tile: one workgroup owns ONE 16x16 tile of one direction
+// (four times the workgroups, no K slices across workgroups, no workspace), v_mfma_f32_16x16x4_f32 straight from global
+// memory (exact fp32, the rate of 32x32x2), two named register stages of U 16-deep groups, partial tiles meet in LDS, where
+// the epilogue (bias / ReLU / store) runs.  Both operands k-contiguous (the nn.Linear forward).
+//
+// The sums are those of the 32x32 kernel, term by term: K is cut into the same V = 8 (K >= 512) or 4 contiguous ranges, one
+// fmaf chain each, and the chains meet in the same order.  The workgroup has four waves (256 threads); wave w owns the
+// R = V / 4 ranges w * R ... w * R + R - 1, one accumulator each, so with R = 2 consecutive MFMAs are independent (the
+// dependent latency of the instruction is 40 cycles against 32 of issue).  Whenever K % (16 * V) == 0 - every decoder
+// product - the ranges are the 32x32 kernel's own and the output is bit-identical to sbl_gemm2_f32's; for other K the
+// ranges are rounded to 16 instead of 8 and only the rounding differs.
+//
+// MFMA operand map (16x16x4): lane l = (i = l & 15, g = l >> 4) supplies A[i][k] and B[k][j = i] for ONE k per instruction
+// and the instruction chains g = 0, 1, 2, 3.  The lane loads the float4 of row i at k = kb + 4g of a 16-deep group (a wave
+// load covers 16 rows x 64 contiguous bytes).  The 32x32 kernel's chain runs k = 0, 4, 1, 5 | 2, 6, 3, 7 through each 8 of K
+// (32x32x2 pairs k and k + 4), so lanes l and l ^ 32 first trade two of their four values (v_permlane32_swap: g = 0 / 1 keep
+// x, z and receive the partner's x, z as y, w; g = 2 / 3 receive the partner's y, w as x, z and keep y, w); afterwards
+// component x holds k = 0, 4, 1, 5 on g = 0, 1, 2, 3, z holds 2, 6, 3, 7, y holds 8, 12, 9, 13 and w 10, 14, 11, 15: the
+// MFMAs go x, z, y, w.
+// Needs K % 16 == 0, 16-byte aligned operands and lda % 4 == ldb % 4 == 0 (the host checks).
+__device__ __forceinline__ void sk16_trade(float& lo, float& hi) {      // lanes 32-63 of lo <-> lanes 0-31 of hi
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(lo), __float_as_uint(hi), false, false);
+    lo = __uint_as_float(r[0]);
+    hi = __uint_as_float(r[1]);
+}
+
+#define SBL_ROWS16_WAVES 4
+template <int V, int U>
+__global__ __launch_bounds__(SBL_ROWS16_WAVES * 64) void sbl_skinny16_gemm_kernel(SkinnyOperand<true> a, SkinnyOperand<true> b, SkinnyEpi e,
+                                                                                  SkinnyDual du, int M, int N, int K) {
+    constexpr int R = V / SBL_ROWS16_WAVES;
+    static_assert(R * SBL_ROWS16_WAVES == V, "whole ranges per wave");
+    __shared__ float red[V][256];
+    if (blockIdx.z) {
+        a.p = du.A1;
+        b.p = du.B1;
+        e.C = du.C1;
+        e.bias = du.bias1;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i15 = lane & 15, g = lane >> 4;
+    // XCD-aware tile order, as in sbl_skinny_gemm_kernel: XCD x takes the column tiles n = x (mod 8)
+    int mt = blockIdx.x, nt = blockIdx.y;
+    {
+        const int MT = gridDim.x, NT = gridDim.y;
+        if ((NT & 7) == 0) {
+            const int lin = blockIdx.y * MT + blockIdx.x;
+            const int xcd = lin & 7, q = lin >> 3;
+            mt = q % MT;
+            nt = (q / MT) * 8 + xcd;
+        }
+    }
+    const int m0 = mt * 16, n0 = nt * 16;
+    const int ra = min(m0 + i15, M - 1);     // clamped: rows beyond the edge are computed but never stored
+    const int rb = min(n0 + i15, N - 1);
+    // the V ranges of K: contiguous, multiples of 16, the last ones short or empty; range 0 of a wave is its longest
+    const int per = ((K + V - 1) / V + 15) & ~15;
+    int kbeg[R], kend[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        kbeg[j] = (wave * R + j) * per;
+        kend[j] = min(K, kbeg[j] + per);
+    }
+    const int len = kend[0] - kbeg[0];
+    sbl_stamp_begin(e.stamp);
+
+    f32x4 acc[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float4 a0[R][U], b0[R][U], a1[R][U], b1[R][U];      // two named register stages (static indexing only)
+#define SK_LOAD(AV, BV, O)                                                         \
+    _Pragma("unroll") for (int j = 0; j < R; ++j)                                  \
+    _Pragma("unroll") for (int u = 0; u < U; ++u) {                                \
+        AV[j][u] = a.load(ra, kbeg[j] + (O) + u * 16 + 4 * g, kend[j]);            \
+        BV[j][u] = b.load(rb, kbeg[j] + (O) + u * 16 + 4 * g, kend[j]);            \
+    }
+#define SK_MMA(AV, BV)                                                                                                        \
+    _Pragma("unroll") for (int u = 0; u < U; ++u) {                                                                           \
+        _Pragma("unroll") for (int j = 0; j < R; ++j) {                                                                       \
+            sk16_trade(AV[j][u].x, AV[j][u].y);                                                                               \
+            sk16_trade(AV[j][u].z, AV[j][u].w);                                                                               \
+            sk16_trade(BV[j][u].x, BV[j][u].y);                                                                               \
+            sk16_trade(BV[j][u].z, BV[j][u].w);                                                                               \
+        }                                                                                                                     \
+        _Pragma("unroll") for (int j = 0; j < R; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[j][u].x, BV[j][u].x, acc[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < R; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[j][u].z, BV[j][u].z, acc[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < R; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[j][u].y, BV[j][u].y, acc[j], 0, 0, 0); \
+        _Pragma("unroll") for (int j = 0; j < R; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[j][u].w, BV[j][u].w, acc[j], 0, 0, 0); \
+    }
+    SK_LOAD(a0, b0, 0)
+    for (int o = 0; o < len; o += 32 * U) {
+        const bool has1 = o + 16 * U < len;
+        if (has1) { SK_LOAD(a1, b1, o + 16 * U) }
+        SK_MMA(a0, b0)
+        if (o + 32 * U < len) { SK_LOAD(a0, b0, o + 32 * U) }
+        if (has1) { SK_MMA(a1, b1) }
+    }
+#undef SK_LOAD
+#undef SK_MMA
+    // meet in LDS: red[range][r*64 + lane] (conflict-free); element (r, lane) is C[m0 + 4g + r][n0 + i]
+#pragma unroll
+    for (int j = 0; j < R; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[wave * R + j][r * 64 + lane] = acc[j][r];
+    __syncthreads();
+    for (int el = tid; el < 256; el += SBL_ROWS16_WAVES * 64) {
+        float v = 0.f;
+#pragma unroll
+        for (int w = 0; w < V; ++w) v += red[w][el];
+        const int r = el >> 6, ln = el & 63;
+        const int m = m0 + 4 * (ln >> 4) + r;
+        const int n = n0 + (ln & 15);
+        if (m < M && n < N) {
+            if (e.bias) v += e.bias[n];
+            if (e.relu) v = fmaxf(v, 0.f);
+            e.C[(long)m * e.ldc + n] = v;
+        }
+    }
+    sbl_stamp_end(e.stamp);
+}
+
+// (V, U) by K: V is sbl_launch_skinny's NW (what makes the sums the same), U is sbl_rows16_deep_k in tuning.h.  Returns V * 16 + U.
+static inline int sbl_launch_skinny16(const float* A, long lda, const float* B, long ldb, const SkinnyEpi& e, const SkinnyDual& du,
+                                      int M, int N, int K, hipStream_t s) {
+    SkinnyOperand<true> a{A, lda, M};
+    SkinnyOperand<true> b{B, ldb, N};
+    const dim3 grid(sbl_cdiv(M, 16), sbl_cdiv(N, 16), 2), block(SBL_ROWS16_WAVES * 64);
+    if (K >= sbl_rows16_deep_k) { hipLaunchKernelGGL((sbl_skinny16_gemm_kernel<8, 4>), grid, block, 0, s, a, b, e, du, M, N, K); return 8 * 16 + 4; }
+    if (K >= 512) { hipLaunchKernelGGL((sbl_skinny16_gemm_kernel<8, 2>), grid, block, 0, s, a, b, e, du, M, N, K); return 8 * 16 + 2; }
+    hipLaunchKernelGGL((sbl_skinny16_gemm_kernel<4, 2>), grid, block, 0, s, a, b, e, du, M, N, K);
+    return 4 * 16 + 2;
+}
+
 template <bool AKC, bool BKC>
 static inline void sbl_launch_skinny(const float* A, long lda, const float* B, long ldb, const SkinnyEpi& e, int M, int N,
                                      int K, hipStream_t s, const SkinnyDual* dual = nullptr) {

@@ -24,6 +24,19 @@ constexpr int sbl_wave_ksplit_max_tiles = 320;   // largest tile count that take
 // many workgroups, at most this many ways (target 128 / 256 / 512: 30.40 / 30.34 / 30.52 ms; up to 16 splits: 30.56; splitting
 // the 192-640-tile launches too, targets 512 / 1024: 32.77 / 31.22 against 31.07 ms)
 constexpr int sbl_gemm2_split_tiles = 192, sbl_gemm2_split_target = 256, sbl_gemm2_split_max = 8;
+// row-starved two-direction products (sbl_gemm2_rows_f32): a launch whose 32x32 tiling would give fewer than this many
+// workgroups (2 * cdiv(M, 32) * cdiv(N, 32)) takes 16x16 tiles (sbl_skinny16_gemm_kernel) instead
+// (same-box step A/B, parent / this value, three interleaved runs each: 30.161, 30.262, 30.177 / 29.908, 29.939, 29.812 ms;
+// kernel trace: K = 2048 launches 29.0 -> 14.9 us, the moved K = 512 ones 10.0 -> 6.4 us.  Only this value was run in the step.)
+constexpr int sbl_rows16_max_wgs32 = 256;
+// ... and at most this many rows per direction: sbl_gemm2_f32's bound for its 32x32 skinny kernel (max_m), whose sums the 16x16
+// kernel repeats term by term.  Above it the K = 2048 products come from the tiled split-K route, and moving them (M = 144...224,
+// the optional second step) changes their rounding: with dropout on, the two row layouts of the last decoder layer then differ
+// by 1.4 x the bound that tests/test_decoder_last_layer_rows_gpu.py holds them to (f32, alternating coins)
+constexpr int sbl_rows16_max_m = 128;
+// ... its register stages: 4 16-deep groups per range and stage from this K on (K = 2048: a range is 256 deep, half of it in
+// flight per stage), 2 below (K = 512: both stages together hold a whole 64-deep range)
+constexpr int sbl_rows16_deep_k = 1024;
 
 // ---- trunk convolutions (conv.hip, conv_patch_wgrad.h)
 constexpr int sbl_pm_max_hw = 121;               // largest Ho*Wo of a 3x3 / stride-1 convolution that takes the position-major path (ResNet
