@@ -676,6 +676,20 @@ int sbl_opt_finalize(double* state, const double* partials, long nparts, double 
  * written: p, m, v keep their bits. */
 int sbl_adam_step_dev(float* p, const float* g, float* m, float* v, long n, const double* state, float beta1, float beta2,
                       float eps, float grad_scale, float clip_value, sbl_stream_t stream);
+/* sbl_adam_step_dev with an exponential moving average of the weights in the same launch: p, m, v are updated by that
+ * kernel's arithmetic (bit-identical to it), then e += w * (p_new - e) in fp32 (the difference rounded, product and sum one
+ * fused multiply-add) with w = (float)(1 - d_t) and d_t in double from t = state[SBL_OPT_STEP], the count AFTER
+ * sbl_opt_finalize's increment: d_t = min(ema_decay, (1 + t) / (10 + t)) when ema_warmup != 0, else ema_decay.  Every
+ * thread derives w itself: no extra launch, no state slot.  Order in a step: sbl_grad_sumsq, sbl_opt_finalize, then this
+ * in place of sbl_adam_step_dev.  With state[SBL_OPT_SKIP] set nothing is written: p, m, v, e keep their bits.  ema_decay
+ * must lie in (0, 1); 16-byte accesses when all five buffers are 16-byte aligned. */
+int sbl_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* e, long n, const double* state, float beta1,
+                          float beta2, float eps, float grad_scale, float clip_value, double ema_decay, int ema_warmup,
+                          sbl_stream_t stream);
+/* a[i] <-> b[i] for i in [0, n), in place and exact (each element is read from both buffers and written to both by one
+ * thread); the launch geometry of the kernels above.  The two ranges must not overlap.  It reads no state: the caller
+ * decides when an exchange is due (FusedAdam.swap_ema: live weights <-> their average, then the weight re-pack). */
+int sbl_swap_f32(float* a, float* b, long n, sbl_stream_t stream);
 
 #ifdef __cplusplus
 }

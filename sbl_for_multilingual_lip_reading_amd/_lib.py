@@ -92,6 +92,8 @@ SIGNATURES = {
     "sbl_grad_sumsq": [P, L, F, F, P, L, L, P],
     "sbl_opt_finalize": [P, P, L, D, I, D, D, F, F, P],
     "sbl_adam_step_dev": [P, P, P, P, L, P, F, F, F, F, F, P],
+    "sbl_adam_ema_step_dev": [P, P, P, P, P, L, P, F, F, F, F, F, D, I, P],
+    "sbl_swap_f32": [P, P, L, P],
     "sbl_preprocess_clips": [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_set_matmul_precision": [I],
     "sbl_set_tuning": [I, I],

@@ -12,6 +12,8 @@ nothing is ever unpickled:
   * `save_checkpoint` writes the same plain-tensor format (+ the flat Adam moments when a FusedAdam is given), which
     the reference loads with `model.load_state_dict(torch.load(path)['model_state_dict'])`.
 """
+import contextlib
+
 import torch
 
 
@@ -27,13 +29,23 @@ def _to_cpu(obj):
     raise TypeError("optimizer state holds a %s: only tensors, numbers, strings and containers of them are saved" % type(obj).__name__)
 
 
-def save_checkpoint(path, model, optimizer=None, **meta):
+def save_checkpoint(path, model, optimizer=None, averaged=False, **meta):
     """model: Transformer (or any module of this package).  optimizer: TransformerOptimizer / DeviceNoamOptimizer / FusedAdam /
-    None.  A device-mode FusedAdam carries its device state buffer as the tensor `opt_state` of its state dict."""
+    None.  A device-mode FusedAdam carries its device state buffer as the tensor `opt_state` of its state dict, and one
+    built with ema_decay its weight average as `ema`.
+
+    averaged=True (needs such an averaging optimizer): `model_state_dict` is taken inside optimizer.averaged(), so the file
+    holds the AVERAGED weights under the reference's names and the reference's test.py evaluates them as they are;
+    `optimizer_state` is the live state as always (moments, step, and the same average as `ema`), but the live weights are
+    in no field of such a file: to resume training, also keep a checkpoint written with averaged=False."""
     m = model.module if hasattr(model, "module") else model          # nn.DataParallel wrapper, SBL/train.py:246-250
-    out = {"model_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}}
+    inner = getattr(optimizer, "optimizer", optimizer)
+    if averaged and getattr(inner, "ema", None) is None:
+        raise ValueError("save_checkpoint(averaged=True) needs a FusedAdam built with ema_decay")
+    # a caller already inside averaged() gets the averaged weights without a second exchange
+    with (inner.averaged() if averaged and not inner._averaging else contextlib.nullcontext()):
+        out = {"model_state_dict": {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}}
     if optimizer is not None:
-        inner = getattr(optimizer, "optimizer", optimizer)
         out["step_num"] = int(getattr(optimizer, "step_num", 0))
         # FusedAdam: flat tensors and scalars; torch.optim.Adam (the reference's optimizer, SBL/train.py:75): nested
         # {'state': {idx: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} - plain containers of tensors and

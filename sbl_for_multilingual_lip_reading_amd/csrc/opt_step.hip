@@ -1,6 +1,8 @@
 // Device-side optimizer step: gradient sum of squares -> (norm, clip coefficient, step count, rate, bias corrections, skip
 // flag) in a double[8] state buffer -> Adam that reads every per-step scalar from that buffer.  Nothing returns to the host
-// between the three launches, so zero_grad + forward + backward + update can be captured as one hipGraph.
+// between the three launches, so zero_grad + forward + backward + update can be captured as one hipGraph.  The Adam launch
+// can also keep an exponential moving average of the weights (sbl_adam_ema_step_dev), and sbl_swap_f32 exchanges live and
+// averaged weights in place for evaluation.
 #include "sbl_common.h"
 
 #include <math.h>
@@ -186,14 +188,8 @@ extern "C" int sbl_opt_finalize(double* state, const double* partials, long npar
 // ------------------------------------------------------------------ Adam, per-step scalars from the state buffer
 // g' = clamp(g * gscale) * coef, then adam_kernel's arithmetic (misc.hip) in its order.  A skipped step returns before the
 // first store: p, m, v keep their bits.
-template <bool VEC>
-__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, long n, const double* __restrict__ st, float b1,
-                                                       float b2, float eps, float gscale, float clip) {
-    if (st[SBL_OPT_SKIP] != 0.0) return;
-    const float coef = (float)st[SBL_OPT_CLIP_COEF];
-    const float step_size = (float)st[SBL_OPT_STEP_SIZE], inv_sqrt_bc2 = (float)st[SBL_OPT_INV_SQRT_BC2];
-    const long n4 = n >> 2;
+// One element of the update; both Adam kernels below expand it, so their p, m, v agree bit for bit.  It reads gscale,
+// clip, coef, b1, b2, step_size, inv_sqrt_bc2 and eps from the kernel that expands it.
 #define SBL_ADAM_ONE(P, G, M, V)                                         \
     do {                                                                 \
         const float gi = clamp_nan((G) * gscale, clip) * coef;           \
@@ -203,6 +199,14 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
         (V) = vi;                                                        \
         (P) -= step_size * mi / (sqrtf(vi) * inv_sqrt_bc2 + eps);        \
     } while (0)
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, long n, const double* __restrict__ st, float b1,
+                                                       float b2, float eps, float gscale, float clip) {
+    if (st[SBL_OPT_SKIP] != 0.0) return;
+    const float coef = (float)st[SBL_OPT_CLIP_COEF];
+    const float step_size = (float)st[SBL_OPT_STEP_SIZE], inv_sqrt_bc2 = (float)st[SBL_OPT_INV_SQRT_BC2];
+    const long n4 = n >> 2;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 g4 = load4<VEC>(g, i);
         float4 p4 = load4<VEC>(p, i), m4 = load4<VEC>(m, i), v4 = load4<VEC>(v, i);
@@ -222,7 +226,6 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, co
         v[j] = vj;
         p[j] = pj;
     }
-#undef SBL_ADAM_ONE
 }
 extern "C" int sbl_adam_step_dev(float* p, const float* g, float* m, float* v, long n, const double* state, float beta1,
                                  float beta2, float eps, float grad_scale, float clip_value, sbl_stream_t stream) {
@@ -238,5 +241,106 @@ extern "C" int sbl_adam_step_dev(float* p, const float* g, float* m, float* v, l
         hipLaunchKernelGGL(adam_dev_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, state, beta1, beta2,
                            eps, grad_scale, clip_value);
     SBL_LAUNCH_CHECK("sbl_adam_step_dev");
+    return 0;
+}
+
+// ------------------------------------------------------------------ Adam + exponential moving average of the weights
+// SBL_ADAM_ONE for p, m, v (adam_dev_kernel's bits), then e += w * (p_new - e) in fp32: the difference is rounded, the
+// product and the sum are one fused multiply-add.  w = (float)(1 - d_t) with d_t in double from t = st[SBL_OPT_STEP], the
+// count sbl_opt_finalize has already advanced: d_t = min(decay, (1 + t) / (10 + t)) under warm-up, else decay.  Every
+// thread derives w itself (two double operations): no launch and no state slot of its own.  A skipped step returns before
+// the first store: p, m, v, e keep their bits.
+template <bool VEC>
+__global__ __launch_bounds__(256) void adam_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, float* __restrict__ e, long n,
+                                                           const double* __restrict__ st, float b1, float b2, float eps,
+                                                           float gscale, float clip, double decay, int warm) {
+    if (st[SBL_OPT_SKIP] != 0.0) return;
+    const float coef = (float)st[SBL_OPT_CLIP_COEF];
+    const float step_size = (float)st[SBL_OPT_STEP_SIZE], inv_sqrt_bc2 = (float)st[SBL_OPT_INV_SQRT_BC2];
+    const double t = st[SBL_OPT_STEP];
+    const double d_t = warm ? fmin(decay, (1.0 + t) / (10.0 + t)) : decay;
+    const float w = (float)(1.0 - d_t);
+    const long n4 = n >> 2;
+#define SBL_EMA_ONE(E, P) (E) = __fmaf_rn(w, (P) - (E), (E))
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 g4 = load4<VEC>(g, i);
+        float4 p4 = load4<VEC>(p, i), m4 = load4<VEC>(m, i), v4 = load4<VEC>(v, i), e4 = load4<VEC>(e, i);
+        SBL_ADAM_ONE(p4.x, g4.x, m4.x, v4.x);
+        SBL_ADAM_ONE(p4.y, g4.y, m4.y, v4.y);
+        SBL_ADAM_ONE(p4.z, g4.z, m4.z, v4.z);
+        SBL_ADAM_ONE(p4.w, g4.w, m4.w, v4.w);
+        SBL_EMA_ONE(e4.x, p4.x);
+        SBL_EMA_ONE(e4.y, p4.y);
+        SBL_EMA_ONE(e4.z, p4.z);
+        SBL_EMA_ONE(e4.w, p4.w);
+        store4<VEC>(m, i, m4);
+        store4<VEC>(v, i, v4);
+        store4<VEC>(p, i, p4);
+        store4<VEC>(e, i, e4);
+    }
+    const long j = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && j < n) {
+        float pj = p[j], mj = m[j], vj = v[j], ej = e[j];
+        SBL_ADAM_ONE(pj, g[j], mj, vj);
+        SBL_EMA_ONE(ej, pj);
+        m[j] = mj;
+        v[j] = vj;
+        p[j] = pj;
+        e[j] = ej;
+    }
+#undef SBL_EMA_ONE
+}
+#undef SBL_ADAM_ONE
+extern "C" int sbl_adam_ema_step_dev(float* p, const float* g, float* m, float* v, float* e, long n, const double* state,
+                                     float beta1, float beta2, float eps, float grad_scale, float clip_value, double ema_decay,
+                                     int ema_warmup, sbl_stream_t stream) {
+    SBL_REQUIRE(p && g && m && v && e && state, "sbl_adam_ema_step_dev: null pointer");
+    SBL_REQUIRE(n > 0, "sbl_adam_ema_step_dev: n=%ld must be positive", n);
+    SBL_REQUIRE(opt_aligned8(state), "sbl_adam_ema_step_dev: unaligned state buffer");
+    SBL_REQUIRE(((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)e)) & 3) == 0,
+                "sbl_adam_ema_step_dev: unaligned buffer");
+    SBL_REQUIRE(ema_decay > 0.0 && ema_decay < 1.0, "sbl_adam_ema_step_dev: ema_decay=%g outside (0, 1)", ema_decay);
+    const int grid = opt_grid(n);
+    if (sbl_aligned16(p) && sbl_aligned16(g) && sbl_aligned16(m) && sbl_aligned16(v) && sbl_aligned16(e))
+        hipLaunchKernelGGL(adam_ema_dev_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, e, n, state, beta1,
+                           beta2, eps, grad_scale, clip_value, ema_decay, ema_warmup);
+    else
+        hipLaunchKernelGGL(adam_ema_dev_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, e, n, state, beta1,
+                           beta2, eps, grad_scale, clip_value, ema_decay, ema_warmup);
+    SBL_LAUNCH_CHECK("sbl_adam_ema_step_dev");
+    return 0;
+}
+
+// ------------------------------------------------------------------ exchange of two buffers
+// a[i] <-> b[i]: every element is loaded from both sides by the one thread that then stores it to both, so the exchange
+// is exact and needs no scratch; the ranges must not overlap (the host refuses).
+template <bool VEC>
+__global__ __launch_bounds__(256) void swap_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const float4 a4 = load4<VEC>(a, i), b4 = load4<VEC>(b, i);
+        store4<VEC>(a, i, b4);
+        store4<VEC>(b, i, a4);
+    }
+    const long j = (n4 << 2) + threadIdx.x;
+    if (blockIdx.x == 0 && j < n) {
+        const float aj = a[j], bj = b[j];
+        a[j] = bj;
+        b[j] = aj;
+    }
+}
+extern "C" int sbl_swap_f32(float* a, float* b, long n, sbl_stream_t stream) {
+    SBL_REQUIRE(a && b, "sbl_swap_f32: null pointer");
+    SBL_REQUIRE(n > 0, "sbl_swap_f32: n=%ld must be positive", n);
+    SBL_REQUIRE(((((uintptr_t)a) | ((uintptr_t)b)) & 3) == 0, "sbl_swap_f32: unaligned buffer");
+    const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+    SBL_REQUIRE(ua < ub ? ub - ua >= bytes : ua - ub >= bytes, "sbl_swap_f32: the two ranges of %ld elements overlap", n);
+    const int grid = opt_grid(n);
+    if (sbl_aligned16(a) && sbl_aligned16(b))
+        hipLaunchKernelGGL(swap_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    else
+        hipLaunchKernelGGL(swap_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a, b, n);
+    SBL_LAUNCH_CHECK("sbl_swap_f32");
     return 0;
 }

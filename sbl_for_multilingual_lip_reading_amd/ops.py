@@ -1708,6 +1708,23 @@ def adam_step_dev(p, g, m, v, state, beta1, beta2, eps, grad_scale=1.0, clip_val
     call("sbl_adam_step_dev", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(state), beta1, beta2, eps, grad_scale, clip_value, _s())
 
 
+def adam_ema_step_dev(p, g, m, v, e, state, beta1, beta2, eps, grad_scale=1.0, clip_value=0.0, ema_decay=0.9999, ema_warmup=True):
+    """adam_step_dev plus, in the same launch, e += w * (p_new - e) with w = 1 - d_t derived from state[OPT_STEP]: d_t =
+    min(ema_decay, (1 + t) / (10 + t)) under warm-up, else ema_decay.  A skipped step leaves e alone too."""
+    _need_cuda(p, g, m, v, e, state)
+    assert state.dtype == torch.float64 and state.numel() == OPT_STATE_SLOTS
+    assert g.numel() == m.numel() == v.numel() == e.numel() == p.numel()
+    call("sbl_adam_ema_step_dev", _p(p), _p(g), _p(m), _p(v), _p(e), p.numel(), _p(state), beta1, beta2, eps, grad_scale,
+         clip_value, ema_decay, int(bool(ema_warmup)), _s())
+
+
+def swap_(a, b):
+    """Exchange the contents of two non-overlapping contiguous fp32 buffers in place (exact; one launch, no scratch)."""
+    _need_cuda(a, b)
+    assert a.dtype == b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    call("sbl_swap_f32", _p(a), _p(b), a.numel(), _s())
+
+
 _LUT = {}
 
 

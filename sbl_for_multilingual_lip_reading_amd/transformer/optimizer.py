@@ -51,12 +51,22 @@ class FusedAdam(object):
                       device copy: that variant is for eager use)
     In data-parallel mode nothing else is needed: step() runs after GradientExchange.finish() on the summed gradient and
     grad_scale applies before the norm.  The kernels sum in an order fixed by the range lengths alone (no atomics), so
-    replicas holding the same gradient derive bit-identical coefficients and stay in step."""
+    replicas holding the same gradient derive bit-identical coefficients and stay in step.
+
+    WEIGHT AVERAGING (ema_decay in (0, 1); turns device mode on).  `ema` is a second flat buffer, a clone of the parameters
+    at construction, and the update launch (sbl_adam_ema_step_dev in place of sbl_adam_step_dev) also does
+    ema += (1 - d_t) * (p_new - ema), d_t = min(ema_decay, (1 + t) / (10 + t)) with ema_warmup (t: applied steps), else
+    ema_decay: one more read and write in the pass that already streams p, g, m, v.  A skipped step and a frozen range
+    leave it alone, so frozen parameters keep ema == p.  `with opt.averaged(): model.validate(...)` evaluates the averaged
+    weights; swap_ema() is the exchange it is made of; reset_ema() restarts the average from weights loaded by hand.  The
+    average travels in state_dict() as `ema` / `ema_decay`."""
 
     def __init__(self, flat, lr=1e-3, betas=(0.9, 0.98), eps=1e-9, grad_scale=1.0, max_grad_norm=None, clip_value=None,
-                 skip_nonfinite=False, noam=None):
+                 skip_nonfinite=False, noam=None, ema_decay=None, ema_warmup=True):
         import torch
         from ._env import ops
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError("ema_decay must lie in (0, 1), got %r" % (ema_decay,))
         self._ops = ops
         self.flat = flat
         self.param_groups = [{"params": list(flat.model.parameters()), "lr": lr, "betas": betas, "eps": eps}]
@@ -68,7 +78,12 @@ class FusedAdam(object):
         self.clip_value = float(clip_value) if clip_value else 0.0
         self.skip_nonfinite = bool(skip_nonfinite)
         self.noam = (float(noam[0]), float(noam[1])) if noam is not None else None
-        self.device_mode = bool(self.max_grad_norm or self.clip_value or self.skip_nonfinite or self.noam is not None)
+        self.ema_decay = float(ema_decay) if ema_decay is not None else None
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = flat.flat_param.clone() if self.ema_decay is not None else None
+        self._averaging = False          # inside averaged(): the flat parameters hold the average, `ema` the live weights
+        self.device_mode = bool(self.max_grad_norm or self.clip_value or self.skip_nonfinite or self.noam is not None
+                                or self.ema_decay is not None)
         if self.device_mode:
             if self.max_grad_norm < 0 or self.clip_value < 0 or (self.noam and min(self.noam) <= 0):
                 raise ValueError("max_grad_norm, clip_value, and noam's k and warmup_steps must be positive")
@@ -142,6 +157,8 @@ class FusedAdam(object):
         Adam(filter(lambda p: p.requires_grad, model.parameters())) in SBL/train.py:75, frozen parameters and their
         moments are left untouched."""
         g = self.param_groups[0]
+        if self._averaging:
+            raise RuntimeError("FusedAdam.step() inside averaged(): the parameters hold the averaged weights")
         if self.device_mode:
             return self._step_device(g)
         self.step_count += 1
@@ -167,18 +184,59 @@ class FusedAdam(object):
         o.opt_finalize(self.opt_state, self._partials, nparts, self.max_grad_norm, self.skip_nonfinite, self.noam,
                        g["betas"][0], g["betas"][1])
         for a, b in ranges:
-            o.adam_step_dev(f.flat_param[a:b], f.flat_grad[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], self.opt_state,
-                            g["betas"][0], g["betas"][1], g["eps"], self.grad_scale, self.clip_value)
+            if self.ema is not None:
+                o.adam_ema_step_dev(f.flat_param[a:b], f.flat_grad[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], self.ema[a:b],
+                                    self.opt_state, g["betas"][0], g["betas"][1], g["eps"], self.grad_scale, self.clip_value,
+                                    self.ema_decay, self.ema_warmup)
+            else:
+                o.adam_step_dev(f.flat_param[a:b], f.flat_grad[a:b], self.exp_avg[a:b], self.exp_avg_sq[a:b], self.opt_state,
+                                g["betas"][0], g["betas"][1], g["eps"], self.grad_scale, self.clip_value)
         o.refresh_packed_weights()
+
+    # ---- weight averaging
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("FusedAdam: no weight average is kept (build the optimizer with ema_decay)")
+
+    def reset_ema(self):
+        """Restart the average from the current weights (after weights were loaded by hand)."""
+        self._need_ema()
+        if self._averaging:
+            raise RuntimeError("FusedAdam.reset_ema() inside averaged()")
+        self.ema.copy_(self.flat.flat_param)
+
+    def swap_ema(self):
+        """Exchange live and averaged weights in place over the trainable ranges (frozen ranges hold ema == p), exactly,
+        then re-pack the cached convolution weight images: one sbl_swap_f32 per range, no allocation and no read-back, so
+        it can be captured.  Twice is the identity."""
+        self._need_ema()
+        for a, b in self.flat.trainable_ranges():
+            self._ops.swap_(self.flat.flat_param[a:b], self.ema[a:b])
+        self._ops.refresh_packed_weights()
+
+    def averaged(self):
+        """Context manager: inside it the model's parameters are the averaged ones, so Transformer.validate, recognize*,
+        checkpoint.save_checkpoint and the model's state_dict() see them; the live weights come back on exit, also when the
+        body raises.  BatchNorm running statistics are buffers, not parameters: they are NOT averaged, the live ones are
+        used.  step() inside the context raises.  Entry and exit are one swap_ema() each (capturable)."""
+        self._need_ema()
+        return _Averaged(self)
 
     def state_dict(self):
         if self.device_mode:
-            return {"step": self.steps_applied, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                    "lr": self.param_groups[0]["lr"], "opt_state": self.opt_state}
+            sd = {"step": self.steps_applied, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
+                  "lr": self.param_groups[0]["lr"], "opt_state": self.opt_state}
+            if self.ema is not None:
+                # inside averaged() the two buffers have changed places (frozen ranges are equal in both)
+                sd["ema"] = self.flat.flat_param if self._averaging else self.ema
+                sd["ema_decay"] = self.ema_decay
+            return sd
         return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
                 "lr": self.param_groups[0]["lr"]}
 
     def load_state_dict(self, sd):
+        if self._averaging:
+            raise RuntimeError("FusedAdam.load_state_dict() inside averaged()")
         self.step_count = int(sd["step"])
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
@@ -189,6 +247,30 @@ class FusedAdam(object):
                 self._lr_uploaded = None          # the next eager step uploads param_groups' rate again
             else:                                 # a default-mode checkpoint: only the step count is known
                 self._write_state(self.step_count)
+        if self.ema is not None:                  # a stored average is ignored when this optimizer keeps none
+            if sd.get("ema") is not None:
+                self.ema.copy_(sd["ema"])
+            else:                                 # no average in the checkpoint: start it from the weights as loaded
+                self.ema.copy_(self.flat.flat_param)      # (checkpoint.load_checkpoint loads the model first)
+
+
+class _Averaged(object):
+    """FusedAdam.averaged(): swap_ema() on entry and on exit."""
+
+    def __init__(self, opt):
+        self.opt = opt
+
+    def __enter__(self):
+        if self.opt._averaging:
+            raise RuntimeError("FusedAdam.averaged() does not nest")
+        self.opt.swap_ema()
+        self.opt._averaging = True
+        return self.opt
+
+    def __exit__(self, *exc):
+        self.opt._averaging = False
+        self.opt.swap_ema()
+        return False
 
 
 def _f32(x):
@@ -216,6 +298,15 @@ class DeviceNoamOptimizer(object):
 
     def step(self):
         return self.optimizer.step()
+
+    def swap_ema(self):
+        return self.optimizer.swap_ema()
+
+    def averaged(self):
+        return self.optimizer.averaged()
+
+    def reset_ema(self):
+        return self.optimizer.reset_ema()
 
     @property
     def lr(self):

@@ -8,6 +8,11 @@ bf16x6 by default) and prints one JSON line:
   (c) eager_default_ms   zero_grad, forward, loss, backward, TransformerOptimizer(FusedAdam(default)).step(), issued eagerly
   (d) eager_device_ms    the same step with DeviceNoamOptimizer(FusedAdam(max_grad_norm, skip_nonfinite, noam))
   (e) graph_device_ms    step (d) captured once as one hipGraph and replayed
+  (f) update_plain_us    (b) again, in the group of the two below
+  (g) update_ema_us      the update with the weight average in the same launch (sbl_adam_ema_step_dev in place of sbl_adam_step_dev)
+  (h) update_lerp_us     (b) followed by torch.Tensor.lerp_ of the average over the same ranges (the unfused alternative)
+      8, 10 and 11 fp32 accesses per element
+  (i) swap_ema_us        FusedAdam.swap_ema(): sbl_swap_f32 over the trainable ranges + the weight re-pack
 
 Every figure is the median over --rounds windows of --steps calls (device events around each window, after --warmup calls);
 the variants of a group alternate inside each round, and *_spread is (max - min) / median over the rounds.
@@ -74,6 +79,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--update-reps", type=int, default=50, help="calls per window of the update-only timings (a), (b)")
+    ap.add_argument("--ema-decay", type=float, default=0.9999, help="decay of the weight average in (f), (h) and the exchange")
     ap.add_argument("--precision", default="bf16x6")
     ap.add_argument("--peak-tbs", type=float, default=8.0, help="HBM peak the byte rates are quoted against")
     args = ap.parse_args()
@@ -157,11 +163,47 @@ def main():
 
         u = alternate({"adam": adam_host, "device_update": update_device, "sumsq_finalize": sumsq_only}, args.update_reps, 5,
                       args.rounds)
+
+        # ---- (f), (g), (h): the update with and without the weight average, and the average as a pass of its own
+        fe = FusedAdam(flat, max_grad_norm=5.0, skip_nonfinite=True, noam=(0.2, 4000), ema_decay=args.ema_decay)
+        lerp_w = 1.0 - args.ema_decay
+
+        def update_ema():
+            nparts = 0
+            for a, b in ranges:
+                nparts += ops.grad_sumsq(flat.flat_grad[a:b], fe._partials, nparts, 1.0, 0.0)
+            ops.opt_finalize(fe.opt_state, fe._partials, nparts, fe.max_grad_norm, True, fe.noam, 0.9, 0.98)
+            for a, b in ranges:
+                ops.adam_ema_step_dev(flat.flat_param[a:b], flat.flat_grad[a:b], fe.exp_avg[a:b], fe.exp_avg_sq[a:b], fe.ema[a:b],
+                                      fe.opt_state, 0.9, 0.98, 1e-9, 1.0, 0.0, fe.ema_decay, fe.ema_warmup)
+
+        def update_then_lerp():
+            update_device()
+            for a, b in ranges:
+                fe.ema[a:b].lerp_(flat.flat_param[a:b], lerp_w)
+
+        def swap_and_repack():
+            fe.swap_ema()
+
+        e = alternate({"update_plain": update_device, "update_ema": update_ema, "update_lerp": update_then_lerp},
+                      args.update_reps, 5, args.rounds)
+        # an even number of exchanges per window and in the warm-up: the weights end where they started
+        e.update(alternate({"swap_ema": swap_and_repack}, args.update_reps // 2 * 2, 4, args.rounds))
     for k, acc in (("adam", 7), ("device_update", 8), ("sumsq_finalize", 1)):
         ms, spread = u[k]
         nbytes = acc * 4 * n
         out[k + "_us"], out[k + "_spread"], out[k + "_bytes"] = round(ms * 1e3, 1), round(spread, 4), nbytes
         out[k + "_frac_of_peak"] = round(nbytes / (ms * 1e-3) / (args.peak_tbs * 1e12), 4)
+    # 8 accesses per element without the average, 10 with it in the update launch, 8 + 3 with torch's lerp_ after the update;
+    # the exchange moves 4 (the weight re-pack it ends with is not counted in its bytes)
+    for k, acc in (("update_plain", 8), ("update_ema", 10), ("update_lerp", 11), ("swap_ema", 4)):
+        ms, spread = e[k]
+        nbytes = acc * 4 * n
+        out[k + "_us"], out[k + "_spread"], out[k + "_bytes"] = round(ms * 1e3, 1), round(spread, 4), nbytes
+        out[k + "_frac_of_peak"] = round(nbytes / (ms * 1e-3) / (args.peak_tbs * 1e12), 4)
+    out["ema_decay"] = args.ema_decay
+    out["ema_over_plain_time"], out["ema_over_plain_bytes"] = round(e["update_ema"][0] / e["update_plain"][0], 4), round(10 / 8, 4)
+    out["ema_over_lerp_time"], out["ema_over_lerp_bytes"] = round(e["update_ema"][0] / e["update_lerp"][0], 4), round(10 / 11, 4)
     out["device_over_adam_time"] = round(u["device_update"][0] / u["adam"][0], 4)
     out["device_over_adam_bytes"] = round(8 / 7, 4)
     out["graph_over_eager_device"] = round(r["graph_device"][0] / r["eager_device_again"][0], 4)
