@@ -502,7 +502,8 @@ def test_basic_block_chain_fwd_bwd(ops):
     oracle, so that backward takes the cross-block path: every BatchNorm's backward sums but the last bn2's come from an
     input-gradient epilogue.  Then the same chain with the hand-off severed (each block's output cloned before the next
     block), which takes the sbl_bn_bwd_reduce fallback for every bn2 and the downsample BN: two fresh forward passes,
-    compared under the float-reorder bound of test_backward_cut_at_frontend_features_equals_single_backward.
+    compared under the bound of test_backward_cut_at_frontend_features_equals_single_backward (two evaluations that may take
+    one ReLU decision differently; tests/test_frontend_grads_gpu.py holds the severed chain of the whole trunk tightly).
     Tolerances are test_basic_block_fwd_bwd's (5e-5 / 5e-4 / 1e-3 / 1e-5) and that test's 3e-2: the implementation with
     three tape nodes per block, which this test was first run on, measured 9.5e-6 / 9.5e-7 / 1.9e-6 / 1.2e-7 and, for
     the severed chain, 5.1e-7 (worst of both arithmetics)."""
@@ -961,7 +962,8 @@ def test_frontend_small_golden(ops, golden_modules):
               "resnet18.layer1.0.bn1.weight", "resnet18.layer2.0.conv1.weight", "resnet18.layer2.0.downsample.0.weight",
               "resnet18.layer3.0.downsample.1.bias"):
         ref = g["fe.grad:" + k]
-        # 17 stacked train-mode BatchNorms over only 12 images: ill-conditioned (see test_oracle_golden.py)
+        # the fixture is the reference's own fp32 evaluation: one ReLU / pool decision taken differently moves these by 1e-2
+        # (DESIGN.md section 2, fact 1); the composed backward is held tightly by tests/test_frontend_grads_gpu.py
         assert relerr(params[k].grad, ref) < 2e-2, (k, relerr(params[k].grad, ref))
     sd = fe.state_dict()
     assert maxdiff(sd["frontend3D.1.running_mean"], g["fe.after:frontend3D.1.running_mean"]) < 1e-6
@@ -1107,8 +1109,9 @@ def test_e2e_train_step_golden(ops, tag):
     assert d_l < 1e-3 and d_r < 1e-3
     assert np.array_equal(pl.argmax(-1).cpu().numpy(), g["argmax_l2r"]) and np.array_equal(pr.argmax(-1).cpu().numpy(), g["argmax_r2l"])
     assert abs(loss.item() - float(g["loss"])) < 1e-3
-    # gradients: norms within 2 % for every one of the 475 parameters (frontend grads are ill-conditioned through
-    # 17 train-mode BatchNorms at batch 2; transformer grads agree to ~1e-4), full tensors for the stored ones
+    # gradients: norms within 2 % for every one of the 475 parameters (a frontend ReLU / pool decision that the reference's
+    # fp32 evaluation took differently moves frontend gradients by 1e-2, see tests/test_frontend_grads_gpu.py for the tight
+    # check; transformer grads agree to ~1e-4), full tensors for the stored ones
     named = dict(m.named_parameters())
     worst = 0.0
     for n, ref in zip(g["grad_names"], g["grad_norms"]):
@@ -1325,7 +1328,7 @@ def test_flat_direct_accumulation_and_two_streams_match_plain_autograd(ops, B):
     assert maxdiff(pl2, pl1) < 2e-5 and abs(loss1 - loss2) < 1e-5
     for n, p in m2.named_parameters():
         ref = g1[n]
-        tol = 2e-2 if n.startswith("visual_frontend") else 1e-3     # BN-amplified fp32 reorder noise, see above
+        tol = 2e-2 if n.startswith("visual_frontend") else 1e-3     # one differing ReLU / pool decision: tests/test_frontend_grads_gpu.py
         d = maxdiff(p.grad, ref)
         if "pos_ffn" in n and not d < tol * float(ref.abs().max()) + 2e-6:
             # a feed-forward pre-activation within rounding of zero: the two paths (one launch per direction / both
@@ -1382,7 +1385,7 @@ def test_backward_cut_at_frontend_features_equals_single_backward(ops):
     for seg, (a, b) in grads[0][1].items():
         ref, got = grads[0][0][a:b].double(), grads[1][0][a:b].double()
         rel = float((got - ref).norm() / ref.norm())
-        assert rel < (3e-2 if seg.startswith("visual") else 1e-4), (seg, rel)      # BN-amplified reorder noise in the frontend
+        assert rel < (3e-2 if seg.startswith("visual") else 1e-4), (seg, rel)      # a differing ReLU / pool decision; tight: test_frontend_grads_gpu.py
 
 
 def test_device_input_pipeline_bit_exact(ops):
