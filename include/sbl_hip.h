@@ -589,6 +589,46 @@ int sbl_pair_score_tail(const float* y_l, const float* y_r, long ldy, const floa
                         const int64_t* ys_r2l, long ldys, const int32_t* n_pos, float* logp, float* score_dir, float* score,
                         int32_t* best, int S, int G, int V, int D, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- lexicon-constrained beam search (single-direction decoder)
+ * Every layer of the single-direction decoder is causal, so ONE KV-cached beam search restricted to the prefixes of the word
+ * list ranks the lexicon by the model's own score: every hypothesis is a word, the n-best are distinct words, and the search
+ * runs Cmax + 1 steps (Cmax = the longest word, <= 15) instead of Ti.
+ *
+ * Trie of a lexicon (above): node 0 is the empty prefix and there is one node per distinct non-empty prefix of any word,
+ *   numbered breadth-first with siblings in ascending token id, so the children of a node are consecutive;
+ *   P <= 1 + sum of c_w nodes.  Three tables of P entries:
+ *   mask int64: bit v is set iff prefix(p) + [v] is a node; bit eos is set iff prefix(p) is a word (words hold neither sos nor
+ *     eos, so the eos bit is unambiguous);
+ *   first int32: the node of the lowest-token child;  child(p, v) = first[p] + popcount(mask[p] & ~bit(eos) & (bit(v) - 1)),
+ *     clamped to 0 .. P-1;
+ *   word int32: the lowest word index whose tokens are prefix(p), or -1 if there is none (duplicate rows of the lexicon share
+ *     a node; the lowest index answers for them).
+ * Constrained search: the search of sbl_beam_tail word for word - the same candidate arithmetic in fp32, tie order, history,
+ *   ended list and ancestry rows - except that every slot carries a node q (the root at the start), candidate (slot, v)
+ *   exists only where bit v of mask[q] is set, and the kept rank's node is child(q_parent, v) for v != eos and q_parent for
+ *   v == eos (0 at a rank where nothing is kept).  The candidate's value is score + log_softmax(logits)[v]
+ *   (+ log_prior[last_tok][v]); the log-softmax runs over all V classes and is NOT renormalised over the allowed ones, so an
+ *   ended hypothesis carries log P(w, eos | clip) of the teacher-forced model (plus priors).  The last-step rule of
+ *   sbl_beam_tail is untouched: the host sets maxlen = Cmax + 1, and with a real lexicon only eos candidates exist there.
+ *   Node values read from memory are clamped to 0 .. P-1, as anc is: a bad table never reads out of bounds.
+ *
+ * sbl_beam_tail with the constraint: the arguments of sbl_beam_tail, then trie_mask / trie_first (P) and node (S) int32,
+ * updated in place like last_tok.  With the one-node table P = 1, mask = all V bits, first = 0 it equals sbl_beam_tail bit
+ * for bit in every output.  One 8-byte mask load per slot, a bit test per lane, a popcount for the child. */
+int sbl_beam_tail_lex(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
+                      const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par, float* hist_score,
+                      int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count, int step, int maxlen, int eos,
+                      const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next, int N, int W, int V, int D,
+                      const int64_t* trie_mask, const int32_t* trie_first, int P, int32_t* node, sbl_stream_t stream);
+/* Exact lookup of R token rows in the trie, one thread per row.  ys (R, ldys >= Ly) int64; from each row, by the hypothesis
+ * rule of sbl_lexicon_shortlist: entries 1 .. Ly-1, cut before the first eos, without the entries equal to sos or ignore.
+ * The tokens are walked from the root.  node (R) int32 = the node reached, -1 if a token has no child (or is outside 0..63);
+ * word (R) int32 = trie_word[node], -1 if the walk failed or the end node is not a word (an empty row: -1).  It gives the
+ * n-best of the constrained search their word indices and greedy rows an exact-match lookup.  R == 0 is a successful no-op. */
+int sbl_lexicon_lookup(const int64_t* ys, long ldys, int Ly, int R, const int64_t* trie_mask, const int32_t* trie_first,
+                       const int32_t* trie_word, int P, int64_t sos, int64_t eos, int64_t ignore, int32_t* word, int32_t* node,
+                       sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
  * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.

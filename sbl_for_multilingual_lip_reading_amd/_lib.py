@@ -78,6 +78,8 @@ SIGNATURES = {
     "sbl_decode_tail": [P, L, P, P, L, P, L, I, P, P, I, F, P, I, I, I, P],
     "sbl_beam_attn_step": [P, L, P, P, L, P, P, L, I, P, L, P, L, I, I, I, I, I, F, P],
     "sbl_beam_tail": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P],
+    "sbl_beam_tail_lex": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P, P, I, P, P],
+    "sbl_lexicon_lookup": [P, L, I, I, P, P, P, I, L, L, L, P, P, P],
     "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "sbl_pair_beam_tail": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_lexicon_shortlist": [P, P, L, L, I, P, I, I, I, I, L, L, L, P, P, P, P, P, P, P],

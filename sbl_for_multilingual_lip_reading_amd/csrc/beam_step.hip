@@ -9,6 +9,8 @@
 //   * beam_tail_kernel: one workgroup per clip: the W projections to V <= 64 classes, log-softmax, + log-prior row of the
 //     slot's last token + the slot's score, the best W of the W * V candidates, the hypotheses that end, the new ancestry
 //     rows (double-buffered: the kernel reads the parents' rows), the (step, rank) history, and the next input rows.
+//     beam_tail_kernel<true> (sbl_beam_tail_lex) is the same body restricted to the prefixes of a word list: a slot's
+//     candidates are the tokens its trie node allows (include/sbl_hip.h).
 //   * beam_finish_kernel: one wavefront per clip: the nbest best ended hypotheses (stable), traced back through the history.
 // Ties (the reference leaves them to torch.topk and a stable sort): the lower parent slot first, then the lower token id;
 // in the final list the hypothesis that ended first (earlier step, then better rank).
@@ -21,14 +23,21 @@
 
 // ------------------------------------------------------------------ beam tail: LRW1000/transformer/decoder.py:186-229
 // grid N, 256 threads.  Slot n*W + r is beam position r of clip n.  Flags: 0 = nothing kept at this rank, 1 = live, 2 = ended.
+// LEX (sbl_beam_tail_lex): every slot carries a node of the lexicon's trie (include/sbl_hip.h); candidate (slot, v) exists only
+// where bit v of the node's mask is set - one 8-byte load per slot and a bit test per lane - and the kept rank's node is the
+// parent's child under v, a popcount below bit v.  Everything else is the one body, so the two searches share their arithmetic.
+template <bool LEX>
 __global__ __launch_bounds__(256) void beam_tail_kernel(
     const float* __restrict__ y, long ldy, const float* __restrict__ w, const float* __restrict__ log_prior, float* score,
     int32_t* last_tok, const int32_t* __restrict__ anc_old, int32_t* __restrict__ anc_new, long lda, int32_t* __restrict__ hist_tok,
     int32_t* __restrict__ hist_par, float* __restrict__ hist_score, int32_t* __restrict__ hist_flag, float* __restrict__ end_score,
     int32_t* __restrict__ end_ref, int32_t* end_count, int step, int maxlen, int eos, const float* __restrict__ emb,
-    const float* __restrict__ pe, float emb_scale, float* __restrict__ x_next, int W, int V) {
+    const float* __restrict__ pe, float emb_scale, float* __restrict__ x_next, int W, int V,
+    const int64_t* __restrict__ trie_mask, const int32_t* __restrict__ trie_first, int P, int32_t* node) {
     __shared__ float s_cand[DH_MAX_W * 64];
     __shared__ int s_tok[DH_MAX_W], s_par[DH_MAX_W];
+    __shared__ unsigned long long s_mask[DH_MAX_W];      // LEX: the slots' nodes (clamped to 0 .. P-1) and their masks
+    __shared__ int s_node[DH_MAX_W];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = blockIdx.x;
     const long slot0 = (long)n * W;
@@ -50,8 +59,19 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(
         int lt = last_tok[slot0 + r];
         lt = lt < 0 ? 0 : (lt >= V ? V - 1 : lt);
         const float lp = dh_log_softmax(lane < V ? s_cand[r * 64 + lane] : -INFINITY, lane < V);
+        bool allowed = lane < V;
+        if constexpr (LEX) {
+            int q = node[slot0 + r];
+            q = q < 0 ? 0 : (q >= P ? P - 1 : q);
+            const unsigned long long m = (unsigned long long)trie_mask[q];
+            allowed = allowed && ((m >> lane) & 1ull);
+            if (lane == 0) {
+                s_node[r] = q;
+                s_mask[r] = m;
+            }
+        }
         float c = -INFINITY;
-        if (lane < V && sc > -INFINITY) {
+        if (allowed && sc > -INFINITY) {
             float local = lp;
             if (log_prior) local += log_prior[(long)lt * V + lane];
             c = sc + local;
@@ -107,6 +127,18 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(
             hist_flag[hi] = kept ? (ended ? 2 : 1) : 0;
             score[slot0 + lane] = kept && !ended ? my_sc : -INFINITY;
             last_tok[slot0 + lane] = tok;
+            if constexpr (LEX) {      // the parent's node under tok; <eos> stays at the word's node; nothing kept: the root
+                int q = 0;
+                if (kept) {
+                    q = s_node[par];
+                    if (tok != eos) {
+                        const unsigned long long below = s_mask[par] & ~(1ull << eos) & ((1ull << tok) - 1ull);
+                        q = trie_first[q] + (int)__popcll(below);
+                        q = q < 0 ? 0 : (q >= P ? P - 1 : q);
+                    }
+                }
+                node[slot0 + lane] = q;
+            }
             s_tok[lane] = tok;
             s_par[lane] = par;
         }
@@ -123,30 +155,59 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(
         for (int r = 0; r < W; ++r) dh_next_row(x_next + (slot0 + r) * DH_D, emb, s_tok[r], pe, step + 1, emb_scale);
 }
 
+// the checks and the launch of sbl_beam_tail and sbl_beam_tail_lex (trie_mask != NULL)
+static int beam_tail_launch(const char* name, const float* y, long ldy, const float* w, const float* log_prior, float* score,
+                            int32_t* last_tok, const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok,
+                            int32_t* hist_par, float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref,
+                            int32_t* end_count, int step, int maxlen, int eos, const float* emb, const float* pe, int pe_rows,
+                            float emb_scale, float* x_next, int N, int W, int V, int D, const int64_t* trie_mask,
+                            const int32_t* trie_first, int P, int32_t* node, sbl_stream_t stream) {
+    SBL_REQUIRE(D == DH_D, "%s: D=%d (built for %d)", name, D, DH_D);
+    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "%s: V=%d (V <= %d)", name, V, DH_MAX_V);
+    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "%s: beam W=%d outside 1..%d", name, W, DH_MAX_W);
+    SBL_REQUIRE(W <= V, "%s: beam W=%d above V=%d", name, W, V);
+    SBL_REQUIRE(maxlen >= 1 && maxlen <= BEAM_MAX_LEN, "%s: maxlen=%d outside 1..%d", name, maxlen, BEAM_MAX_LEN);
+    SBL_REQUIRE(N > 0 && step >= 0 && step < maxlen, "%s: N=%d, step %d of %d", name, N, step, maxlen);
+    SBL_REQUIRE(eos >= 0 && eos < V, "%s: eos=%d outside the %d classes", name, eos, V);
+    SBL_REQUIRE(lda >= maxlen, "%s: ancestry rows of %ld entries for maxlen=%d", name, lda, maxlen);
+    SBL_REQUIRE(y && w && score && last_tok && anc_old && anc_new && anc_old != anc_new, "%s: null or aliased state", name);
+    SBL_REQUIRE(hist_tok && hist_par && hist_score && hist_flag && end_score && end_ref && end_count, "%s: null output", name);
+    SBL_REQUIRE(ldy >= D && ldy % 4 == 0, "%s: row stride %ld", name, ldy);
+    SBL_REQUIRE(!x_next || (emb && pe && step + 1 < pe_rows), "%s: next-row embedding needs emb, pe and pe row %d", name, step + 1);
+    SBL_REQUIRE(sbl_aligned16(y) && sbl_aligned16(w), "%s: unaligned", name);
+#define BEAM_TAIL_ARGS                                                                                                          \
+    y, ldy, w, log_prior, score, last_tok, anc_old, anc_new, lda, hist_tok, hist_par, hist_score, hist_flag, end_score, end_ref, \
+        end_count, step, maxlen, eos, emb, pe, emb_scale, x_next, W, V, trie_mask, trie_first, P, node
+    if (trie_mask)
+        hipLaunchKernelGGL(beam_tail_kernel<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
+    else
+        hipLaunchKernelGGL(beam_tail_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
+#undef BEAM_TAIL_ARGS
+    SBL_LAUNCH_CHECK(name);
+    return 0;
+}
+
 extern "C" int sbl_beam_tail(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
                              const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par,
                              float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count, int step,
                              int maxlen, int eos, const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next,
                              int N, int W, int V, int D, sbl_stream_t stream) {
-    SBL_REQUIRE(D == DH_D, "sbl_beam_tail: D=%d (built for %d)", D, DH_D);
-    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "sbl_beam_tail: V=%d (V <= %d)", V, DH_MAX_V);
-    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_beam_tail: beam W=%d outside 1..%d", W, DH_MAX_W);
-    SBL_REQUIRE(W <= V, "sbl_beam_tail: beam W=%d above V=%d", W, V);
-    SBL_REQUIRE(maxlen >= 1 && maxlen <= BEAM_MAX_LEN, "sbl_beam_tail: maxlen=%d outside 1..%d", maxlen, BEAM_MAX_LEN);
-    SBL_REQUIRE(N > 0 && step >= 0 && step < maxlen, "sbl_beam_tail: N=%d, step %d of %d", N, step, maxlen);
-    SBL_REQUIRE(eos >= 0 && eos < V, "sbl_beam_tail: eos=%d outside the %d classes", eos, V);
-    SBL_REQUIRE(lda >= maxlen, "sbl_beam_tail: ancestry rows of %ld entries for maxlen=%d", lda, maxlen);
-    SBL_REQUIRE(y && w && score && last_tok && anc_old && anc_new && anc_old != anc_new, "sbl_beam_tail: null or aliased state");
-    SBL_REQUIRE(hist_tok && hist_par && hist_score && hist_flag && end_score && end_ref && end_count, "sbl_beam_tail: null output");
-    SBL_REQUIRE(ldy >= D && ldy % 4 == 0, "sbl_beam_tail: row stride %ld", ldy);
-    SBL_REQUIRE(!x_next || (emb && pe && step + 1 < pe_rows), "sbl_beam_tail: next-row embedding needs emb, pe and pe row %d",
-                step + 1);
-    SBL_REQUIRE(sbl_aligned16(y) && sbl_aligned16(w), "sbl_beam_tail: unaligned");
-    hipLaunchKernelGGL(beam_tail_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, y, ldy, w, log_prior, score, last_tok, anc_old,
-                       anc_new, lda, hist_tok, hist_par, hist_score, hist_flag, end_score, end_ref, end_count, step, maxlen, eos, emb,
-                       pe, emb_scale, x_next, W, V);
-    SBL_LAUNCH_CHECK("sbl_beam_tail");
-    return 0;
+    return beam_tail_launch("sbl_beam_tail", y, ldy, w, log_prior, score, last_tok, anc_old, anc_new, lda, hist_tok, hist_par,
+                            hist_score, hist_flag, end_score, end_ref, end_count, step, maxlen, eos, emb, pe, pe_rows, emb_scale,
+                            x_next, N, W, V, D, nullptr, nullptr, 0, nullptr, stream);
+}
+
+extern "C" int sbl_beam_tail_lex(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
+                                 const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par,
+                                 float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count,
+                                 int step, int maxlen, int eos, const float* emb, const float* pe, int pe_rows, float emb_scale,
+                                 float* x_next, int N, int W, int V, int D, const int64_t* trie_mask, const int32_t* trie_first,
+                                 int P, int32_t* node, sbl_stream_t stream) {
+    SBL_REQUIRE(P >= 1, "sbl_beam_tail_lex: P=%d trie nodes", P);
+    SBL_REQUIRE(trie_mask && trie_first && node, "sbl_beam_tail_lex: null trie table or node buffer");
+    return beam_tail_launch("sbl_beam_tail_lex", y, ldy, w, log_prior, score, last_tok, anc_old, anc_new, lda, hist_tok, hist_par,
+                            hist_score, hist_flag, end_score, end_ref, end_count, step, maxlen, eos, emb, pe, pe_rows, emb_scale,
+                            x_next, N, W, V, D, trie_mask, trie_first, P, node, stream);
 }
 
 // ------------------------------------------------------------------ n-best and back-trace: LRW1000/transformer/decoder.py:240-245

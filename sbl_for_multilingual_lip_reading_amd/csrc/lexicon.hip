@@ -16,6 +16,9 @@
 // sbl_pair_score_tail - one workgroup per group of G slots.  For every step the 2 G rows go through the heads and the
 // log-softmax of decode_head.h (the code of sbl_pair_beam_tail) and the log-probability of the slot's own token is kept; one lane
 // per slot then adds them in ascending step order, the order of the beam search's totals.
+//
+// sbl_lexicon_lookup - one thread per hypothesis row: the exact walk through the lexicon's trie, the tables the constrained
+// beam tail (sbl_beam_tail_lex, beam_step.hip) reads.  It names the words of that search's n-best and is an exact-match lookup.
 #include "decode_head.h"
 
 #define LX_THREADS 1024
@@ -177,6 +180,51 @@ extern "C" int sbl_lexicon_shortlist(const int64_t* ys_l2r, const int64_t* ys_r2
                        reinterpret_cast<const uint4*>(lex), Wn, H, K, sos, eos, ignore, cand, cand_dist, cand_hyp, cand_ys_l2r,
                        cand_ys_r2l, n_pos);
     SBL_LAUNCH_CHECK("sbl_lexicon_shortlist");
+    return 0;
+}
+
+// ------------------------------------------------------------------ trie walk (the tables of sbl_beam_tail_lex)
+// grid ceil(R / 256), one thread per row: the row's tokens by the hypothesis rule of the shortlist, walked from the root.
+// Node values are clamped to 0 .. P-1 wherever they index a table, so a bad table reads nothing out of bounds.
+__global__ __launch_bounds__(256) void lexicon_lookup_kernel(const int64_t* __restrict__ ys, long ldys, int Ly, int R,
+                                                             const int64_t* __restrict__ trie_mask, const int32_t* __restrict__ trie_first,
+                                                             const int32_t* __restrict__ trie_word, int P, int64_t sos, int64_t eos,
+                                                             int64_t ignore, int32_t* __restrict__ word, int32_t* __restrict__ node) {
+    const long r = (long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int64_t* row = ys + r * ldys;
+    const unsigned long long not_eos = eos >= 0 && eos < 64 ? ~(1ull << eos) : ~0ull;
+    int q = 0;
+    bool open = true, found = true;
+    for (int i = 1; i < Ly; ++i) {
+        const int64_t t = row[i];
+        open = open && t != eos;
+        if (!open || t == sos || t == ignore || !found) continue;
+        const unsigned long long m = (unsigned long long)trie_mask[q] & not_eos;
+        if (t < 0 || t >= 64 || !((m >> t) & 1ull)) {
+            found = false;
+            continue;
+        }
+        q = trie_first[q] + (int)__popcll(m & ((1ull << t) - 1ull));
+        q = q < 0 ? 0 : (q >= P ? P - 1 : q);
+    }
+    word[r] = found ? trie_word[q] : -1;
+    node[r] = found ? q : -1;
+}
+
+extern "C" int sbl_lexicon_lookup(const int64_t* ys, long ldys, int Ly, int R, const int64_t* trie_mask, const int32_t* trie_first,
+                                  const int32_t* trie_word, int P, int64_t sos, int64_t eos, int64_t ignore, int32_t* word,
+                                  int32_t* node, sbl_stream_t stream) {
+    SBL_REQUIRE(R >= 0, "sbl_lexicon_lookup: R=%d", R);
+    SBL_REQUIRE(Ly >= 1 && ldys >= Ly, "sbl_lexicon_lookup: rows of %d entries with stride %ld", Ly, ldys);
+    SBL_REQUIRE(P >= 1, "sbl_lexicon_lookup: P=%d trie nodes", P);
+    SBL_REQUIRE(sos != eos, "sbl_lexicon_lookup: sos and eos are both %ld", (long)sos);
+    if (R == 0) return 0;
+    SBL_REQUIRE(ys && trie_mask && trie_first && trie_word, "sbl_lexicon_lookup: null input");
+    SBL_REQUIRE(word && node, "sbl_lexicon_lookup: null output");
+    hipLaunchKernelGGL(lexicon_lookup_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, ys, ldys, Ly, R, trie_mask,
+                       trie_first, trie_word, P, sos, eos, ignore, word, node);
+    SBL_LAUNCH_CHECK("sbl_lexicon_lookup");
     return 0;
 }
 

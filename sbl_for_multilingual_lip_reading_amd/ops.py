@@ -2062,9 +2062,11 @@ def beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_pr
 
 class BeamState(object):
     """The device buffers of one beam search over N clips with W slots each (include/sbl_hip.h, sbl_beam_tail): allocated
-    once per call; reset() restores the start (one hypothesis <sos> of score 0 per clip) with fill launches only."""
+    once per call; reset() restores the start (one hypothesis <sos> of score 0 per clip) with fill launches only.
+    lex=True adds `node` (N, W) int32, the slots' trie nodes of the lexicon-constrained search (sbl_beam_tail_lex); reset()
+    puts every slot at the root."""
 
-    def __init__(self, N, W, maxlen, sos_id, device):
+    def __init__(self, N, W, maxlen, sos_id, device, lex=False):
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)      # noqa: E731
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)    # noqa: E731
         self.N, self.W, self.maxlen, self.sos_id = N, W, maxlen, sos_id
@@ -2073,29 +2075,42 @@ class BeamState(object):
         self.hist_tok, self.hist_par, self.hist_flag = i32(N, maxlen, W), i32(N, maxlen, W), i32(N, maxlen, W)
         self.hist_score = f32(N, maxlen, W)
         self.end_score, self.end_ref, self.end_count = f32(N, W * maxlen), i32(N, W * maxlen), i32(N)
+        self.node = i32(N, W) if lex else None
         self.reset()
 
     def reset(self):
         self.score.fill_(float("-inf"))
         self.score[:, 0] = 0.0
         self.last_tok.fill_(self.sos_id)
+        if self.node is not None:
+            self.node.zero_()
 
     def history(self):
         return self.hist_tok, self.hist_par, self.hist_score, self.hist_flag
 
 
-def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None):
+def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None, trie=None):
     """Tail of beam step `step` in one launch (sbl_beam_tail) on the rows y (N*W, 512): the best W candidates of every clip
-    into the BeamState `st` (ancestry buffer step % 2 is read, the other one written), x_next = the next input rows."""
+    into the BeamState `st` (ancestry buffer step % 2 is read, the other one written), x_next = the next input rows.
+    trie: None, or the (mask, first, word) tables of Lexicon.trie() - then the launch is sbl_beam_tail_lex, a candidate exists
+    only where the slot's node st.node allows its token, and st.node is updated in place (st needs lex=True)."""
     S, D = y.shape
     V = w.size(0)
     assert S == st.N * st.W and y.stride(1) == 1 and w.is_contiguous()
     assert log_prior is None or (log_prior.dtype == torch.float32 and log_prior.shape == (V, V) and log_prior.is_contiguous())
     assert x_next is None or (x_next.is_contiguous() and x_next.shape == (S, D) and pe.is_contiguous() and emb.is_contiguous())
-    call("sbl_beam_tail", _p(y), y.stride(0), _p(w), _p(log_prior), _p(st.score), _p(st.last_tok), _p(st.anc[step % 2]),
-         _p(st.anc[1 - step % 2]), st.anc.stride(1), _p(st.hist_tok), _p(st.hist_par), _p(st.hist_score), _p(st.hist_flag),
-         _p(st.end_score), _p(st.end_ref), _p(st.end_count), int(step), st.maxlen, int(eos_id), _p(emb), _p(pe), pe.size(0),
-         emb_scale, _p(x_next), st.N, st.W, V, D, _s())
+    args = (_p(y), y.stride(0), _p(w), _p(log_prior), _p(st.score), _p(st.last_tok), _p(st.anc[step % 2]),
+            _p(st.anc[1 - step % 2]), st.anc.stride(1), _p(st.hist_tok), _p(st.hist_par), _p(st.hist_score), _p(st.hist_flag),
+            _p(st.end_score), _p(st.end_ref), _p(st.end_count), int(step), st.maxlen, int(eos_id), _p(emb), _p(pe), pe.size(0),
+            emb_scale, _p(x_next), st.N, st.W, V, D)
+    if trie is None:
+        call("sbl_beam_tail", *args, _s())
+        return
+    mask, first = trie[0], trie[1]
+    if st.node is None:
+        raise _lib.SblHipError("beam_tail: a trie needs a BeamState with a node buffer (lex=True)")
+    _check_trie(mask, first, None, y.device)
+    call("sbl_beam_tail_lex", *args, _p(mask), _p(first), mask.numel(), _p(st.node), _s())
 
 
 def beam_finish(st, nbest, eos_id):
@@ -2191,6 +2206,39 @@ def lexicon_shortlist(ys_l2r, ys_r2l, lex, K, sos_id, eos_id, ignore_id):
     call("sbl_lexicon_shortlist", _p(ys_l2r), _p(ys_r2l), ys_l2r.stride(0), ys_l2r.stride(1), Ly, _p(lex), Wn, N, H, K, int(sos_id),
          int(eos_id), int(ignore_id), *(_p(t) for t in out), _s())
     return out
+
+
+def _check_trie(mask, first, word, device):
+    """The tables of Lexicon.trie(): contiguous int64 / int32 / int32 vectors of one length P >= 1 on `device`."""
+    P = mask.numel()
+    ok = mask.dtype == torch.int64 and first.dtype == torch.int32 and mask.dim() == 1 and first.shape == mask.shape and P >= 1
+    ok = ok and mask.is_contiguous() and first.is_contiguous() and mask.device == device and first.device == device
+    if word is not None:
+        ok = ok and word.dtype == torch.int32 and word.shape == mask.shape and word.is_contiguous() and word.device == device
+    if not ok:
+        raise _lib.SblHipError("trie tables must be contiguous int64 mask / int32 first / int32 word vectors of one length on %s" % device)
+
+
+def lexicon_lookup(ys, trie, sos_id, eos_id, ignore_id):
+    """Exact trie walk of token rows in one launch (include/sbl_hip.h, sbl_lexicon_lookup).  ys: int64 (..., Ly) rows of
+    recognize / beam_search (the last dimension contiguous, the leading ones collapsible to one row stride, else copied);
+    trie: the (mask, first, word) tables of Lexicon.trie() on the same device.  Returns (word, node), int32 of ys.shape[:-1]:
+    the word index (-1: no such word) and the node reached (-1: a token without a child).  No sync."""
+    mask, first, word = trie
+    _need_cuda(ys, mask)
+    if ys.dtype != torch.int64 or ys.dim() < 1 or ys.size(-1) < 1:
+        raise ValueError("lexicon_lookup: ys must be int64 rows, got %s %s" % (ys.dtype, tuple(ys.shape)))
+    _check_trie(mask, first, word, ys.device)
+    lead, Ly = ys.shape[:-1], ys.size(-1)
+    rows = ys.reshape(-1, Ly)      # a view where the strides allow it
+    if rows.stride(1) != 1 or (rows.size(0) > 1 and rows.stride(0) < Ly):
+        rows = rows.contiguous()
+    R = rows.size(0)
+    out_w = torch.empty(R, dtype=torch.int32, device=ys.device)
+    out_n = torch.empty(R, dtype=torch.int32, device=ys.device)
+    call("sbl_lexicon_lookup", _p(rows), max(rows.stride(0), Ly), Ly, R, _p(mask), _p(first), _p(word), mask.numel(), int(sos_id),
+         int(eos_id), int(ignore_id), _p(out_w), _p(out_n), _s())
+    return out_w.view(lead), out_n.view(lead)
 
 
 def pair_score_tail(y_l, y_r, w_l, w_r, ys_l2r, ys_r2l, n_pos, G, logp, score_dir, score, best):

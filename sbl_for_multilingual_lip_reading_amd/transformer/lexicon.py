@@ -1,5 +1,6 @@
 """The word list of a closed-vocabulary benchmark (LRW: 500 words, LRW1000: 1000) as token rows, packed for
-sbl_lexicon_shortlist (include/sbl_hip.h): Decoder.recognize_words maps the decoder's hypotheses onto it."""
+sbl_lexicon_shortlist (include/sbl_hip.h): Decoder.recognize_words maps the decoder's hypotheses onto it.  Its trie
+(Lexicon.trie) constrains the beam search of the single-direction model (Seq2SeqDecoder.recognize_words, sbl_beam_tail_lex)."""
 import torch
 
 from ._env import config, ops
@@ -46,6 +47,8 @@ class Lexicon:
             packed[i, :len(w)] = torch.tensor(w, dtype=torch.uint8)
         packed[:, 15] = self.lengths.to(torch.uint8)
         self.packed = packed.to(self.device)
+        self.max_len = int(self.lengths.max())
+        self._trie = None
 
     def __len__(self):
         return self.tokens.size(0)
@@ -53,6 +56,44 @@ class Lexicon:
     def word(self, w):
         """The token ids of word w as a list."""
         return self.tokens[w, :int(self.lengths[w])].tolist()
+
+    def trie(self):
+        """The (mask int64, first int32, word int32) tables of the lexicon's trie on `device`, each of P entries, as
+        include/sbl_hip.h defines them (node 0 the empty prefix, breadth-first numbering with siblings in ascending token
+        id; bit v of mask[p]: prefix(p) + [v] is a node, bit eos: prefix(p) is a word; first[p] the lowest-token child, 0
+        at a leaf; word[p] the lowest word index that spells prefix(p) or -1).  Built once on the host and cached."""
+        if self._trie is None:
+            kids, owner = [{}], [-1]          # insertion-numbered first, then renumbered breadth-first
+            for i, (row, c) in enumerate(zip(self.tokens.tolist(), self.lengths.tolist())):
+                p = 0
+                for t in row[:c]:
+                    if t not in kids[p]:
+                        kids[p][t] = len(kids)
+                        kids.append({})
+                        owner.append(-1)
+                    p = kids[p][t]
+                if owner[p] < 0:
+                    owner[p] = i
+            order = [0]
+            for p in order:                   # grows while it is walked: a queue
+                order.extend(kids[p][t] for t in sorted(kids[p]))
+            new = {old: k for k, old in enumerate(order)}
+            mask, first, word = [], [], []
+            for old in order:
+                bits = sum(1 << t for t in kids[old]) | ((1 << self.eos_id) if owner[old] >= 0 else 0)
+                mask.append(bits - (1 << 64) if bits >> 63 else bits)      # the bit pattern as a signed 64-bit value
+                first.append(new[kids[old][min(kids[old])]] if kids[old] else 0)
+                word.append(owner[old])
+            self._trie = (torch.tensor(mask, dtype=torch.int64).to(self.device), torch.tensor(first, dtype=torch.int32).to(self.device),
+                          torch.tensor(word, dtype=torch.int32).to(self.device))
+        return self._trie
+
+    def lookup(self, ys):
+        """The word index of every token row of ys int64 (..., Ly) on `device` (rows as recognize / beam_search return them:
+        entry 0 is skipped, the row is cut before the first eos, sos / ignore entries are dropped), -1 where the tokens spell
+        no word: int32 of shape ys.shape[:-1].  Duplicate words answer with their lowest index.  One launch
+        (sbl_lexicon_lookup), no sync."""
+        return ops.lexicon_lookup(ys, self.trie(), self.sos_id, self.eos_id, self.ignore_id)[0]
 
     @classmethod
     def from_targets(cls, gold, names=None, device=None, **ids):

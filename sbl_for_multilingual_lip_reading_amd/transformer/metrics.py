@@ -81,7 +81,8 @@ class ErrorRateMeter:
 class WordAccuracyMeter:
     """Word accuracy of closed-vocabulary decodes (Transformer.validate_words) over an epoch: int64 device counters
     n (clips), n_correct (word == gold_word) and n_in_shortlist (gold_word is among the shortlisted candidates, the ceiling of
-    what rescoring can reach).  Integer torch ops on the device; update() does not synchronise and, after the first call of
+    what rescoring can reach; for Seq2SeqTransformer.validate_words, whose candidates are the distinct words of the constrained
+    beam search's n-best, it reads "gold word among the n-best").  Integer torch ops on the device; update() does not synchronise and, after the first call of
     a batch shape, allocates nothing (the work buffers of every batch shape seen are kept), so it can be captured with the
     decode.  All state is integer: it sums exactly across calls, replays and ranks."""
 

@@ -27,6 +27,11 @@ MAX_BEAM = 16             # slots per clip in the beam tail (csrc/decode_head.h)
 # scores (N, nbest) fp32, n_hyps (N) int32 (ranks beyond it: length 0, score -inf), history = the per-(clip, step, rank)
 # kept (token, parent rank, score, flag) tensors, each (N, maxlen, W)
 BeamResult = collections.namedtuple("BeamResult", ("yseq", "lengths", "scores", "n_hyps", "history"))
+# recognize_words' result: word (N,) int64, the lexicon word of the best hypothesis (-1: no hypothesis ended); cand (N, nbest)
+# int32, the distinct words of the n-best, best first (-1 beyond n_hyps); score (N, nbest) fp32 = log P(word, eos | clip) of
+# the teacher-forced model (+ priors), -inf beyond n_hyps; n_hyps (N) int32; yseq (N, nbest, Cmax + 3) int64 as in BeamResult.
+# `word` and `cand` are what metrics.WordAccuracyMeter.update reads.
+WordBeamResult = collections.namedtuple("WordBeamResult", ("word", "cand", "score", "n_hyps", "yseq"))
 
 
 class Seq2SeqDecoder(nn.Module):
@@ -242,12 +247,31 @@ class Seq2SeqDecoder(nn.Module):
         reference leaves to torch.topk: the lower parent slot first, then the lower token id.  A candidate of score -inf
         is never kept.  The step is KV-cached like the greedy decode (one new row per slot and step; the slots' caches are
         followed through an ancestry table, never copied), eval-only, with no host read: capturable as one hipGraph."""
+        return self.beam_search_lex(encoder_outputs, beam_size, nbest, decode_max_len, log_prior, None)
+
+    def beam_search_lex(self, encoder_outputs, beam_size, nbest=1, decode_max_len=0, log_prior=None, lexicon=None):
+        """beam_search with an optional word list.  lexicon (transformer.lexicon.Lexicon, on the encoder output's device,
+        with this decoder's vocab / sos / eos; decode_max_len must then be 0): the search is restricted to the prefixes of
+        the words (include/sbl_hip.h, sbl_beam_tail_lex).  Every hypothesis is a word, the n-best are distinct words, scores
+        are not renormalised over the allowed tokens, and the search runs maxlen = longest word + 1 steps -> BeamResult.
+        None: the unconstrained search of beam_search, launch for launch."""
         enc = encoder_outputs
         self._check_encoder(enc)
         N, T, D = enc.shape
         W, nbest = int(beam_size), int(nbest)
         maxlen = int(decode_max_len) or T
         V = self.n_tgt_vocab
+        if lexicon is not None:
+            if (lexicon.vocab, lexicon.sos_id, lexicon.eos_id) != (V, self.sos_id, self.eos_id):
+                raise _lib.SblHipError("Seq2SeqDecoder.beam_search_lex: the lexicon's vocab / sos / eos = %d / %d / %d, the decoder's %d / %d / %d"
+                                       % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, V, self.sos_id, self.eos_id))
+            if lexicon.packed.device != enc.device:
+                raise _lib.SblHipError("Seq2SeqDecoder.beam_search_lex: the lexicon is on %s, the encoder output on %s"
+                                       % (lexicon.packed.device, enc.device))
+            if int(decode_max_len) != 0:
+                raise _lib.SblHipError("Seq2SeqDecoder.beam_search_lex: decode_max_len = %d with a lexicon (the longest word sets "
+                                       "the number of steps; pass 0)" % decode_max_len)
+            maxlen = lexicon.max_len + 1
         if not 1 <= W <= min(MAX_BEAM, V):
             raise _lib.SblHipError("Seq2SeqDecoder.beam_search: beam_size = %d outside 1..min(%d, V = %d)" % (W, MAX_BEAM, V))
         if not 1 <= nbest <= MAX_BEAM:
@@ -262,11 +286,12 @@ class Seq2SeqDecoder(nn.Module):
             raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
         self._fuse()
         with torch.no_grad():
-            return self._beam_cached(enc, W, nbest, maxlen, None if log_prior is None else log_prior.contiguous())
+            return self._beam_cached(enc, W, nbest, maxlen, None if log_prior is None else log_prior.contiguous(),
+                                     None if lexicon is None else lexicon.trie())
 
-    def _beam_cached(self, enc, W, nbest, maxlen, log_prior):
+    def _beam_cached(self, enc, W, nbest, maxlen, log_prior, trie=None):
         S = enc.size(0) * W       # the W slots of a clip read the clip's cross-attention K / V
-        st = ops.BeamState(enc.size(0), W, maxlen, self.sos_id, enc.device)
+        st = ops.BeamState(enc.size(0), W, maxlen, self.sos_id, enc.device, lex=trie is not None)
         tok0 = torch.full((S, 1), self.sos_id, dtype=torch.long, device=enc.device)
 
         def attn(i, q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append):
@@ -274,8 +299,17 @@ class Seq2SeqDecoder(nn.Module):
             ops.beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, st.anc[i % 2] if append else None, out, W, H, n_prev, append)
 
         self._cached_steps(enc, S, maxlen, tok0, attn,
-                           lambda y, w, i, *head: ops.beam_tail(y, w, log_prior, st, i, self.eos_id, *head))
+                           lambda y, w, i, *head: ops.beam_tail(y, w, log_prior, st, i, self.eos_id, *head, trie=trie))
         return BeamResult(*ops.beam_finish(st, nbest, self.eos_id), st.history())
+
+    def recognize_words(self, encoder_outputs, lexicon, beam_size=8, nbest=1, log_prior=None):
+        """Closed-vocabulary decode in one pass: the beam search restricted to `lexicon` (beam_search_lex),
+        then one lookup launch that names the n-best -> WordBeamResult.  The score of a word is the model's own
+        log P(word, eos | clip) (+ log_prior's bigram terms); with a beam no narrower than the trie it is the exact ranking
+        of the lexicon.  No host read: capturable as one hipGraph once lexicon.trie() has been built."""
+        res = self.beam_search_lex(encoder_outputs, beam_size, nbest, 0, log_prior, lexicon)
+        cand = lexicon.lookup(res.yseq)
+        return WordBeamResult(cand[:, 0].long(), cand, res.scores, res.n_hyps, res.yseq)
 
 
 class Seq2SeqTransformer(nn.Module):
@@ -343,5 +377,21 @@ class Seq2SeqTransformer(nn.Module):
         meter.update_single(ys, padded_target, valid_rows=valid_rows)
         return ys
 
+    def recognize_words(self, input, lexicon, beam_size=8, nbest=1, log_prior=None):
+        """Closed-vocabulary decode of (N, T, H, W) crops (or ops.RawClips): Seq2SeqDecoder.recognize_words on the encoder
+        output -> WordBeamResult, the lexicon word of every clip with the distinct words of its n-best and their scores."""
+        enc, _ = self._encode(input)
+        return self.decoder.recognize_words(enc, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
 
-__all__ = ["Seq2SeqDecoder", "Seq2SeqTransformer", "BeamResult", "MAX_TGT_LEN"]
+    def validate_words(self, padded_input, gold_word, lexicon, meter, valid_rows=None, beam_size=8, nbest=1, log_prior=None):
+        """One validation batch of a closed-vocabulary benchmark: recognize_words, then `meter` (metrics.WordAccuracyMeter)
+        counts the clips whose word is gold_word (N,) int64 - word indices into `lexicon`, as Lexicon.from_targets returns
+        them - and those whose n-best holds it (the meter's n_in_shortlist).  No host read: in eval() under torch.no_grad()
+        the call is capturable as one hipGraph, like validate; `valid_rows` (device int32[1]) masks the tail of a short last
+        batch.  Returns the WordBeamResult."""
+        res = self.recognize_words(padded_input, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
+        meter.update(res, gold_word, valid_rows=valid_rows)
+        return res
+
+
+__all__ = ["Seq2SeqDecoder", "Seq2SeqTransformer", "BeamResult", "WordBeamResult", "MAX_TGT_LEN"]

@@ -4,13 +4,18 @@ T = 29 encoder frames = decode steps, 6 decoder layers, 48 classes, on a fixed e
 under one hipGraph, and the batched beam search (Seq2SeqDecoder.beam_search) with W = 1, 5 and 8, eager and under one
 hipGraph.  Prints one JSON line: milliseconds per call (median of --steps runs after --warmup runs, device events on one
 stream), milliseconds per decode step, the ratio to the greedy decode, and whether a W = 8 step is no slower than eight
-W = 1 steps.
+W = 1 steps.  With --lexicon-words N (default 1000 seeded random words of 2..13 tokens) it then times the lexicon-constrained
+search (Seq2SeqDecoder.beam_search_lex with a Lexicon: longest word + 1 steps) next to the unconstrained one at the same W,
+both eager and under one hipGraph, in --rounds alternating rounds: per W the medians over the rounds' medians with their
+spread (max - min), per search and per decode step ("lex_*" keys).
 
     python tools/bench_beam.py --steps 20 --warmup 5
 """
 import argparse
 import json
 import os
+import random
+import statistics
 import sys
 
 import torch
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--precision", default="bf16x6")
+    ap.add_argument("--lexicon-words", type=int, default=1000, help="0: skip the lexicon-constrained runs")
+    ap.add_argument("--rounds", type=int, default=5)
     args = ap.parse_args()
 
     from sbl_for_multilingual_lip_reading_amd import ops
@@ -73,6 +80,32 @@ def main():
             del graph, keep
     if 1 in args.beams and 8 in args.beams:
         out["beam8_step_not_slower_than_8_beam1_steps"] = bool(out["beam8_graph_ms"] <= 8 * out["beam1_graph_ms"])
+    if args.lexicon_words:
+        from sbl_for_multilingual_lip_reading_amd.transformer.lexicon import Lexicon
+        rnd = random.Random(0)
+        lex = Lexicon([[rnd.randrange(2, V) for _ in range(rnd.randint(2, 13))] for _ in range(args.lexicon_words)],
+                      device=dev, vocab=V)
+        lex.trie()          # built on the host once, before any capture
+        steps_lex = lex.max_len + 1
+        out.update(lex_words=args.lexicon_words, lex_steps=steps_lex, lex_trie_nodes=int(lex.trie()[0].numel()), lex_rounds=args.rounds)
+        med, spread = statistics.median, lambda v: max(v) - min(v)      # noqa: E731
+        with torch.no_grad():
+            for W in args.beams:
+                runs = {"beam": (lambda: dec.beam_search(enc, W, args.nbest, 0, prior), T),
+                        "lex": (lambda: dec.beam_search_lex(enc, W, args.nbest, 0, prior, lex), steps_lex)}
+                graphs = {k: graphed(fn) for k, (fn, _) in runs.items()}
+                ms = {(k, mode): [] for k in runs for mode in ("eager", "graph")}
+                for _ in range(args.rounds):          # alternating: beam, lex, beam, lex, ...
+                    for k, (fn, _) in runs.items():
+                        ms[k, "eager"].append(timed(fn, args.steps, args.warmup)[0])
+                        ms[k, "graph"].append(timed(graphs[k][0].replay, args.steps, args.warmup)[0])
+                for (k, mode), v in ms.items():
+                    n = runs[k][1]
+                    tag = "lex_%s%d_%s" % (k, W, mode)
+                    out[tag + "_ms"], out[tag + "_ms_spread"] = round(med(v), 4), round(spread(v), 4)
+                    out[tag + "_ms_per_step"], out[tag + "_ms_per_step_spread"] = round(med(v) / n, 5), round(spread(v) / n, 5)
+                out["lex_lex%d_graph_over_beam" % W] = round(med(ms["lex", "graph"]) / med(ms["beam", "graph"]), 4)
+                del graphs
     print(json.dumps(out))
 
 
