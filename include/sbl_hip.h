@@ -629,6 +629,44 @@ int sbl_lexicon_lookup(const int64_t* ys, long ldys, int Ly, int R, const int64_
                        const int32_t* trie_word, int P, int64_t sos, int64_t eos, int64_t ignore, int32_t* word, int32_t* node,
                        sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- lexicon-constrained pair beam search (SBL decoder)
+ * The same constraint for the pair search of sbl_pair_beam_tail, through ONE trie over PAIRS of tokens: a hypothesis pair is
+ * one lexicon word w, its l2r row spelling w and its r2l row reversed(w).  The n-best are distinct words, a word's total is
+ * the sum sbl_pair_score_tail forms over its c_w + 1 trained positions, and the search runs Cmax + 1 steps.
+ *
+ * Pair trie of a lexicon: a state is what both directions have emitted after t steps of one word of c tokens,
+ *   (w[:t], w[c-t:]) - the prefix, and the suffix that the r2l row has spelled backwards.  Node 0 is the empty state; one node
+ *   per distinct state of any word at any depth 0..c_w (words of different length share equal states); one TERMINAL node per
+ *   distinct word, the child of its depth-c_w state under the key (eos, eos).  The key of an edge is a * 64 + b < 4096, a the
+ *   l2r and b the r2l token of the step: (w[t], w[c-1-t]) for t < c, (eos, eos) at t = c.  Nodes are numbered breadth-first
+ *   with the children of a node in ascending key, so the child reached through CSR entry e is node e + 1.
+ *   P <= 2 + sum of (c_w + 1) nodes, E = P - 1 edges.  Three int32 tables:
+ *   begin (P + 1): CSR offsets into key; a terminal node has an empty range;
+ *   key (E): the edge keys, ascending inside a node;
+ *   word (P): at a terminal node the lowest word index that spells it (duplicate rows share a node), -1 elsewhere.
+ *
+ * Tail of step `step`: the arguments, launch shape, logits and per-row log-softmax of sbl_pair_beam_tail (one body), then the
+ * tables, node_old / node_new (S) int32 - double-buffered like the prefixes, a rank reads its parent's node; the search starts
+ * with every node 0 - and hist_node (N, maxlen, W).  Candidates of a live slot s at node q = node_old[s]:
+ *   word[q] >= 0 (the pair has ended): exactly one, tokens (eos, eos), total score[s] and score_dir[s] UNCHANGED (no add: the
+ *     values are carried bit for bit), node q;
+ *   otherwise one per entry e in begin[q] .. begin[q+1], a = key[e] >> 6, b = key[e] & 63: total = score[s] + (lpL[s][a] +
+ *     lpR[s][b]) added in fp32 in that order, score_dir[s][0] + lpL[s][a] and score_dir[s][1] + lpR[s][b], node e + 1.
+ *   The log-softmax runs over all V classes and is NOT renormalised over the allowed tokens.
+ * The clip's best W candidates are kept in descending total; exact ties go to the lower slot, then the lower entry e (the
+ * lower key) - simpler than the rank order of sbl_pair_beam_tail, whose candidates are a product of two sorted lists.  A
+ * candidate of total -inf or NaN is never kept; a rank without a candidate gets the scores -inf, eos tokens, its own rank as
+ * parent and node 0.  Any candidate count is handled (the root may have min(Wn, V*V) children).
+ * A bad table never reads out of bounds: nodes read from memory are clamped to 0 .. P-1, begin values to 0 .. E (an empty or
+ * inverted range: no candidates), a key with a token >= V is a -inf candidate, and the node written is min(e + 1, P - 1).
+ * Written: score, score_dir, ys_new_* and the four histories as sbl_pair_beam_tail writes them, hist_node, node_new. */
+int sbl_pair_beam_tail_lex(const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r, float* score,
+                           float* score_dir, const int64_t* ys_old_l, const int64_t* ys_old_r, int64_t* ys_new_l,
+                           int64_t* ys_new_r, long ldys, int32_t* hist_tok_l, int32_t* hist_tok_r, int32_t* hist_par,
+                           float* hist_score, int step, int maxlen, int eos, int N, int W, int V, int D, const int32_t* trie_begin,
+                           const int32_t* trie_key, const int32_t* trie_word, int P, int E, const int32_t* node_old,
+                           int32_t* node_new, int32_t* hist_node, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- stage-1 classification heads (CLS pre-training)
  * CLS/transformer/transformer.py:31-35 as oracle.sbl_oracle.cls_forward restates it (the shipped forward's mean(dim=2)
  * raises): enc (N,T,D) row-major, D = 512; fc_1500 = W1 (C1,D) + b1, fc_2 = W2 (C2,D) + b2, C2 <= 16.

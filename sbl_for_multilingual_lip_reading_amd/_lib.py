@@ -82,6 +82,7 @@ SIGNATURES = {
     "sbl_lexicon_lookup": [P, L, I, I, P, P, P, I, L, L, L, P, P, P],
     "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
     "sbl_pair_beam_tail": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P],
+    "sbl_pair_beam_tail_lex": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P, P, P, I, I, P, P, P, P],
     "sbl_lexicon_shortlist": [P, P, L, L, I, P, I, I, I, I, L, L, L, P, P, P, P, P, P, P],
     "sbl_pair_score_tail": [P, P, L, P, P, P, P, L, P, P, P, P, P, I, I, I, I, P],
     "sbl_smoothed_ce_fwd": [P, P, P, I, I, F, I, P],

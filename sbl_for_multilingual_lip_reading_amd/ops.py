@@ -2130,16 +2130,24 @@ class PairBeamState(object):
     (include/sbl_hip.h, sbl_pair_beam_tail): total and per-direction scores, the two double-buffered prefix tables
     ys[d][k] (N*W, maxlen+1) int64 - step i reads k = i % 2 and writes the other - and the (N, maxlen, W) history.
     Allocated once per call; reset() restores the start (every prefix <sos>, slot 0 of every clip at score 0, the other
-    slots dead) with fill launches only."""
+    slots dead) with fill launches only.
+    lex=True adds the node buffers of the lexicon-constrained search (sbl_pair_beam_tail_lex): `node` (2, N, W) int32,
+    double-buffered like the prefixes, and `hist_node` (N, maxlen, W); reset() puts every slot at the root.  row_len (>=
+    maxlen + 1) widens the prefix rows: that search runs maxlen = Cmax + 1 steps on the 17-entry rows the decoder stage reads,
+    and the entries behind maxlen keep reset()'s <eos>."""
 
-    def __init__(self, N, W, maxlen, sos_id, eos_id, device):
+    def __init__(self, N, W, maxlen, sos_id, eos_id, device, lex=False, row_len=None):
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=device)      # noqa: E731
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)    # noqa: E731
         self.N, self.W, self.maxlen, self.sos_id, self.eos_id = N, W, maxlen, sos_id, eos_id
+        row_len = maxlen + 1 if row_len is None else int(row_len)
+        if row_len < maxlen + 1:
+            raise ValueError("PairBeamState: prefix rows of %d entries for maxlen = %d (+1)" % (row_len, maxlen))
         self.score, self.score_dir = f32(N, W), f32(N, W, 2)
-        self.ys = torch.empty(2, 2, N * W, maxlen + 1, dtype=torch.int64, device=device)      # [direction][buffer]
+        self.ys = torch.empty(2, 2, N * W, row_len, dtype=torch.int64, device=device)      # [direction][buffer]
         self.hist_tok_l, self.hist_tok_r, self.hist_par = i32(N, maxlen, W), i32(N, maxlen, W), i32(N, maxlen, W)
         self.hist_score = f32(N, maxlen, W)
+        self.node, self.hist_node = (i32(2, N, W), i32(N, maxlen, W)) if lex else (None, None)
         self.reset()
 
     def reset(self):
@@ -2149,6 +2157,12 @@ class PairBeamState(object):
         self.score_dir[:, 0] = 0.0
         self.ys.fill_(self.eos_id)
         self.ys[:, :, :, 0] = self.sos_id
+        if self.node is not None:
+            self.node.zero_()
+
+    def nodes(self, step):
+        """The (N, W) trie nodes that step `step` reads (lex=True): what step - 1 wrote."""
+        return self.node[step % 2]
 
     def prefixes(self, step):
         """(l2r, r2l) prefix tables that step `step` reads: what step - 1 wrote."""
@@ -2170,6 +2184,29 @@ def pair_beam_tail(y_l, y_r, w_l, w_r, st, step):
     call("sbl_pair_beam_tail", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
          _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
          _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _s())
+
+
+def pair_beam_tail_lex(y_l, y_r, w_l, w_r, st, step, pair_trie):
+    """pair_beam_tail restricted to a word list, in one launch (include/sbl_hip.h, sbl_pair_beam_tail_lex).  pair_trie: the
+    (begin (P + 1), key (P - 1), word (P)) int32 tables of Lexicon.pair_trie() on the same device; st: a PairBeamState with
+    lex=True, whose node buffer step % 2 is read and the other one written, like the prefixes."""
+    S, D = y_l.shape
+    V = w_l.size(0)
+    assert S == st.N * st.W and y_r.shape == y_l.shape and w_r.shape == w_l.shape
+    assert y_l.stride(1) == 1 and y_r.stride(1) == 1 and y_l.stride(0) == y_r.stride(0) and w_l.is_contiguous() and w_r.is_contiguous()
+    begin, key, word = pair_trie
+    _need_cuda(y_l, y_r, w_l, w_r, st.score, begin, key, word)
+    if st.node is None:
+        raise _lib.SblHipError("pair_beam_tail_lex: a pair trie needs a PairBeamState with node buffers (lex=True)")
+    P, E = word.numel(), key.numel()
+    ok = all(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == y_l.device for t in pair_trie)
+    if not ok or P < 1 or begin.numel() != P + 1:
+        raise _lib.SblHipError("pair trie tables must be contiguous int32 vectors begin (P + 1) / key (E) / word (P) on %s" % y_l.device)
+    old, new = st.ys[:, step % 2], st.ys[:, 1 - step % 2]
+    call("sbl_pair_beam_tail_lex", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
+         _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
+         _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _p(begin), _p(key), _p(word), P, E,
+         _p(st.node[step % 2]), _p(st.node[1 - step % 2]), _p(st.hist_node), _s())
 
 
 # --------------------------------------------------------------------------- #

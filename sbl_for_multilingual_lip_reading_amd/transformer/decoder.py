@@ -17,6 +17,7 @@ MAX_PAIR_BEAM = 16          # slots per clip of Decoder.beam_search (csrc/pair_b
 PairBeamResult = collections.namedtuple("PairBeamResult", ("ys_l2r", "ys_r2l", "scores", "scores_dir", "history"))
 PairScore = collections.namedtuple("PairScore", ("score", "score_dir", "logp", "best"))
 WordResult = collections.namedtuple("WordResult", ("word", "cand", "cand_dist", "cand_hyp", "score", "score_dir"))
+PairWordBeamResult = collections.namedtuple("PairWordBeamResult", ("word", "cand", "score", "score_dir", "ys_l2r", "ys_r2l", "history"))
 SCORE_PAIRS_MAX_ROWS = 1 << 16      # rows of one score_pairs stage (136 per slot): 128 MiB of activations per 512 columns
 
 
@@ -419,6 +420,46 @@ class Decoder(nn.Module):
         ps = self.score_pairs(enc, sl.cand_ys_l2r, sl.cand_ys_r2l, sl.n_pos, group=K)
         word = sl.cand.gather(1, ps.best.long().unsqueeze(1)).squeeze(1).long()
         return WordResult(word, sl.cand, sl.cand_dist, sl.cand_hyp, ps.score.view(N, K), ps.score_dir.view(N, K, 2))
+
+    def beam_search_lex(self, encoder_outputs, lexicon, beam_size, nbest=1):
+        """Closed-vocabulary decode in ONE pass: beam_search restricted to the words of `lexicon` (transformer.lexicon.Lexicon)
+        through its pair trie (Lexicon.pair_trie; include/sbl_hip.h, sbl_pair_beam_tail_lex).  Every hypothesis pair is one
+        word - the l2r row spells w, the r2l row reversed(w), which is what the model was trained on - so the n-best are
+        distinct words.  The stage, the K/V hoist and the two streams are beam_search's; the tail keeps, of the trie edges
+        of every live slot, the clip's best W by score[s] + (lpL[a] + lpR[b]) (ties: lower slot, then lower key), and a pair
+        that has emitted (eos, eos) is carried with its score unchanged.  The log-softmax is not renormalised and there is no
+        length normalisation or prior, so a word's total is score_pairs(..., n_pos = c_w + 1) on its rows, the quantity
+        recognize_words ranks by.  steps = lexicon.max_len + 1 iterations (host-known): after the last one every live slot
+        sits on a terminal node.  No host read: capturable as one hipGraph.
+        Returns PairWordBeamResult(word (N,) int64, cand (N, nbest) int32 = the n-best words, best first, -1 at dead ranks,
+        score (N, nbest), score_dir (N, nbest, 2), ys_l2r, ys_r2l (N, nbest, 17) int64 = sos, w, eos fill and sos,
+        reversed(w), eos fill, history = (l2r token, r2l token, parent rank, total score, node), each (N, steps, W))."""
+        enc = encoder_outputs
+        W, nbest = int(beam_size), int(nbest)
+        if not 1 <= W <= MAX_PAIR_BEAM:
+            raise _lib.SblHipError("Decoder.beam_search_lex: beam_size = %d outside 1..%d" % (W, MAX_PAIR_BEAM))
+        if not 1 <= nbest <= W:
+            raise _lib.SblHipError("Decoder.beam_search_lex: nbest = %d outside 1..beam_size = %d" % (nbest, W))
+        if not enc.is_cuda:
+            raise _lib.SblHipError("Decoder.beam_search_lex needs the encoder output on the GPU (got a %s tensor); there is no "
+                                   "CPU path" % enc.device)
+        if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
+            raise _lib.SblHipError("Decoder.beam_search_lex: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
+                                   % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+        N, L = enc.size(0), config.MAX_DECODE_LEN + 1
+        S, steps = N * W, lexicon.max_len + 1
+        trie = lexicon.pair_trie()
+        with torch.no_grad():
+            layers, main, side, kv = self._begin(enc)
+            st = ops.PairBeamState(N, W, steps, self.sos_id, self.eos_id, enc.device, lex=True, row_len=L)
+            heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
+            for i in range(steps):
+                last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W)
+                ops.pair_beam_tail_lex(last[0], last[1], heads[0], heads[1], st, i, trie)
+            cand = trie[2][st.nodes(steps)[:, :nbest].long()]      # a dead rank sits on node 0, whose word is -1
+        ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(steps))
+        return PairWordBeamResult(cand[:, 0].long(), cand, st.score[:, :nbest], st.score_dir[:, :nbest], ys_l, ys_r,
+                                  st.history() + (st.hist_node,))
 
 
 class DecoderLayer(nn.Module):

@@ -1,6 +1,8 @@
 """The word list of a closed-vocabulary benchmark (LRW: 500 words, LRW1000: 1000) as token rows, packed for
 sbl_lexicon_shortlist (include/sbl_hip.h): Decoder.recognize_words maps the decoder's hypotheses onto it.  Its trie
-(Lexicon.trie) constrains the beam search of the single-direction model (Seq2SeqDecoder.recognize_words, sbl_beam_tail_lex)."""
+(Lexicon.trie) constrains the beam search of the single-direction model (Seq2SeqDecoder.recognize_words, sbl_beam_tail_lex),
+its trie over pairs of tokens (Lexicon.pair_trie) the pair beam search of the SBL decoder (Decoder.beam_search_lex,
+sbl_pair_beam_tail_lex)."""
 import torch
 
 from ._env import config, ops
@@ -49,6 +51,7 @@ class Lexicon:
         self.packed = packed.to(self.device)
         self.max_len = int(self.lengths.max())
         self._trie = None
+        self._pair_trie = None
 
     def __len__(self):
         return self.tokens.size(0)
@@ -87,6 +90,37 @@ class Lexicon:
             self._trie = (torch.tensor(mask, dtype=torch.int64).to(self.device), torch.tensor(first, dtype=torch.int32).to(self.device),
                           torch.tensor(word, dtype=torch.int32).to(self.device))
         return self._trie
+
+    def pair_trie(self):
+        """The (begin int32 (P + 1), key int32 (P - 1), word int32 (P)) tables of the lexicon's PAIR trie on `device`, as
+        include/sbl_hip.h defines them for sbl_pair_beam_tail_lex (Decoder.beam_search_lex).  A node is what both directions
+        have emitted after t steps of one word of c tokens, (w[:t], w[c-t:]); node 0 the empty state; one terminal node per
+        distinct word behind the key (eos, eos) of its depth-c state.  Edge key = a * 64 + b with (a, b) = (w[t], w[c-1-t]);
+        breadth-first numbering with the children of a node in ascending key, so the child behind CSR entry e is node e + 1.
+        word[p]: at a terminal node the lowest word index that spells it, -1 elsewhere.  Built once on the host and cached."""
+        if self._pair_trie is None:
+            kids, owner = [{}], [-1]          # insertion-numbered first, then renumbered breadth-first
+            for i, (row, c) in enumerate(zip(self.tokens.tolist(), self.lengths.tolist())):
+                w = row[:c]
+                p = 0
+                for k in [w[t] * 64 + w[c - 1 - t] for t in range(c)] + [self.eos_id * 64 + self.eos_id]:
+                    if k not in kids[p]:
+                        kids[p][k] = len(kids)
+                        kids.append({})
+                        owner.append(-1)
+                    p = kids[p][k]
+                if owner[p] < 0:
+                    owner[p] = i
+            order = [0]
+            for p in order:                   # grows while it is walked: a queue
+                order.extend(kids[p][k] for k in sorted(kids[p]))
+            begin, key, word = [0], [], []
+            for old in order:
+                key.extend(sorted(kids[old]))
+                begin.append(len(key))
+                word.append(owner[old])
+            self._pair_trie = tuple(torch.tensor(t, dtype=torch.int32).to(self.device) for t in (begin, key, word))
+        return self._pair_trie
 
     def lookup(self, ys):
         """The word index of every token row of ys int64 (..., Ly) on `device` (rows as recognize / beam_search return them:

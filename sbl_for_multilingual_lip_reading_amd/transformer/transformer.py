@@ -74,3 +74,18 @@ class Transformer(nn.Module):
         res = self.recognize_words(padded_input, lexicon, beam_size=beam_size, nbest=nbest, shortlist=shortlist)
         meter.update(res, gold_word, valid_rows=valid_rows)
         return res
+
+    def recognize_words_lex(self, input, lexicon, beam_size, nbest=1):
+        """Closed-vocabulary decode of (N, T, H, W) crops (or ops.RawClips) in one pass: Decoder.beam_search_lex on the encoder
+        output -> PairWordBeamResult, the nbest best lexicon words of every clip by the model's own pair score."""
+        enc, _ = self._encode(input)
+        return self.decoder.beam_search_lex(enc, lexicon, beam_size, nbest)
+
+    def validate_words_lex(self, padded_input, gold_word, lexicon, meter, valid_rows=None, beam_size=8, nbest=1):
+        """validate_words through the lexicon-constrained pair beam search (recognize_words_lex): `meter`
+        (metrics.WordAccuracyMeter, unchanged) counts the clips whose word is gold_word, and as n_in_shortlist those whose
+        n-best words hold it.  No host sync: capturable as one hipGraph in eval() under torch.no_grad(); `valid_rows` (device
+        int32[1]) masks the tail of a short last batch.  Returns the PairWordBeamResult."""
+        res = self.recognize_words_lex(padded_input, lexicon, beam_size, nbest)
+        meter.update(res, gold_word, valid_rows=valid_rows)
+        return res
