@@ -343,6 +343,21 @@ int sbl_attention_seg_bwd(const float* dout, long lddo, const float* q, long ldq
 int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
                                   long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group, float scale,
                                   float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream);
+/* Attention with a key count per entry, inference only (ragged clips: the padded frames behind a clip's end are no keys).
+ * Lk_fixed >= 1: sbl_attention_seg_grouped_fwd, where kv_len is a DEVICE array of B / kv_group counts and sequence b sees key j
+ * iff j < min(max(kv_len[b / kv_group], 0), Lk_fixed).  Lk_fixed == 0: self-attention of ONE segment (nseg == 1, kv_group == 1,
+ * the encoder): kv_len has B counts and every query row of sequence b sees the keys j < kv_len[b] of its own rows, clamped the
+ * same way; there is no causal mode.  A sequence without a visible key gets o = 0.  Key / value rows at or behind the count are
+ * never loaded, so whatever they hold (NaN included) cannot reach o.  No probabilities are written and there is no backward.  The
+ * dropout mask index of probability (i, j) is the one of the call without counts (the layout of Lk_fixed, or L, keys).  The
+ * kernels are chosen from the host-known shapes as sbl_attention_seg_grouped_fwd chooses them (self-attention: by seg_L[0]);
+ * kv_len is never read on the host, so a captured graph follows counts that are overwritten in place.  On the one-wavefront
+ * kernels (L <= 16 and Lk <= 32; one segment of 17..32 rows) sequence b's output is bit-identical to that of
+ * sbl_attention_seg_grouped_fwd on K/V cut to its count. */
+int sbl_attention_seg_len_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                              long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
+                              const int32_t* kv_len, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
+                              sbl_stream_t stream);
 /* Stage head of the SBL decoder for BOTH directions in one launch: out_d = dropout(emb[tok_d] + pe[:L]) for every segment
  * of the stage (SBL/transformer/decoder.py:116-120); mask = f(seed, offset_d, element index inside the stage's rows), the
  * indexing of sbl_dropout, which regenerates it in backward.  drop_p == 0: plain embedding + PE. */

@@ -48,6 +48,7 @@ SIGNATURES = {
     "sbl_attention_seg_fwd": [P, L, P, L, P, L, P, L, P, I, P, I, I, P, I, I, F, F, P, U64, P],
     "sbl_attention_seg2_fwd": [P, P, L, P, P, L, P, P, L, P, P, L, P, P, I, I, I, P, I, I, F, F, P, U64, U64, P],
     "sbl_attention_seg_grouped_fwd": [P, L, P, L, P, L, P, L, I, I, P, I, I, I, F, F, P, U64, P],
+    "sbl_attention_seg_len_fwd": [P, L, P, L, P, L, P, L, I, I, P, I, I, I, P, F, F, P, U64, P],
     "sbl_gemm2_f32": [I, I, I, P, P, L, P, P, L, P, P, L, P, P, I, P, L, P],
     "sbl_gemm2_rows_f32": [I, I, I, P, P, L, P, P, L, P, P, L, P, P, I, P, L, P],
     "sbl_add_layernorm2_fwd": [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I, I, F, F, P, U64, U64, P],

@@ -44,13 +44,18 @@ __device__ __forceinline__ bool at_masked(int mask_kind, const uint8_t* mask, in
 
 // kv_group > 1 (cross-attention only, Lk_fixed > 0): sequence b attends to the key / value rows of entry b / kv_group, of which
 // there are B / kv_group (the beam slots of a clip share the clip's hoisted K/V).  write_p = false: no probability output.
+// KVLEN (inference, no mask, no p_out): sequence b sees keys j < min(max(kv_len[b / kv_group], 0), Lk) only.  The rows behind the
+// count are never read - they are zeros in LDS, like the padding behind Lk - and the products run over the count's own 32-row
+// tiles; the probability layout, and with it the dropout mask index of (i, j), stays that of Lk keys.
+template <bool KVLEN = false>
 __device__ __forceinline__ void attention_fwd_body(const float* __restrict__ q, long ldq, const float* __restrict__ k,
                                                    long ldk, const float* __restrict__ v, long ldv,
                                                    float* __restrict__ o, long ldo, float* __restrict__ p_out,
                                                    int mask_kind, const uint8_t* __restrict__ mask, int B, int H,
                                                    const SegDesc& segs, int Lk_fixed, float scale, uint32_t thresh,
                                                    float keep_scale, const uint64_t* __restrict__ seed,
-                                                   uint64_t offset, int sz, unsigned long long* stamp, int kv_group, bool write_p) {
+                                                   uint64_t offset, int sz, unsigned long long* stamp, int kv_group, bool write_p,
+                                                   const int32_t* __restrict__ kv_len = nullptr) {
     sbl_stamp_begin(stamp);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *Qs = smem, *Ks = smem + sz, *Vs = smem + 2 * sz, *Ss = smem + 3 * sz;      // sz = rows actually needed x AT_LD
@@ -62,10 +67,12 @@ __device__ __forceinline__ void attention_fwd_body(const float* __restrict__ q, 
     const int Lq = segs.L[sidx], Lk = Lk_fixed > 0 ? Lk_fixed : Lq;
     const long qrow = segs.row_off[sidx] + (long)b * Lq;
     const long krow = Lk_fixed > 0 ? (long)(b / kv_group) * Lk : qrow;
-    const int Lqp = (Lq + 31) & ~31, Lkp = (Lk + 31) & ~31;
+    int Lv = Lk;                                      // visible keys
+    if constexpr (KVLEN) Lv = min(max(kv_len[b / kv_group], 0), Lk);
+    const int Lqp = (Lq + 31) & ~31, Lkp = (Lv + 31) & ~31;
     load_head(Qs, q + qrow * ldq + h * 64, ldq, Lq, Lqp, tid);
-    load_head(Ks, k + krow * ldk + h * 64, ldk, Lk, Lkp, tid);
-    load_head(Vs, v + krow * ldv + h * 64, ldv, Lk, Lkp, tid);
+    load_head(Ks, k + krow * ldk + h * 64, ldk, Lv, Lkp, tid);
+    load_head(Vs, v + krow * ldv + h * 64, ldv, Lv, Lkp, tid);
     __syncthreads();
     // S = Q K^T * scale
     const int TQ = Lqp >> 5, TK = Lkp >> 5;
@@ -84,7 +91,7 @@ __device__ __forceinline__ void attention_fwd_body(const float* __restrict__ q, 
     for (int i = wave; i < Lqp; i += 4) {
         float pv = 0.f, pd = 0.f;
         if (i < Lq) {
-            const bool valid = lane < Lk && !at_masked(mask_kind, mask, b, i, lane, Lq, Lk);
+            const bool valid = lane < Lv && !at_masked(mask_kind, mask, b, i, lane, Lq, Lk);
             const float s = valid ? Ss[i * AT_LD + lane] : -INFINITY;
             const float m = wave_max(s);
             const float e = valid ? __expf(s - m) : 0.f;
@@ -129,6 +136,15 @@ __global__ __launch_bounds__(256) void attention_grouped_fwd_kernel(const float*
                                                                     uint64_t offset, int sz) {
     attention_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, nullptr, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
                        offset, sz, nullptr, kv_group, false);
+}
+__global__ __launch_bounds__(256) void attention_len_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                                long ldk, const float* __restrict__ v, long ldv,
+                                                                float* __restrict__ o, long ldo, int B, int H, SegDesc segs,
+                                                                int Lk_fixed, int kv_group, const int32_t* __restrict__ kv_len,
+                                                                float scale, uint32_t thresh, float keep_scale,
+                                                                const uint64_t* __restrict__ seed, uint64_t offset, int sz) {
+    attention_fwd_body<true>(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, nullptr, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
+                             offset, sz, nullptr, kv_group, false, kv_len);
 }
 
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const float* __restrict__ dout, long lddo, const float* __restrict__ q,
@@ -337,7 +353,9 @@ __device__ __forceinline__ SmallProb small_prob(int prob, int B, int H, const Se
     return P;
 }
 
-template <bool ENDS = false>
+// KVLEN: as in attention_fwd_body.  The key tiles are those of the count (one tile for <= 16 visible keys), so a sequence
+// computes what the plain kernel computes on its K/V cut to the count: a masked key of a tile enters as an exact zero.
+template <bool ENDS = false, bool KVLEN = false>
 __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict__ q, long ldq, const float* __restrict__ k,
                                                          long ldk, const float* __restrict__ v, long ldv,
                                                          float* __restrict__ o, long ldo, float* __restrict__ p_out,
@@ -345,14 +363,17 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
                                                          float scale, uint32_t thresh, float keep_scale,
                                                          const uint64_t* __restrict__ seed, uint64_t offset, int nprob,
                                                          unsigned long long* stamp = nullptr, const SegDesc* full = nullptr,
-                                                         int kv_group = 1, bool write_p = true) {
+                                                         int kv_group = 1, bool write_p = true,
+                                                         const int32_t* __restrict__ kv_len = nullptr) {
     const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
     const int prob = blockIdx.x * 4 + (threadIdx.x >> 6);
     sbl_stamp_begin(stamp);      // (thread 0 = wavefront 0 of the workgroup, which always has a problem)
     if (prob >= nprob) return;   // whole wavefront; the kernel has no barrier
     const SmallProb P = small_prob<ENDS>(prob, B, H, segs, Lk_fixed, full, kv_group);
     const int Lq = P.Lq, Lk = P.Lk;
-    const int NT = Lk > 16 ? 2 : 1;
+    int Lv = Lk;                                      // visible keys
+    if constexpr (KVLEN) Lv = min(max(kv_len[P.b / kv_group], 0), Lk);
+    const int NT = Lv > 16 ? 2 : 1;
     const float* qb = q + P.qrow * ldq + P.h * 64;
     const float* kb = k + P.krow * ldk + P.h * 64;
     const float* vb = v + P.krow * ldv + P.h * 64;
@@ -365,12 +386,12 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
     for (int t = 0; t < 2; ++t) {
         if (t < NT) {
             RowFrag kf;
-            frag_load(kf, kb, ldk, 16 * t + n, 16 * t + n < Lk, g);
+            frag_load(kf, kb, ldk, 16 * t + n, 16 * t + n < Lv, g);
             const f32x4 acc = frag_dot(kf, qf);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * t + 4 * g + r;
-                const bool valid = j < Lk && !(causal && j > n + P.qoff);
+                const bool valid = j < Lv && !(causal && j > n + P.qoff);
                 s[t][r] = valid ? acc[r] * scale : -INFINITY;
                 m = fmaxf(m, s[t][r]);
             }
@@ -417,7 +438,7 @@ __device__ __forceinline__ void attention_small_fwd_body(const float* __restrict
             for (int r = 0; r < 4; ++r) {
                 const int j = 16 * t + 4 * g + r;
                 float vv[4];
-                ld4(vv, vb + (long)j * ldv + 4 * n, j < Lk);
+                ld4(vv, vb + (long)j * ldv + 4 * n, j < Lv);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) oacc[e] = MFMA16(s[t][r], vv[e], oacc[e]);
             }
@@ -449,6 +470,15 @@ __global__ __launch_bounds__(256) void attention_small_grouped_fwd_kernel(const 
                                                                           uint64_t offset, int nprob) {
     attention_small_fwd_body(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed, offset,
                              nprob, nullptr, nullptr, kv_group, false);
+}
+__global__ __launch_bounds__(256) void attention_small_len_fwd_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k,
+                                                                      long ldk, const float* __restrict__ v, long ldv,
+                                                                      float* __restrict__ o, long ldo, int B, int H, SegDesc segs,
+                                                                      int Lk_fixed, int kv_group, const int32_t* __restrict__ kv_len,
+                                                                      float scale, uint32_t thresh, float keep_scale,
+                                                                      const uint64_t* __restrict__ seed, uint64_t offset, int nprob) {
+    attention_small_fwd_body<false, true>(q, ldq, k, ldk, v, ldv, o, ldo, nullptr, 0, B, H, segs, Lk_fixed, scale, thresh, keep_scale, seed,
+                                          offset, nprob, nullptr, nullptr, kv_group, false, kv_len);
 }
 // Two same-shape problems in one launch (the two decoder directions; blockIdx.y picks the operand set).
 struct AttFwdSet {
@@ -840,6 +870,45 @@ extern "C" int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const flo
     hipLaunchKernelGGL(attention_grouped_fwd_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k,
                        ldk, v, ldv, o, ldo, B, H, d, Lk_fixed, kv_group, scale, thresh, keep_scale, seed, offset, sz);
     SBL_LAUNCH_CHECK("sbl_attention_seg_grouped_fwd");
+    return 0;
+}
+
+// sbl_attention_seg_grouped_fwd with a device-side key count per K/V entry (include/sbl_hip.h); Lk_fixed == 0: one segment of
+// self-attention, the count per sequence.  The dispatch is the grouped entry's, on the host-known shapes alone: kv_len is never
+// read here.
+extern "C" int sbl_attention_seg_len_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                                         long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
+                                         const int32_t* kv_len, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
+                                         sbl_stream_t stream) {
+    SegDesc d;
+    SBL_REQUIRE(kv_len, "sbl_attention_seg_len_fwd: kv_len is NULL");
+    SBL_REQUIRE(sbl_make_segs(d, seg_L, nseg, B, H, Lk_fixed) > 0, "sbl_attention_seg_len_fwd: bad segment list (nseg=%d, 1..%d)", nseg, SBL_MAX_SEG);
+    SBL_REQUIRE(Lk_fixed >= 0, "sbl_attention_seg_len_fwd: Lk=%d", Lk_fixed);
+    SBL_REQUIRE(Lk_fixed > 0 || (nseg == 1 && kv_group == 1),
+                "sbl_attention_seg_len_fwd: self-attention (Lk = 0) takes one segment and kv_group 1 (got nseg=%d, kv_group=%d)", nseg, kv_group);
+    SBL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "sbl_attention_seg_len_fwd: B=%d is no multiple of the group size %d", B, kv_group);
+    if (int e = at_check("sbl_attention_seg_len_fwd", B, H, d, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
+    SBL_REQUIRE(q && k && v && o && sbl_aligned16(q) && sbl_aligned16(k) && sbl_aligned16(v) && sbl_aligned16(o),
+                "sbl_attention_seg_len_fwd: null/unaligned pointer");
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_seg_len_fwd: bad dropout args");
+    const uint32_t thresh = drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u;
+    const float keep_scale = 1.f / (1.f - drop_p);
+    const bool small = at_small_ok(d, Lk_fixed, 0);
+    if (small || at_qtile_ok(d, Lk_fixed, 0)) {
+        const int Lk = Lk_fixed > 0 ? Lk_fixed : d.L[0];      // query tiles of a self-attention read the sequence's own L rows
+        const SegDesc t = small ? d : at_qtile_desc(d.L[0], Lk);
+        const int nprob = (small ? nseg : 2) * B * H;
+        hipLaunchKernelGGL(attention_small_len_fwd_kernel, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk,
+                           v, ldv, o, ldo, B, H, t, small ? Lk_fixed : Lk, kv_group, kv_len, scale, thresh, keep_scale, seed, offset, nprob);
+        SBL_LAUNCH_CHECK("sbl_attention_seg_len_fwd(small)");
+        return 0;
+    }
+    const int sz = at_rows_sz(d, nseg, Lk_fixed);
+    static bool attr_set[64] = {false};
+    SBL_HIP(sbl_raise_lds_cap((const void*)attention_len_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
+    hipLaunchKernelGGL(attention_len_fwd_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k,
+                       ldk, v, ldv, o, ldo, B, H, d, Lk_fixed, kv_group, kv_len, scale, thresh, keep_scale, seed, offset, sz);
+    SBL_LAUNCH_CHECK("sbl_attention_seg_len_fwd");
     return 0;
 }
 

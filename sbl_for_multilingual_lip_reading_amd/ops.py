@@ -774,15 +774,34 @@ def out_ln_fwd(h, a, res, seed, off, bufs=None):
     return o, y, mean, rstd
 
 
-def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o, kv_group=None):
+def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o, kv_group=None, kv_len=None):
     """Attention sub-layer on the rows x (B * sum(segL), D) of a ragged batch: segment s has B sequences of length segL[s].
     kv = None: self-attention inside each segment; else cross-attention to the rows kv (B * Lk, 2 * H * 64) = [K|V] (a
     column block of a wider buffer is fine).  Returns (y, (qkv, att, p, o, mean, rstd)): the second is what attn_bwd wants
     back; p = the segments' (H*B, L, Lk) probability blocks back to back.
     kv_group = W (inference only, no mask): kv holds B / W entries and sequence b attends to entry b // W
-    (sbl_attention_seg_grouped_fwd); no probabilities are kept (p = None)."""
+    (sbl_attention_seg_grouped_fwd); no probabilities are kept (p = None).
+    kv_len (inference only, no mask; kv_group = None means 1): a device int32 tensor of key counts, one per kv entry (B /
+    kv_group of them) or, with kv = None (one segment), one per sequence: only the keys j < kv_len[.] are attended to
+    (sbl_attention_seg_len_fwd).  The counts are never read on the host; p = None."""
     HD = a.H * 64
     qkv = lin_fwd(a.inp, x)
+    if kv_len is not None:
+        G = 1 if kv_group is None else int(kv_group)
+        assert not torch.is_grad_enabled() and mask_kind == 0 and B % G == 0
+        assert kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous() and kv_len.numel() == B // G, \
+            "kv_len: a contiguous CUDA int32 tensor of %d counts" % (B // G)
+        if kv is None:
+            assert G == 1 and len(segL) == 1
+            k, v, ldk, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, 0
+        else:
+            assert kv.size(0) % (B // G) == 0
+            k, v, ldk, Lk = kv, kv[:, HD:], _rows(kv)[1], kv.size(0) // (B // G)
+        att = _new(x, x.size(0), HD)
+        call("sbl_attention_seg_len_fwd", _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(att), HD, B, a.H, *_segs(segL), Lk, G,
+             _p(kv_len), 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+        o, y, mean, rstd = out_ln_fwd(a, att, x, seed, off_o)
+        return y, (qkv, att, None, o, mean, rstd)
     if kv_group is not None:
         assert kv is not None and mask_kind == 0 and B % kv_group == 0 and kv.size(0) % (B // kv_group) == 0
         ldk = _rows(kv)[1]

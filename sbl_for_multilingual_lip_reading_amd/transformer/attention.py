@@ -80,23 +80,25 @@ class MultiHeadAttention(nn.Module):
         return ops.KVProjectFn.apply(k.reshape(-1, k.size(-1)), self.w_ks.weight, self.w_ks.bias,
                                      self.w_vs.weight, self.w_vs.bias)
 
-    def forward_rows(self, x2, B, segL, mask=None, kv_proj=None, kv_group=None):
+    def forward_rows(self, x2, B, segL, mask=None, kv_proj=None, kv_group=None, kv_len=None):
         """Sub-layer on a ragged batch of rows: x2 (B*sum(segL), d_model); segment s holds B sequences of length
         segL[s] (the SBL decoder batches the steps of one teacher-forced run this way).  kv_proj=None: self-attention
         inside each segment; else cross-attention to the pre-projected [K|V] rows (B*Lk, 2*n_head*64).
         mask: None | 'causal' (| a (B,Lq,Lk) tensor when there is a single segment).  Returns (out rows, attn flat).
         kv_group = W (beam search; no_grad only, no mask): kv_proj holds B / W entries, sequence b attends to entry b // W,
-        and no probabilities come back (attn is None)."""
+        and no probabilities come back (attn is None).
+        kv_len (no_grad only, no mask): device int32 key counts, one per kv_proj entry or - self-attention of one segment -
+        per sequence; keys at or behind the count are not attended to (ops.attn_fwd); attn is None."""
         drop_p = self.dropout.p if self.training else 0.0
-        if kv_group is not None:
-            assert kv_proj is not None and mask is None and not torch.is_grad_enabled()
-            ops._need_cuda(x2, kv_proj)
+        if kv_group is not None or kv_len is not None:
+            assert mask is None and not torch.is_grad_enabled() and (kv_proj is not None or kv_group is None)
+            ops._need_cuda(x2, kv_proj, kv_len)
             seed, off_a, off_o = None, 0, 0
             if drop_p > 0:
                 st = ops.dropout_state(x2.device)
                 seed, off_a, off_o = st.seed, st.next_offset(), st.next_offset()
-            y, _ = ops.attn_fwd(self.handle(cross=True), x2.contiguous(), B, tuple(segL), kv_proj, 0, None, seed, off_a, off_o,
-                                kv_group=kv_group)
+            y, _ = ops.attn_fwd(self.handle(cross=kv_proj is not None), x2.contiguous(), B, tuple(segL), kv_proj, 0, None, seed,
+                                off_a, off_o, kv_group=kv_group, kv_len=kv_len)
             return y, None
         if isinstance(mask, str) or mask is None:
             mask_kind, mask_t = (1, None) if mask == "causal" else (0, None)

@@ -201,10 +201,25 @@ class Decoder(nn.Module):
                 kv[1] = [lay.enc_attn.project_kv(encoder_outputs) for lay in layers[1]]
         return layers, main, side, kv
 
-    def _stage(self, ys, B, segL, layers, main, side, kv, kv_group=None):
+    @staticmethod
+    def _kv_len(encoder_input_lengths, encoder_outputs):
+        """The cross-attention key counts of a decode: None, or the clips' frame counts as a device int32 (N,) tensor (a CUDA
+        int32 tensor is used as it is and never read on the host)."""
+        lens = encoder_input_lengths
+        if lens is None:
+            return None
+        if not (isinstance(lens, torch.Tensor) and lens.is_cuda):
+            lens = torch.as_tensor(lens, dtype=torch.int32).to(encoder_outputs.device)
+        if lens.dtype != torch.int32 or lens.shape != (encoder_outputs.size(0),) or not lens.is_contiguous():
+            raise _lib.SblHipError("encoder_input_lengths: a contiguous int32 (%d,) tensor, got %s %s"
+                                   % (encoder_outputs.size(0), lens.dtype, tuple(lens.shape)))
+        return lens
+
+    def _stage(self, ys, B, segL, layers, main, side, kv, kv_group=None, kv_len=None):
         """One stage on B sequences per segment: embedding + PE of the token tables ys[direction], the n_layers layers of
         both directions with the fusion after each -> x[direction], the rows (B * sum(segL), d_model) behind the last
-        fusion.  kv_group = W: kv belongs to B / W clips whose W beam slots share it (DecoderLayer.forward_rows)."""
+        fusion.  kv_group = W: kv belongs to B / W clips whose W beam slots share it (DecoderLayer.forward_rows).
+        kv_len: the clips' frame counts (`_kv_len`), the keys of every cross-attention."""
         emb = self.tgt_word_emb.weight
         pe = self.positional_encoding.pe[0]
         x = [ops.dropout(ops.EmbedPEFn.apply(ys[d], B, segL, emb, pe), self.dropout.p, self.training) for d in (0, 1)]
@@ -212,26 +227,27 @@ class Decoder(nn.Module):
             slf_mask = 'causal' if n == 0 else None       # decoder.py:123-125 vs :150,:157
             if side is None:
                 for d in (0, 1):
-                    x[d] = layers[d][n].forward_rows(x[d], B, segL, slf_mask, kv[d][n], kv_group)
+                    x[d] = layers[d][n].forward_rows(x[d], B, segL, slf_mask, kv[d][n], kv_group, kv_len)
             else:
                 # the l2r and r2l layers are independent until the fusion: run them on two HIP streams so their
                 # small kernels overlap on the 256 CUs (fork / join is captured as parallel hipGraph branches;
                 # autograd replays backward on the same two streams)
                 side.wait_stream(main)
-                x[0] = layers[0][n].forward_rows(x[0], B, segL, slf_mask, kv[0][n], kv_group)
+                x[0] = layers[0][n].forward_rows(x[0], B, segL, slf_mask, kv[0][n], kv_group, kv_len)
                 with torch.cuda.stream(side):
-                    x[1] = layers[1][n].forward_rows(x[1], B, segL, slf_mask, kv[1][n], kv_group)
+                    x[1] = layers[1][n].forward_rows(x[1], B, segL, slf_mask, kv[1][n], kv_group, kv_len)
                 main.wait_stream(side)
             x[0], x[1] = ops.FusionFn.apply(x[0], x[1], B, segL)
         return x
 
-    def _stage_last(self, ys, B, segL, layers, main, side, kv, kv_group=None):
+    def _stage_last(self, ys, B, segL, layers, main, side, kv, kv_group=None, kv_len=None):
         """`_stage`, then position -1 of every prefix: per direction the (len(segL) * B, d_model) rows the heads read."""
-        x = self._stage(ys, B, segL, layers, main, side, kv, kv_group)
+        x = self._stage(ys, B, segL, layers, main, side, kv, kv_group, kv_len)
         return [ops.GatherLastFn.apply(x[d], B, segL) for d in (0, 1)]
 
-    def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode):
-        """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383)."""
+    def _run(self, encoder_outputs, gold_l2r, gold_r2l, teacher_mode, kv_len=None):
+        """The 16 decoding steps shared by forward (decoder.py:106-186) and recognize_beam (:310-383).  kv_len (inference
+        only): the clips' frame counts (`_stage`)."""
         maxlen = config.MAX_DECODE_LEN
         N = encoder_outputs.size(0)
         dev = encoder_outputs.device
@@ -261,7 +277,7 @@ class Decoder(nn.Module):
         with ops.deferring():      # decoder weights are used once per stage: their dW GEMMs are deferred and merged
             for (i0, i1) in stages:
                 segL = tuple(range(i0 + 1, i1 + 2))            # prefix lengths of the steps in this stage
-                last = self._stage_last(ys, N, segL, layers, main, side, kv)     # (nseg*N, 512) per direction
+                last = self._stage_last(ys, N, segL, layers, main, side, kv, kv_len=kv_len)     # (nseg*N, 512) per direction
                 for d in (0, 1):
                     pred = ops.linear(last[d], heads[d])                   # (nseg*N, 58)
                     # unbind (one stack in backward) instead of row slices (a zero-filled (nseg*N, 58) buffer, a copy and
@@ -299,13 +315,17 @@ class Decoder(nn.Module):
         outs, _ = self._run(encoder_outputs, ys_out_pad_l2r, ys_out_pad_r2l, teacher_mode=True)
         return torch.stack(outs[0], 1), ys_out_pad_l2r, torch.stack(outs[1], 1), ys_out_pad_r2l
 
-    def recognize_beam(self, encoder_outputs):
-        """Greedy decode, always own argmax (decoder.py:301-385).  Returns (ys_l2r, ys_r2l) (N,17) int64."""
+    def recognize_beam(self, encoder_outputs, encoder_input_lengths=None):
+        """Greedy decode, always own argmax (decoder.py:301-385).  Returns (ys_l2r, ys_r2l) (N,17) int64.
+        encoder_input_lengths (here and in every decode method below): None, or the clips' frame counts - N ints or a device
+        int32 (N,) tensor, which is never read on the host.  Clip n then attends to the encoder rows t < lengths[n] only, so
+        whatever the rows behind hold does not matter and the clip decodes as it would alone at its length."""
         with torch.no_grad():
-            _, ys = self._run(encoder_outputs, None, None, teacher_mode=False)
+            _, ys = self._run(encoder_outputs, None, None, teacher_mode=False,
+                              kv_len=self._kv_len(encoder_input_lengths, encoder_outputs))
         return ys[0], ys[1]
 
-    def beam_search(self, encoder_outputs, beam_size, nbest=1):
+    def beam_search(self, encoder_outputs, beam_size, nbest=1, encoder_input_lengths=None):
         """Beam search over PAIRS of an l2r and an r2l prefix - the search that recognize_beam's name and the reference's
         beam_size / nbest arguments promise (decoder.py:301-385 is greedy).  A pair is fused exactly as row b of the two
         directions is in `_run`; every clip keeps W = beam_size pairs, the batch is S = N * W rows, and because the upper
@@ -331,12 +351,12 @@ class Decoder(nn.Module):
             raise _lib.SblHipError("Decoder.beam_search needs the encoder output on the GPU (got a %s tensor); there is no "
                                    "CPU path" % enc.device)
         with torch.no_grad():
-            st = self._beam_run(enc, W)
+            st = self._beam_run(enc, W, self._kv_len(encoder_input_lengths, enc))
         N, L = enc.size(0), config.MAX_DECODE_LEN + 1
         ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(config.MAX_DECODE_LEN))
         return PairBeamResult(ys_l, ys_r, st.score[:, :nbest], st.score_dir[:, :nbest], st.history())
 
-    def _beam_run(self, encoder_outputs, W):
+    def _beam_run(self, encoder_outputs, W, kv_len=None):
         """The 16 steps of beam_search -> the final ops.PairBeamState.  The stage is `_run`'s, at batch N * W."""
         maxlen = config.MAX_DECODE_LEN
         N = encoder_outputs.size(0)
@@ -345,11 +365,11 @@ class Decoder(nn.Module):
         st = ops.PairBeamState(N, W, maxlen, self.sos_id, self.eos_id, encoder_outputs.device)
         heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
         for i in range(maxlen):
-            last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W)
+            last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W, kv_len=kv_len)
             ops.pair_beam_tail(last[0], last[1], heads[0], heads[1], st, i)
         return st
 
-    def score_pairs(self, encoder_outputs, ys_l2r, ys_r2l, n_pos=None, group=1):
+    def score_pairs(self, encoder_outputs, ys_l2r, ys_r2l, n_pos=None, group=1, encoder_input_lengths=None):
         """Pair scores of S given token rows (include/sbl_hip.h, sbl_pair_score_tail): with lpL_i / lpR_i the two heads'
         log-softmax at the last position of prefix length i + 1 of slot s - the pair fused exactly as `_run` and beam_search
         fuse it - taken at ys_l2r[s][i+1] / ys_r2l[s][i+1]: logp[s, i] = (lpL_i, lpR_i) for i < n_pos[s], else 0; score_dir
@@ -374,6 +394,7 @@ class Decoder(nn.Module):
             raise _lib.SblHipError("Decoder.score_pairs: %d and %d token rows for %d clips in groups of %d (1..%d)"
                                    % (S, ys[1].size(0), N, G, MAX_PAIR_BEAM))
         dev = enc.device
+        kv_len = self._kv_len(encoder_input_lengths, enc)
         out = PairScore(torch.empty(S, device=dev), torch.empty(S, 2, device=dev), torch.empty(S, maxlen, 2, device=dev),
                         torch.empty(N, dtype=torch.int32, device=dev))
         segL = tuple(range(1, maxlen + 1))
@@ -385,12 +406,13 @@ class Decoder(nn.Module):
                 s0, s1 = c0 * G, c1 * G
                 layers, main, side, kv = self._begin(enc[c0:c1])
                 tok = [y[s0:s1] for y in ys]
-                last = self._stage_last(tok, s1 - s0, segL, layers, main, side, kv, kv_group=G)
+                last = self._stage_last(tok, s1 - s0, segL, layers, main, side, kv, kv_group=G,
+                                        kv_len=None if kv_len is None else kv_len[c0:c1])
                 ops.pair_score_tail(last[0], last[1], heads[0], heads[1], tok[0], tok[1], None if n_pos is None else n_pos[s0:s1], G,
                                     out.logp[s0:s1], out.score_dir[s0:s1], out.score[s0:s1], out.best[c0:c1])
         return out
 
-    def recognize_words(self, encoder_outputs, lexicon, beam_size=None, nbest=1, shortlist=8):
+    def recognize_words(self, encoder_outputs, lexicon, beam_size=None, nbest=1, shortlist=8, encoder_input_lengths=None):
         """Closed-vocabulary decode: the word of `lexicon` (transformer.lexicon.Lexicon) for every clip, in two passes on the
         device.  Hypotheses: the greedy pair of recognize_beam (beam_size = None, H = 1) or the nbest pairs of
         beam_search(beam_size, nbest) (H = nbest).  Shortlist (sbl_lexicon_shortlist): D(h, w) = lev(p_l, w) +
@@ -410,18 +432,19 @@ class Decoder(nn.Module):
         if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
             raise _lib.SblHipError("Decoder.recognize_words: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
                                    % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+        kv_len = self._kv_len(encoder_input_lengths, enc)
         if beam_size is None:
-            ys_l, ys_r = self.recognize_beam(enc)
+            ys_l, ys_r = self.recognize_beam(enc, kv_len)
         else:
-            res = self.beam_search(enc, beam_size, nbest)
+            res = self.beam_search(enc, beam_size, nbest, kv_len)
             ys_l, ys_r = res.ys_l2r, res.ys_r2l
         N = enc.size(0)
         sl = ops.lexicon_shortlist(ys_l, ys_r, lexicon.packed, K, self.sos_id, self.eos_id, IGNORE_ID)
-        ps = self.score_pairs(enc, sl.cand_ys_l2r, sl.cand_ys_r2l, sl.n_pos, group=K)
+        ps = self.score_pairs(enc, sl.cand_ys_l2r, sl.cand_ys_r2l, sl.n_pos, group=K, encoder_input_lengths=kv_len)
         word = sl.cand.gather(1, ps.best.long().unsqueeze(1)).squeeze(1).long()
         return WordResult(word, sl.cand, sl.cand_dist, sl.cand_hyp, ps.score.view(N, K), ps.score_dir.view(N, K, 2))
 
-    def beam_search_lex(self, encoder_outputs, lexicon, beam_size, nbest=1):
+    def beam_search_lex(self, encoder_outputs, lexicon, beam_size, nbest=1, encoder_input_lengths=None):
         """Closed-vocabulary decode in ONE pass: beam_search restricted to the words of `lexicon` (transformer.lexicon.Lexicon)
         through its pair trie (Lexicon.pair_trie; include/sbl_hip.h, sbl_pair_beam_tail_lex).  Every hypothesis pair is one
         word - the l2r row spells w, the r2l row reversed(w), which is what the model was trained on - so the n-best are
@@ -449,12 +472,13 @@ class Decoder(nn.Module):
         N, L = enc.size(0), config.MAX_DECODE_LEN + 1
         S, steps = N * W, lexicon.max_len + 1
         trie = lexicon.pair_trie()
+        kv_len = self._kv_len(encoder_input_lengths, enc)
         with torch.no_grad():
             layers, main, side, kv = self._begin(enc)
             st = ops.PairBeamState(N, W, steps, self.sos_id, self.eos_id, enc.device, lex=True, row_len=L)
             heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
             for i in range(steps):
-                last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W)
+                last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W, kv_len=kv_len)
                 ops.pair_beam_tail_lex(last[0], last[1], heads[0], heads[1], st, i, trie)
             cand = trie[2][st.nodes(steps)[:, :nbest].long()]      # a dead rank sits on node 0, whose word is -1
         ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(steps))
@@ -471,11 +495,12 @@ class DecoderLayer(nn.Module):
         self.enc_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=dropout)
 
-    def forward_rows(self, x2, B, segL, slf_attn_mask, enc_kv, kv_group=None):
+    def forward_rows(self, x2, B, segL, slf_attn_mask, enc_kv, kv_group=None, kv_len=None):
         """The layer on a ragged batch of rows (see MultiHeadAttention.forward_rows); non_pad_mask is all ones on
-        this path (decoder.py:109,112).  kv_group = W: enc_kv belongs to B / W clips whose W beam slots share it."""
+        this path (decoder.py:109,112).  kv_group = W: enc_kv belongs to B / W clips whose W beam slots share it.
+        kv_len: device int32 key counts of the enc_kv entries (cross-attention only)."""
         x2, _ = self.slf_attn.forward_rows(x2, B, segL, mask=slf_attn_mask)
-        x2, _ = self.enc_attn.forward_rows(x2, B, segL, mask=None, kv_proj=enc_kv, kv_group=kv_group)
+        x2, _ = self.enc_attn.forward_rows(x2, B, segL, mask=None, kv_proj=enc_kv, kv_group=kv_group, kv_len=kv_len)
         return self.pos_ffn(x2)
 
     def forward(self, dec_input, enc_output, non_pad_mask=None, slf_attn_mask=None, dec_enc_attn_mask=None,

@@ -12,7 +12,9 @@ from .utils import get_non_pad_mask, get_attn_pad_mask
 class Encoder(nn.Module):
     """Frame features (N, T, d_input) -> dropout(LayerNorm(linear_in(x)) + PE) -> n_layers post-norm
     self-attention + FFN layers -> (N, T, d_model).  Positions past input_lengths[n] are masked out as keys and
-    zeroed after every sub-layer."""
+    zeroed after every sub-layer.  With gradients disabled a ragged batch takes the key-count attention kernels
+    (sbl_attention_seg_len_fwd: no mask tensor, the padded frames' K/V rows are never read); with gradients enabled
+    the explicit (N, T, T) mask."""
 
     def __init__(self, d_input, n_layers, n_head, d_k, d_v,
                  d_model, d_inner, dropout=0.1, pe_maxlen=5000):
@@ -35,15 +37,22 @@ class Encoder(nn.Module):
                                          for _ in range(n_layers))
 
     def forward(self, padded_input, input_lengths, return_attns=False):
-        """padded_input (N, T, d_input), input_lengths N ints.  Returns (out,) or, with return_attns,
+        """padded_input (N, T, d_input); input_lengths: N ints on the host (ragged when one is < T), or a CUDA int32 (N,)
+        tensor, which is never read on the host and always counts as ragged.  Returns (out,) or, with return_attns,
         (out, [per-layer attention (n_head*N, T, T)])."""
         N, T, _ = padded_input.shape
-        if all(int(l) >= T for l in input_lengths):
-            # full-length batch (what Transformer always passes): every mask would be a no-op
+        on_device = isinstance(input_lengths, torch.Tensor) and input_lengths.is_cuda
+        kv_len = None
+        if not on_device and all(int(l) >= T for l in input_lengths):
+            # full-length batch (what Transformer passes without lengths): every mask would be a no-op
             non_pad_mask, slf_attn_mask = None, None
-        else:
+        elif torch.is_grad_enabled() or return_attns:
             non_pad_mask = get_non_pad_mask(padded_input, input_lengths)
             slf_attn_mask = get_attn_pad_mask(padded_input, input_lengths, T)
+        else:
+            kv_len = input_lengths if on_device else torch.as_tensor([int(l) for l in input_lengths], dtype=torch.int32)
+            kv_len = kv_len.to(device=padded_input.device, dtype=torch.int32).contiguous().view(N)
+            non_pad_mask, slf_attn_mask = get_non_pad_mask(padded_input, kv_len), None
 
         # the layers' weight gradients are deferred and issued as one grouped launch when backward reaches the
         # encoder input (second stream, under the frontend backward) or at the end of backward, whichever is first
@@ -57,7 +66,7 @@ class Encoder(nn.Module):
 
             attns = [] if return_attns else None
             for layer in self.layer_stack:
-                h, attn = layer(h, non_pad_mask=non_pad_mask, slf_attn_mask=slf_attn_mask)
+                h, attn = layer(h, non_pad_mask=non_pad_mask, slf_attn_mask=slf_attn_mask, kv_len=kv_len)
                 if attns is not None:
                     attns.append(attn)
         return (h,) if attns is None else (h, attns)
@@ -71,7 +80,13 @@ class EncoderLayer(nn.Module):
         self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
         self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=dropout)
 
-    def forward(self, enc_input, non_pad_mask=None, slf_attn_mask=None):
-        h, attn = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask)
+    def forward(self, enc_input, non_pad_mask=None, slf_attn_mask=None, kv_len=None):
+        """kv_len (no_grad only, instead of slf_attn_mask): device int32 (N,), the keys t < kv_len[n] are attended to."""
+        if kv_len is not None:
+            N, T, D = enc_input.shape
+            h, attn = self.slf_attn.forward_rows(enc_input.reshape(N * T, D), N, (T,), kv_len=kv_len)
+            h = h.view(N, T, D)
+        else:
+            h, attn = self.slf_attn(enc_input, enc_input, enc_input, mask=slf_attn_mask)
         h = mask_rows(h, non_pad_mask)
         return mask_rows(self.pos_ffn(h), non_pad_mask), attn
