@@ -28,23 +28,25 @@ def preprocess(padded, sos_id=0, eos_id=1, ignore_id=-1):
     return ys_in, ys_out
 
 
-def _layers(sd, x, enc, n_layers, slf_mask, cross_mask, non_pad):
+def _layers(sd, x, enc, n_layers, slf_mask, cross_mask, non_pad, drop=0.0):
     for n in range(n_layers):
         p = "decoder.layer_stack.%d" % n
-        x, _ = O.mha(sd, p + ".slf_attn", x, x, slf_mask)
+        x, _ = O.mha(sd, p + ".slf_attn", x, x, slf_mask, drop=drop)
         if non_pad is not None:
             x = x * non_pad
-        x, _ = O.mha(sd, p + ".enc_attn", x, enc, cross_mask)
+        x, _ = O.mha(sd, p + ".enc_attn", x, enc, cross_mask, drop=drop)
         if non_pad is not None:
             x = x * non_pad
-        x = O.ffn(sd, p + ".pos_ffn", x)
+        x = O.ffn(sd, p + ".pos_ffn", x, drop)
         if non_pad is not None:
             x = x * non_pad
     return x
 
 
-def decoder_forward(sd, tgt, enc, n_layers, scale, enc_lengths=None, sos_id=0, eos_id=1):
-    """decoder.py:81-136 -> (pred (N, 14, V), gold (N, 14))."""
+def decoder_forward(sd, tgt, enc, n_layers, scale, enc_lengths=None, sos_id=0, eos_id=1, drop=0.0):
+    """decoder.py:81-136 -> (pred (N, 14, V), gold (N, 14)).  drop > 0: train mode, every dropout decision through
+    O._dropout in the order embedding, then per layer the self-attention probabilities and output, the cross-attention
+    probabilities and output, the feed-forward output."""
     ys_in, ys_out = preprocess(tgt, sos_id, eos_id)
     N, L = ys_in.shape
     pad = ys_in.eq(eos_id)
@@ -52,8 +54,8 @@ def decoder_forward(sd, tgt, enc, n_layers, scale, enc_lengths=None, sos_id=0, e
     cross_mask = None
     if enc_lengths is not None:
         cross_mask = (torch.arange(enc.size(1)).unsqueeze(0) >= torch.as_tensor(enc_lengths).unsqueeze(1)).unsqueeze(1).expand(-1, L, -1)
-    x = sd["decoder.tgt_word_emb.weight"][ys_in] * scale + O.positional_encoding(L).unsqueeze(0)
-    x = _layers(sd, x, enc, n_layers, slf_mask, cross_mask, (~pad).float().unsqueeze(-1))
+    x = O._dropout(sd["decoder.tgt_word_emb.weight"][ys_in] * scale + O.positional_encoding(L).unsqueeze(0), drop, drop > 0)
+    x = _layers(sd, x, enc, n_layers, slf_mask, cross_mask, (~pad).to(x.dtype).unsqueeze(-1), drop)
     return F.linear(x, sd["decoder.tgt_word_prj.weight"]), ys_out
 
 
