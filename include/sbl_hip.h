@@ -545,6 +545,42 @@ int sbl_beam_finish(const float* end_score, const int32_t* end_ref, const int32_
                     const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N, int W,
                     int maxlen, int nbest, int sos, int eos, sbl_stream_t stream);
 
+/* ---------------------------------------------------------------- ragged clips in the single-direction decodes
+ * Clip n of a padded batch decodes as the reference decodes it ALONE, cut to its first l_n frames: LRW/transformer/decoder.py
+ * :138-176 (greedy, maxlen = encoder_outputs.size(1) = l_n there) and LRW1000/transformer/decoder.py:131-245 (beam search,
+ * maxlen = l_n with decode_max_len == 0, :139-141; the forced end of :213-218 then comes at step l_n - 1).  All counts are
+ * device arrays that no entry reads on the host, so a captured graph follows an array that is overwritten in place.
+ *
+ * sbl_decode_attn_step / sbl_beam_attn_step with a key count per K/V entry, cross-attention only (append must be 0):
+ * kv_len holds B counts (decode) or S / W counts (beam, one per clip); row b sees key j iff
+ * j < min(max(kv_len[clip], 0), n_prev).  Cache rows at or behind the count are never loaded, in the score pass and in the
+ * value pass, so whatever they hold cannot reach o; a row without a visible key gets o = 0.  Row b's output is bit-identical
+ * to the entry without counts called with n_prev = its count on the same K / V.  anc / lda of sbl_beam_attn_step_len are
+ * kept for the argument list's sake and unused, as in sbl_beam_attn_step with append = 0 (pass NULL, 0).  Refused before
+ * any launch: kv_len == NULL,
+ * append != 0, and everything the entries without counts refuse. */
+int sbl_decode_attn_step_len(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                             float* v_cache, long ldc, int Lcap, float* o, long ldo, int B, int H, int n_prev, int append,
+                             float scale, const int32_t* kv_len, sbl_stream_t stream);
+int sbl_beam_attn_step_len(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                           float* v_cache, long ldc, int Lcap, const int32_t* anc, long lda, float* o, long ldo, int S, int W,
+                           int H, int n_prev, int append, float scale, const int32_t* kv_len, sbl_stream_t stream);
+/* sbl_beam_tail with a last step per clip: clip_steps (N) int32; every kept hypothesis of clip n ends (with the appended
+ * <eos> at no score) at step clamp(clip_steps[n], 1, maxlen) - 1 instead of maxlen - 1.  From the next step on the clip has no
+ * live hypothesis: its slots carry -inf, nothing is kept, the history flags are 0 and the ended list stays as it is.  With
+ * clip_steps[n] == maxlen for every clip all outputs equal sbl_beam_tail's bit for bit.  (The lexicon tail has no such form:
+ * its step count is the longest word's.) */
+int sbl_beam_tail_len(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
+                      const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par,
+                      float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count, int step,
+                      int maxlen, int eos, const float* emb, const float* pe, int pe_rows, float emb_scale, float* x_next, int N,
+                      int W, int V, int D, const int32_t* clip_steps, sbl_stream_t stream);
+/* sbl_beam_finish after sbl_beam_tail_len, with the same array: a hypothesis that ended at step s has length s + 3 when
+ * s == clamp(clip_steps[n], 1, maxlen) - 1 (the appended <eos>) and s + 2 otherwise.  yseq keeps its maxlen + 2 columns. */
+int sbl_beam_finish_len(const float* end_score, const int32_t* end_ref, const int32_t* end_count, const int32_t* hist_tok,
+                        const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N, int W,
+                        int maxlen, int nbest, int sos, int eos, const int32_t* clip_steps, sbl_stream_t stream);
+
 /* ---------------------------------------------------------------- beam search of the bidirectional SBL decoder
  * The reference's recognize_beam (SBL/transformer/decoder.py:301-385) is greedy; this is the search its beam_size / nbest
  * arguments name.  A hypothesis is a PAIR of an l2r and an r2l prefix that are fused with each other as row b of the two

@@ -82,6 +82,10 @@ SIGNATURES = {
     "sbl_beam_tail_lex": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P, P, I, P, P],
     "sbl_lexicon_lookup": [P, L, I, I, P, P, P, I, L, L, L, P, P, P],
     "sbl_beam_finish": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P],
+    "sbl_decode_attn_step_len": [P, L, P, P, L, P, P, L, I, P, L, I, I, I, I, F, P, P],
+    "sbl_beam_attn_step_len": [P, L, P, P, L, P, P, L, I, P, L, P, L, I, I, I, I, I, F, P, P],
+    "sbl_beam_tail_len": [P, L, P, P, P, P, P, P, L, P, P, P, P, P, P, P, I, I, I, P, P, I, F, P, I, I, I, I, P, P],
+    "sbl_beam_finish_len": [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, P, P],
     "sbl_pair_beam_tail": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P],
     "sbl_pair_beam_tail_lex": [P, P, L, P, P, P, P, P, P, P, P, L, P, P, P, P, I, I, I, I, I, I, I, P, P, P, I, I, P, P, P, P],
     "sbl_lexicon_shortlist": [P, P, L, L, I, P, I, I, I, I, L, L, L, P, P, P, P, P, P, P],

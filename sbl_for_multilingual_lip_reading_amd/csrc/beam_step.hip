@@ -26,14 +26,17 @@
 // LEX (sbl_beam_tail_lex): every slot carries a node of the lexicon's trie (include/sbl_hip.h); candidate (slot, v) exists only
 // where bit v of the node's mask is set - one 8-byte load per slot and a bit test per lane - and the kept rank's node is the
 // parent's child under v, a popcount below bit v.  Everything else is the one body, so the two searches share their arithmetic.
-template <bool LEX>
+// LEN (sbl_beam_tail_len): the clip's own last step, clamp(clip_steps[n], 1, maxlen) - 1, takes the place of maxlen - 1 in the
+// forced end; a clip behind its last step has no live slot, so the body keeps nothing for it.
+template <bool LEX, bool LEN = false>
 __global__ __launch_bounds__(256) void beam_tail_kernel(
     const float* __restrict__ y, long ldy, const float* __restrict__ w, const float* __restrict__ log_prior, float* score,
     int32_t* last_tok, const int32_t* __restrict__ anc_old, int32_t* __restrict__ anc_new, long lda, int32_t* __restrict__ hist_tok,
     int32_t* __restrict__ hist_par, float* __restrict__ hist_score, int32_t* __restrict__ hist_flag, float* __restrict__ end_score,
     int32_t* __restrict__ end_ref, int32_t* end_count, int step, int maxlen, int eos, const float* __restrict__ emb,
     const float* __restrict__ pe, float emb_scale, float* __restrict__ x_next, int W, int V,
-    const int64_t* __restrict__ trie_mask, const int32_t* __restrict__ trie_first, int P, int32_t* node) {
+    const int64_t* __restrict__ trie_mask, const int32_t* __restrict__ trie_first, int P, int32_t* node,
+    const int32_t* __restrict__ clip_steps) {
     __shared__ float s_cand[DH_MAX_W * 64];
     __shared__ int s_tok[DH_MAX_W], s_par[DH_MAX_W];
     __shared__ unsigned long long s_mask[DH_MAX_W];      // LEX: the slots' nodes (clamped to 0 .. P-1) and their masks
@@ -107,7 +110,12 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(
         const int tok = kept ? (my_idx & 63) : eos;
         const int par = kept ? (my_idx >> 6) : lane;
         // decoder.py:213-218: at the last step every kept hypothesis gets an <eos> appended, one that ends in <eos> included
-        const bool ended = kept && (tok == eos || step == maxlen - 1);
+        int last = maxlen - 1;
+        if constexpr (LEN) {
+            const int l = clip_steps[n];
+            last = (l < 1 ? 1 : (l > maxlen ? maxlen : l)) - 1;
+        }
+        const bool ended = kept && (tok == eos || step == last);
         const unsigned long long em = __ballot(ended);
         const int cnt = step == 0 ? 0 : end_count[n];
         const long cap = (long)W * maxlen;
@@ -155,13 +163,14 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(
         for (int r = 0; r < W; ++r) dh_next_row(x_next + (slot0 + r) * DH_D, emb, s_tok[r], pe, step + 1, emb_scale);
 }
 
-// the checks and the launch of sbl_beam_tail and sbl_beam_tail_lex (trie_mask != NULL)
+// the checks and the launch of sbl_beam_tail, sbl_beam_tail_lex (trie_mask != NULL) and sbl_beam_tail_len (clip_steps != NULL)
 static int beam_tail_launch(const char* name, const float* y, long ldy, const float* w, const float* log_prior, float* score,
                             int32_t* last_tok, const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok,
                             int32_t* hist_par, float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref,
                             int32_t* end_count, int step, int maxlen, int eos, const float* emb, const float* pe, int pe_rows,
                             float emb_scale, float* x_next, int N, int W, int V, int D, const int64_t* trie_mask,
-                            const int32_t* trie_first, int P, int32_t* node, sbl_stream_t stream) {
+                            const int32_t* trie_first, int P, int32_t* node, sbl_stream_t stream,
+                            const int32_t* clip_steps = nullptr) {
     SBL_REQUIRE(D == DH_D, "%s: D=%d (built for %d)", name, D, DH_D);
     SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "%s: V=%d (V <= %d)", name, V, DH_MAX_V);
     SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "%s: beam W=%d outside 1..%d", name, W, DH_MAX_W);
@@ -177,11 +186,13 @@ static int beam_tail_launch(const char* name, const float* y, long ldy, const fl
     SBL_REQUIRE(sbl_aligned16(y) && sbl_aligned16(w), "%s: unaligned", name);
 #define BEAM_TAIL_ARGS                                                                                                          \
     y, ldy, w, log_prior, score, last_tok, anc_old, anc_new, lda, hist_tok, hist_par, hist_score, hist_flag, end_score, end_ref, \
-        end_count, step, maxlen, eos, emb, pe, emb_scale, x_next, W, V, trie_mask, trie_first, P, node
-    if (trie_mask)
-        hipLaunchKernelGGL(beam_tail_kernel<true>, dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
+        end_count, step, maxlen, eos, emb, pe, emb_scale, x_next, W, V, trie_mask, trie_first, P, node, clip_steps
+    if (clip_steps)
+        hipLaunchKernelGGL((beam_tail_kernel<false, true>), dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
+    else if (trie_mask)
+        hipLaunchKernelGGL((beam_tail_kernel<true>), dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
     else
-        hipLaunchKernelGGL(beam_tail_kernel<false>, dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
+        hipLaunchKernelGGL((beam_tail_kernel<false>), dim3(N), dim3(256), 0, (hipStream_t)stream, BEAM_TAIL_ARGS);
 #undef BEAM_TAIL_ARGS
     SBL_LAUNCH_CHECK(name);
     return 0;
@@ -210,14 +221,28 @@ extern "C" int sbl_beam_tail_lex(const float* y, long ldy, const float* w, const
                             x_next, N, W, V, D, trie_mask, trie_first, P, node, stream);
 }
 
+extern "C" int sbl_beam_tail_len(const float* y, long ldy, const float* w, const float* log_prior, float* score, int32_t* last_tok,
+                                 const int32_t* anc_old, int32_t* anc_new, long lda, int32_t* hist_tok, int32_t* hist_par,
+                                 float* hist_score, int32_t* hist_flag, float* end_score, int32_t* end_ref, int32_t* end_count,
+                                 int step, int maxlen, int eos, const float* emb, const float* pe, int pe_rows, float emb_scale,
+                                 float* x_next, int N, int W, int V, int D, const int32_t* clip_steps, sbl_stream_t stream) {
+    SBL_REQUIRE(clip_steps, "sbl_beam_tail_len: clip_steps is NULL");
+    return beam_tail_launch("sbl_beam_tail_len", y, ldy, w, log_prior, score, last_tok, anc_old, anc_new, lda, hist_tok, hist_par,
+                            hist_score, hist_flag, end_score, end_ref, end_count, step, maxlen, eos, emb, pe, pe_rows, emb_scale,
+                            x_next, N, W, V, D, nullptr, nullptr, 0, nullptr, stream, clip_steps);
+}
+
 // ------------------------------------------------------------------ n-best and back-trace: LRW1000/transformer/decoder.py:240-245
 // grid N, one wavefront.  The ended list of a clip has at most W * maxlen <= 1024 entries = 16 per lane; nbest rounds of
 // arg-max with the lower list position on equal scores are the stable descending sort truncated to nbest.
+// LEN (sbl_beam_finish_len): the step whose hypotheses carry the appended <eos> is the clip's own last step.
+template <bool LEN>
 __global__ __launch_bounds__(64) void beam_finish_kernel(const float* __restrict__ end_score, const int32_t* __restrict__ end_ref,
                                                          const int32_t* __restrict__ end_count, const int32_t* __restrict__ hist_tok,
                                                          const int32_t* __restrict__ hist_par, int64_t* __restrict__ yseq,
                                                          int32_t* __restrict__ lengths, float* __restrict__ scores,
-                                                         int32_t* __restrict__ n_hyps, int W, int maxlen, int nbest, int sos, int eos) {
+                                                         int32_t* __restrict__ n_hyps, int W, int maxlen, int nbest, int sos, int eos,
+                                                         const int32_t* __restrict__ clip_steps) {
     const int lane = threadIdx.x;
     const int n = blockIdx.x;
     const int cap = W * maxlen;
@@ -257,7 +282,13 @@ __global__ __launch_bounds__(64) void beam_finish_kernel(const float* __restrict
     const int ref = end_ref[(long)n * cap + my_e];
     int s = ref / W, r = ref - s * W;
     s = s < 0 ? 0 : (s >= maxlen ? maxlen - 1 : s);
-    lengths[n * nbest + lane] = s == maxlen - 1 ? maxlen + 2 : s + 2;      // <sos> + s+1 tokens (+ the last step's <eos>)
+    if constexpr (LEN) {
+        const int l = clip_steps[n];
+        const int last = (l < 1 ? 1 : (l > maxlen ? maxlen : l)) - 1;
+        lengths[n * nbest + lane] = s == last ? s + 3 : s + 2;
+    } else {
+        lengths[n * nbest + lane] = s == maxlen - 1 ? maxlen + 2 : s + 2;      // <sos> + s+1 tokens (+ the last step's <eos>)
+    }
     scores[n * nbest + lane] = my_sc;
     row[0] = sos;
     for (int t = s; t >= 0; --t) {
@@ -268,17 +299,37 @@ __global__ __launch_bounds__(64) void beam_finish_kernel(const float* __restrict
     }
 }
 
+static int beam_finish_launch(const char* name, const float* end_score, const int32_t* end_ref, const int32_t* end_count,
+                              const int32_t* hist_tok, const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores,
+                              int32_t* n_hyps, int N, int W, int maxlen, int nbest, int sos, int eos, const int32_t* clip_steps,
+                              sbl_stream_t stream) {
+    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "%s: beam W=%d outside 1..%d", name, W, DH_MAX_W);
+    SBL_REQUIRE(nbest >= 1 && nbest <= BEAM_MAX_NBEST, "%s: nbest=%d outside 1..%d", name, nbest, BEAM_MAX_NBEST);
+    SBL_REQUIRE(maxlen >= 1 && maxlen <= BEAM_MAX_LEN, "%s: maxlen=%d outside 1..%d", name, maxlen, BEAM_MAX_LEN);
+    SBL_REQUIRE(N > 0, "%s: N=%d", name, N);
+    SBL_REQUIRE(end_score && end_ref && end_count && hist_tok && hist_par && yseq && lengths && scores && n_hyps, "%s: null pointer",
+                name);
+    if (clip_steps)
+        hipLaunchKernelGGL(beam_finish_kernel<true>, dim3(N), dim3(64), 0, (hipStream_t)stream, end_score, end_ref, end_count, hist_tok,
+                           hist_par, yseq, lengths, scores, n_hyps, W, maxlen, nbest, sos, eos, clip_steps);
+    else
+        hipLaunchKernelGGL(beam_finish_kernel<false>, dim3(N), dim3(64), 0, (hipStream_t)stream, end_score, end_ref, end_count, hist_tok,
+                           hist_par, yseq, lengths, scores, n_hyps, W, maxlen, nbest, sos, eos, clip_steps);
+    SBL_LAUNCH_CHECK(name);
+    return 0;
+}
+
 extern "C" int sbl_beam_finish(const float* end_score, const int32_t* end_ref, const int32_t* end_count, const int32_t* hist_tok,
                                const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N, int W,
                                int maxlen, int nbest, int sos, int eos, sbl_stream_t stream) {
-    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_beam_finish: beam W=%d outside 1..%d", W, DH_MAX_W);
-    SBL_REQUIRE(nbest >= 1 && nbest <= BEAM_MAX_NBEST, "sbl_beam_finish: nbest=%d outside 1..%d", nbest, BEAM_MAX_NBEST);
-    SBL_REQUIRE(maxlen >= 1 && maxlen <= BEAM_MAX_LEN, "sbl_beam_finish: maxlen=%d outside 1..%d", maxlen, BEAM_MAX_LEN);
-    SBL_REQUIRE(N > 0, "sbl_beam_finish: N=%d", N);
-    SBL_REQUIRE(end_score && end_ref && end_count && hist_tok && hist_par && yseq && lengths && scores && n_hyps,
-                "sbl_beam_finish: null pointer");
-    hipLaunchKernelGGL(beam_finish_kernel, dim3(N), dim3(64), 0, (hipStream_t)stream, end_score, end_ref, end_count, hist_tok,
-                       hist_par, yseq, lengths, scores, n_hyps, W, maxlen, nbest, sos, eos);
-    SBL_LAUNCH_CHECK("sbl_beam_finish");
-    return 0;
+    return beam_finish_launch("sbl_beam_finish", end_score, end_ref, end_count, hist_tok, hist_par, yseq, lengths, scores, n_hyps, N, W,
+                              maxlen, nbest, sos, eos, nullptr, stream);
+}
+
+extern "C" int sbl_beam_finish_len(const float* end_score, const int32_t* end_ref, const int32_t* end_count, const int32_t* hist_tok,
+                                   const int32_t* hist_par, int64_t* yseq, int32_t* lengths, float* scores, int32_t* n_hyps, int N,
+                                   int W, int maxlen, int nbest, int sos, int eos, const int32_t* clip_steps, sbl_stream_t stream) {
+    SBL_REQUIRE(clip_steps, "sbl_beam_finish_len: clip_steps is NULL");
+    return beam_finish_launch("sbl_beam_finish_len", end_score, end_ref, end_count, hist_tok, hist_par, yseq, lengths, scores, n_hyps, N,
+                              W, maxlen, nbest, sos, eos, clip_steps, stream);
 }

@@ -17,6 +17,8 @@
 //     of the hypothesis now living in slot b - and the SLOTS instantiation looks the cache slot of key j up there (score and
 //     value pass).  Rows j < n_prev of every slot were written at step j and are never written again, so no launch reads a
 //     row that the same launch writes.
+//     The LEN instantiations (the `_len` entries, cross-attention over a padded batch of ragged clips) take a key count per
+//     K / V entry in place of the launch's one n_prev; the instantiations without it compile as they did before LEN existed.
 //   * decode_tail_kernel: one workgroup per clip: the bias-free projection to V <= 64 classes (each wave takes every
 //     fourth class, lanes along the 512 features, coalesced), arg-max with the lowest index on ties, the token appended
 //     to ys[:, step + 1], and the next step's input row emb[token] * scale + pe[step + 1] - tokens never visit the host.
@@ -90,14 +92,25 @@ extern "C" int sbl_embed_scale_bwd(const int64_t* tok, long ldt, const float* dy
 // rows of a cache.  Without SLOTS row b owns cache b.  With SLOTS, append: key j is row j of cache anc[b][j] (clamped to
 // 0 .. S-1, so whatever the table holds the reads stay inside the S caches); no append (cross-attention): slot b reads the
 // hoisted cache of clip b / W, of which there are S / W.
-template <bool SLOTS>
+template <bool SLOTS, bool LEN = false>
 __global__ __launch_bounds__(64) void step_attn_kernel(const float* __restrict__ q, long ldq, const float* __restrict__ k_new,
                                                        const float* __restrict__ v_new, long ldn, float* k_cache, float* v_cache,
                                                        long ldc, int Lcap, const int32_t* __restrict__ anc, long lda,
-                                                       float* __restrict__ o, long ldo, int S, int W, int n_prev, int append,
+                                                       float* __restrict__ o, long ldo, int S, int W, int n_keys, int append_arg,
                                                        float scale) {
     const int lane = threadIdx.x;
     const int h = blockIdx.x, b = blockIdx.y;
+    // LEN (the `_len` entries; cross-attention only, so the ancestry argument is free and carries the key counts): the
+    // entry's count, clamped to 0 .. n_keys, takes the place of the number of cached keys.  One wavefront per (row, head),
+    // so the count is wavefront-uniform, and every load below is predicated on it as it is on n_keys without LEN.
+    int n_prev = n_keys;
+    const int append = LEN ? 0 : append_arg;
+    if constexpr (LEN) {
+        const int32_t* kv_len = anc;      // one count per K / V entry: B of them, or S / W with SLOTS (the host passes them here)
+        int l = kv_len[SLOTS ? b / W : b];
+        l = l < 0 ? 0 : l;
+        n_prev = __builtin_amdgcn_readfirstlane(l < n_keys ? l : n_keys);
+    }
     const long col = (long)h * 64;
     const float* qrow = q + (long)b * ldq + col;
     // Row 0 of cache b at this head's columns: without SLOTS every cache address is formed from these, with SLOTS from the
@@ -153,10 +166,14 @@ __global__ __launch_bounds__(64) void step_attn_kernel(const float* __restrict__
     o[(long)b * ldo + col + lane] = acc;
 }
 
-// the checks and the launch behind both entry points; `name` is the entry's, S rows, anc != nullptr only with slots
+// the checks and the launch behind the entry points; `name` is the entry's, S rows, anc != nullptr only with slots.  len: the
+// `_len` entries, whose key counts kv_len travel in the kernel's ancestry argument (append = 0 leaves it unused).
 static int step_attn_launch(const char* name, bool slots, const float* q, long ldq, const float* k_new, const float* v_new, long ldn,
                             float* k_cache, float* v_cache, long ldc, int Lcap, const int32_t* anc, long lda, float* o, long ldo,
-                            int S, int W, int H, int n_prev, int append, float scale, sbl_stream_t stream) {
+                            int S, int W, int H, int n_prev, int append, float scale, sbl_stream_t stream, bool len = false,
+                            const int32_t* kv_len = nullptr) {
+    SBL_REQUIRE(!len || kv_len, "%s: kv_len is NULL", name);
+    SBL_REQUIRE(!len || append == 0, "%s: append=%d (key counts go with the cross-attention, append = 0)", name, append);
     SBL_REQUIRE(Lcap >= 1 && Lcap <= DEC_MAX_KEYS, "%s: Lcap=%d outside 1..%d", name, Lcap, DEC_MAX_KEYS);
     SBL_REQUIRE(append == 0 || append == 1, "%s: append=%d", name, append);
     SBL_REQUIRE(n_prev >= 0 && n_prev + append >= 1 && n_prev + append <= Lcap, "%s: %d cached keys (+%d) do not fit Lcap=%d", name,
@@ -167,8 +184,13 @@ static int step_attn_launch(const char* name, bool slots, const float* q, long l
                 n_prev);
     SBL_REQUIRE(ldq >= (long)H * 64 && ldc >= (long)H * 64 && ldo >= (long)H * 64, "%s: row stride below H*64", name);
     SBL_REQUIRE(ldq % 4 == 0 && ldc % 4 == 0 && sbl_aligned16(q) && sbl_aligned16(k_cache), "%s: unaligned", name);
-    hipLaunchKernelGGL(slots ? step_attn_kernel<true> : step_attn_kernel<false>, dim3(H, S), dim3(64), 0, (hipStream_t)stream, q, ldq,
-                       k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, anc, lda, o, ldo, S, W, n_prev, append, scale);
+    if (len)
+        hipLaunchKernelGGL((slots ? step_attn_kernel<true, true> : step_attn_kernel<false, true>), dim3(H, S), dim3(64), 0,
+                           (hipStream_t)stream, q, ldq, k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, kv_len, 0L, o, ldo, S, W, n_prev,
+                           0, scale);
+    else
+        hipLaunchKernelGGL(slots ? step_attn_kernel<true> : step_attn_kernel<false>, dim3(H, S), dim3(64), 0, (hipStream_t)stream, q,
+                           ldq, k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, anc, lda, o, ldo, S, W, n_prev, append, scale);
     SBL_LAUNCH_CHECK(name);
     return 0;
 }
@@ -188,6 +210,25 @@ extern "C" int sbl_beam_attn_step(const float* q, long ldq, const float* k_new, 
     SBL_REQUIRE(S > 0 && H > 0 && S <= 65535 && S % W == 0, "sbl_beam_attn_step: S=%d H=%d (S a multiple of W=%d)", S, H, W);
     return step_attn_launch("sbl_beam_attn_step", true, q, ldq, k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, anc, lda, o, ldo, S,
                             W, H, n_prev, append, scale, stream);
+}
+
+// the same two entries with a key count per K/V entry (cross-attention over a padded batch of ragged clips)
+extern "C" int sbl_decode_attn_step_len(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                                        float* v_cache, long ldc, int Lcap, float* o, long ldo, int B, int H, int n_prev,
+                                        int append, float scale, const int32_t* kv_len, sbl_stream_t stream) {
+    SBL_REQUIRE(B > 0 && H > 0 && B <= 65535, "sbl_decode_attn_step_len: B=%d H=%d", B, H);
+    return step_attn_launch("sbl_decode_attn_step_len", false, q, ldq, k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, nullptr, 0, o,
+                            ldo, B, 1, H, n_prev, append, scale, stream, true, kv_len);
+}
+
+extern "C" int sbl_beam_attn_step_len(const float* q, long ldq, const float* k_new, const float* v_new, long ldn, float* k_cache,
+                                      float* v_cache, long ldc, int Lcap, const int32_t* anc, long lda, float* o, long ldo, int S,
+                                      int W, int H, int n_prev, int append, float scale, const int32_t* kv_len,
+                                      sbl_stream_t stream) {
+    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_beam_attn_step_len: beam W=%d outside 1..%d", W, DH_MAX_W);
+    SBL_REQUIRE(S > 0 && H > 0 && S <= 65535 && S % W == 0, "sbl_beam_attn_step_len: S=%d H=%d (S a multiple of W=%d)", S, H, W);
+    return step_attn_launch("sbl_beam_attn_step_len", true, q, ldq, k_new, v_new, ldn, k_cache, v_cache, ldc, Lcap, anc, lda, o, ldo,
+                            S, W, H, n_prev, append, scale, stream, true, kv_len);
 }
 
 // ------------------------------------------------------------------ decode tail: LRW/transformer/decoder.py:166-171 + :154-156

@@ -2032,8 +2032,11 @@ class EmbedScalePEFn(torch.autograd.Function):
         return None, demb_ret, None, None
 
 
-def _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale):
-    """The stride checks and the call behind decode_attn_step (W = None: every row owns its cache) and beam_attn_step."""
+def _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale, kv_len=None):
+    """The stride checks and the call behind decode_attn_step (W = None: every row owns its cache) and beam_attn_step.
+    kv_len: None, or the device int32 key counts of the K/V entries (cross-attention only): the `_len` entries."""
+    if kv_len is not None and append:
+        raise _lib.SblHipError("decode / beam_attn_step: key counts go with the cross-attention (append = 0) only")
     S = q.size(0)
     ldc = k_cache.stride(-2)
     nc = S if append or W is None else S // W
@@ -2043,22 +2046,28 @@ def _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, 
     if append:
         assert k_new.stride(0) == v_new.stride(0) and k_new.stride(1) == 1 and v_new.stride(1) == 1
     head = (_p(q), q.stride(0), _p(k_new), _p(v_new), k_new.stride(0) if append else 0, _p(k_cache), _p(v_cache), ldc, Lcap)
-    tail = (H, int(n_prev), int(bool(append)), scale, _s())
+    tail = (H, int(n_prev), int(bool(append)), scale)
+    name, end = ("sbl_decode_attn_step", "sbl_beam_attn_step"), (_s(),)
+    if kv_len is not None:
+        assert kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.shape == (nc,) and kv_len.is_contiguous()
+        name, end = (name[0] + "_len", name[1] + "_len"), (_p(kv_len), _s())
     if W is None:
-        call("sbl_decode_attn_step", *head, _p(out), out.stride(0), S, *tail)
+        call(name[0], *head, _p(out), out.stride(0), S, *tail, *end)
     else:
         if append:
             assert anc.dtype == torch.int32 and anc.dim() == 2 and anc.size(0) == S and anc.stride(1) == 1
-        call("sbl_beam_attn_step", *head, _p(anc) if append else None, anc.stride(0) if append else 0, _p(out), out.stride(0), S,
-             int(W), *tail)
+        call(name[1], *head, _p(anc) if append else None, anc.stride(0) if append else 0, _p(out), out.stride(0), S,
+             int(W), *tail, *end)
     return out
 
 
-def decode_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append, scale=0.125):
+def decode_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append, scale=0.125, kv_len=None):
     """One (clip, head) wavefront each: the single new query row attends to the cache (include/sbl_hip.h,
     sbl_decode_attn_step).  q / k_new / v_new / out: (B, H*64) row views (column slices of wider buffers are fine);
-    k_cache / v_cache: views whose first element is row 0 of clip 0, row stride .stride(-2), batch stride Lcap rows."""
-    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, None, out, None, H, n_prev, append, scale)
+    k_cache / v_cache: views whose first element is row 0 of clip 0, row stride .stride(-2), batch stride Lcap rows.
+    kv_len (append = 0 only): None, or a device int32 (B,) tensor - clip b then sees the keys j < min(max(kv_len[b], 0),
+    n_prev) and a clip without a visible key gets o = 0 (sbl_decode_attn_step_len)."""
+    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, None, out, None, H, n_prev, append, scale, kv_len)
 
 
 def decode_tail(y, w, ys, step, emb, pe, emb_scale, x_next=None, logits=None):
@@ -2072,11 +2081,12 @@ def decode_tail(y, w, ys, step, emb, pe, emb_scale, x_next=None, logits=None):
          int(step), _p(emb), _p(pe), pe.size(0), emb_scale, _p(x_next), B, V, D, _s())
 
 
-def beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale=0.125):
+def beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale=0.125, kv_len=None):
     """decode_attn_step for beam slots (include/sbl_hip.h, sbl_beam_attn_step): q / k_new / v_new / out are (S, H*64) row views,
     S = clips * W.  append: k_cache / v_cache (S, Lcap, H*64) and anc (S, >= n_prev) int32 names the cache slot of every key;
-    otherwise (cross-attention) k_cache / v_cache hold S / W clips and anc is None."""
-    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale)
+    otherwise (cross-attention) k_cache / v_cache hold S / W clips and anc is None.  kv_len (append = 0 only): None, or the
+    device int32 (S / W,) key counts of the clips (sbl_beam_attn_step_len)."""
+    return _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, append, scale, kv_len)
 
 
 class BeamState(object):
@@ -2108,13 +2118,22 @@ class BeamState(object):
         return self.hist_tok, self.hist_par, self.hist_score, self.hist_flag
 
 
-def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None, trie=None):
+def _clip_steps(clip_steps, N):
+    assert clip_steps.is_cuda and clip_steps.dtype == torch.int32 and clip_steps.shape == (N,) and clip_steps.is_contiguous()
+    return _p(clip_steps)
+
+
+def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None, trie=None, clip_steps=None):
     """Tail of beam step `step` in one launch (sbl_beam_tail) on the rows y (N*W, 512): the best W candidates of every clip
     into the BeamState `st` (ancestry buffer step % 2 is read, the other one written), x_next = the next input rows.
     trie: None, or the (mask, first, word) tables of Lexicon.trie() - then the launch is sbl_beam_tail_lex, a candidate exists
-    only where the slot's node st.node allows its token, and st.node is updated in place (st needs lex=True)."""
+    only where the slot's node st.node allows its token, and st.node is updated in place (st needs lex=True).
+    clip_steps (without a trie): None, or the device int32 (N,) step counts of the clips - every kept hypothesis of clip n then
+    ends at step clamp(clip_steps[n], 1, maxlen) - 1 (sbl_beam_tail_len)."""
     S, D = y.shape
     V = w.size(0)
+    if trie is not None and clip_steps is not None:
+        raise _lib.SblHipError("beam_tail: the lexicon search's step count does not depend on the clip (no clip_steps with a trie)")
     assert S == st.N * st.W and y.stride(1) == 1 and w.is_contiguous()
     assert log_prior is None or (log_prior.dtype == torch.float32 and log_prior.shape == (V, V) and log_prior.is_contiguous())
     assert x_next is None or (x_next.is_contiguous() and x_next.shape == (S, D) and pe.is_contiguous() and emb.is_contiguous())
@@ -2122,6 +2141,9 @@ def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None
             _p(st.anc[1 - step % 2]), st.anc.stride(1), _p(st.hist_tok), _p(st.hist_par), _p(st.hist_score), _p(st.hist_flag),
             _p(st.end_score), _p(st.end_ref), _p(st.end_count), int(step), st.maxlen, int(eos_id), _p(emb), _p(pe), pe.size(0),
             emb_scale, _p(x_next), st.N, st.W, V, D)
+    if clip_steps is not None:
+        call("sbl_beam_tail_len", *args, _clip_steps(clip_steps, st.N), _s())
+        return
     if trie is None:
         call("sbl_beam_tail", *args, _s())
         return
@@ -2132,15 +2154,21 @@ def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None
     call("sbl_beam_tail_lex", *args, _p(mask), _p(first), mask.numel(), _p(st.node), _s())
 
 
-def beam_finish(st, nbest, eos_id):
-    """(yseq (N, nbest, maxlen+2) int64, lengths (N, nbest) int32, scores (N, nbest), n_hyps (N) int32): sbl_beam_finish."""
+def beam_finish(st, nbest, eos_id, clip_steps=None):
+    """(yseq (N, nbest, maxlen+2) int64, lengths (N, nbest) int32, scores (N, nbest), n_hyps (N) int32): sbl_beam_finish.
+    clip_steps: None, or the array beam_tail was given - a hypothesis that ended at clip n's last step then has length
+    clip_steps[n] + 2 (sbl_beam_finish_len)."""
     dev = st.score.device
     yseq = torch.empty(st.N, nbest, st.maxlen + 2, dtype=torch.int64, device=dev)
     lengths = torch.empty(st.N, nbest, dtype=torch.int32, device=dev)
     scores = torch.empty(st.N, nbest, dtype=torch.float32, device=dev)
     n_hyps = torch.empty(st.N, dtype=torch.int32, device=dev)
-    call("sbl_beam_finish", _p(st.end_score), _p(st.end_ref), _p(st.end_count), _p(st.hist_tok), _p(st.hist_par), _p(yseq),
-         _p(lengths), _p(scores), _p(n_hyps), st.N, st.W, st.maxlen, int(nbest), int(st.sos_id), int(eos_id), _s())
+    args = (_p(st.end_score), _p(st.end_ref), _p(st.end_count), _p(st.hist_tok), _p(st.hist_par), _p(yseq), _p(lengths), _p(scores),
+            _p(n_hyps), st.N, st.W, st.maxlen, int(nbest), int(st.sos_id), int(eos_id))
+    if clip_steps is None:
+        call("sbl_beam_finish", *args, _s())
+    else:
+        call("sbl_beam_finish_len", *args, _clip_steps(clip_steps, st.N), _s())
     return yseq, lengths, scores, n_hyps
 
 

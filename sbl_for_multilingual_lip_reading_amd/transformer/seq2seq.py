@@ -15,6 +15,7 @@ import torch.nn as nn
 from ._env import _lib, config, ops
 from .decoder import DecoderLayer
 from .module import PositionalEncoding
+from .transformer import Transformer
 from .utils import get_attn_pad_mask
 from .video_frontend import Lipreading
 
@@ -148,7 +149,8 @@ class Seq2SeqDecoder(nn.Module):
         non_pad_mask = (~pad).float().unsqueeze(-1)
         future = torch.ones((L, L), dtype=torch.bool, device=enc.device).triu(1)
         slf_attn_mask = pad.unsqueeze(1) | future.unsqueeze(0)                   # key-pad OR causal, (N, L, L)
-        if all(int(n) >= Ti for n in encoder_input_lengths):
+        on_device = isinstance(encoder_input_lengths, torch.Tensor) and encoder_input_lengths.is_cuda      # never read back
+        if not on_device and all(int(n) >= Ti for n in encoder_input_lengths):
             dec_enc_attn_mask = None                                              # full lengths: the mask is a no-op
         else:
             dec_enc_attn_mask = get_attn_pad_mask(enc, encoder_input_lengths, L)
@@ -167,20 +169,43 @@ class Seq2SeqDecoder(nn.Module):
         return pred, ys_out
 
     # ------------------------------------------------------------------ greedy decode
-    def recognize_beam(self, encoder_outputs, char_list=None, args=None, cached=True):
+    def recognize_beam(self, encoder_outputs, char_list=None, args=None, cached=True, encoder_input_lengths=None):
         """Greedy decode of maxlen = Ti steps (decoder.py:138-176; char_list / args are accepted and unused, as there).
         Returns ys int64 (N, Ti + 1), column 0 is <sos>.  cached=True: one new row per clip and step against per-layer K/V
         caches; cached=False: the reference's loop, the whole prefix re-run at every step through the teacher-forced building
-        blocks (the statement the cached path is tested against).  No host sync either way."""
+        blocks (the statement the cached path is tested against).  No host sync either way.
+        encoder_input_lengths (here and in every decode method below): None, or the clips' frame counts l - N ints or a device
+        int32 (N,) tensor, which is never read on the host.  Clip n then attends to the encoder rows t < l_n only and decodes
+        as the reference decodes it alone, cut to l_n frames: ys[n, 1..l_n] are its l_n tokens and ys[n, l_n+1..] is eos_id
+        (all Ti steps are still issued; the columns behind l_n are overwritten by one masked fill on the device)."""
         self._check_encoder(encoder_outputs)
+        lens = self._kv_len(encoder_input_lengths, encoder_outputs)
         self._fuse()
         with torch.no_grad():
-            return self._greedy_cached(encoder_outputs) if cached else self._greedy_recompute(encoder_outputs)
+            ys = self._greedy_cached(encoder_outputs, lens) if cached else self._greedy_recompute(encoder_outputs, lens)
+            if lens is not None:
+                T = encoder_outputs.size(1)
+                behind = torch.arange(T + 1, device=ys.device).unsqueeze(0) > lens.clamp(1, T).unsqueeze(1)
+                ys.masked_fill_(behind, self.eos_id)
+            return ys
+
+    @staticmethod
+    def _kv_len(encoder_input_lengths, encoder_outputs):
+        """None, or the lengths as the device int32 (N,) tensor the `_len` kernels read (a host sequence is copied once)."""
+        lens = encoder_input_lengths
+        if lens is None:
+            return None
+        if not (isinstance(lens, torch.Tensor) and lens.is_cuda):
+            lens = torch.as_tensor(lens, dtype=torch.int32).to(encoder_outputs.device)
+        if lens.dtype != torch.int32 or lens.shape != (encoder_outputs.size(0),) or not lens.is_contiguous():
+            raise _lib.SblHipError("encoder_input_lengths: a contiguous int32 (%d,) tensor, got %s %s"
+                                   % (encoder_outputs.size(0), lens.dtype, tuple(lens.shape)))
+        return lens
 
     def _new_ys(self, enc):
         return torch.full((enc.size(0), enc.size(1) + 1), self.sos_id, dtype=torch.long, device=enc.device)
 
-    def _greedy_recompute(self, enc):
+    def _greedy_recompute(self, enc, lens=None):
         N, T, _ = enc.shape
         kv = [lay.enc_attn.project_kv(enc) for lay in self.layer_stack]       # step-invariant
         ys = self._new_ys(enc)
@@ -188,17 +213,20 @@ class Seq2SeqDecoder(nn.Module):
         for i in range(T):
             x = ops.EmbedScalePEFn.apply(ys[:, :i + 1], emb, pe, float(self.x_logit_scale))
             x = ops.dropout(x, self.dropout.p, self.training)
+            # ragged clips: the explicit key mask of the teacher-forced pass, built on the device from the lengths tensor
+            cross_mask = None if lens is None else get_attn_pad_mask(enc, lens, i + 1)
             for lay, kv_l in zip(self.layer_stack, kv):
-                x, _, _ = lay(x, enc, non_pad_mask=None, slf_attn_mask='causal', dec_enc_attn_mask=None, enc_kv=kv_l)
+                x, _, _ = lay(x, enc, non_pad_mask=None, slf_attn_mask='causal', dec_enc_attn_mask=cross_mask, enc_kv=kv_l)
             ops.argmax_select(ops.linear(x[:, -1], w), None, ys, i, 1)
         return ys
 
-    def _cached_steps(self, enc, rows, steps, tok0, attn, tail):
+    def _cached_steps(self, enc, rows, steps, tok0, attn, tail, kv_len=None):
         """The KV-cached step loop under the greedy decode and the beam search: `rows` rows per step (the clips, or their
         beam slots) for `steps` steps.  One GEMM for the cross-attention K / V of all layers, the first input row from the
         (rows, >= 1) token table tok0, then per step and layer the 11 launches of DESIGN.md section 4.4 and the tail;
         nothing is read back.  attn(step, ...) takes the arguments of ops.decode_attn_step; tail(y, w, step, emb, pe, scale,
-        x_next) ends a step (x_next: the next step's input rows, None at the last one)."""
+        x_next) ends a step (x_next: the next step's input rows, None at the last one).  kv_len: None, or the clips' device
+        int32 key counts for every cross-attention (attn is then called with kv_len=)."""
         N, T, D = enc.shape
         layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
         nl, H = len(layers), self.n_head
@@ -223,18 +251,21 @@ class Seq2SeqDecoder(nn.Module):
                 attn(i, qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], steps, att, H, i, True)
                 ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
                 ops.lin_fwd(ca.inp, ya, q)
-                attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
+                if kv_len is None:
+                    attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
+                else:
+                    attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False, kv_len=kv_len)
                 ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
                 ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
                 cur = yc
             tail(cur, w, i, emb, pe, scale, x if i + 1 < steps else None)
 
-    def _greedy_cached(self, enc):
+    def _greedy_cached(self, enc, lens=None):
         if self.training and self.dropout.p > 0:
             raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
         ys = self._new_ys(enc)
-        self._cached_steps(enc, enc.size(0), enc.size(1), ys, lambda i, *a: ops.decode_attn_step(*a),
-                           lambda y, w, i, *head: ops.decode_tail(y, w, ys, i, *head))
+        self._cached_steps(enc, enc.size(0), enc.size(1), ys, lambda i, *a, **kw: ops.decode_attn_step(*a, **kw),
+                           lambda y, w, i, *head: ops.decode_tail(y, w, ys, i, *head), kv_len=lens)
         return ys
 
     # ------------------------------------------------------------------ beam search
@@ -246,7 +277,8 @@ class Seq2SeqDecoder(nn.Module):
         ended hypotheses come back, best first, without length normalisation -> BeamResult.  Exact ties, which the
         reference leaves to torch.topk: the lower parent slot first, then the lower token id.  A candidate of score -inf
         is never kept.  The step is KV-cached like the greedy decode (one new row per slot and step; the slots' caches are
-        followed through an ancestry table, never copied), eval-only, with no host read: capturable as one hipGraph."""
+        followed through an ancestry table, never copied), eval-only, with no host read: capturable as one hipGraph.
+        Ragged clips: beam_search_len."""
         return self.beam_search_lex(encoder_outputs, beam_size, nbest, decode_max_len, log_prior, None)
 
     def beam_search_lex(self, encoder_outputs, beam_size, nbest=1, decode_max_len=0, log_prior=None, lexicon=None):
@@ -254,9 +286,21 @@ class Seq2SeqDecoder(nn.Module):
         with this decoder's vocab / sos / eos; decode_max_len must then be 0): the search is restricted to the prefixes of
         the words (include/sbl_hip.h, sbl_beam_tail_lex).  Every hypothesis is a word, the n-best are distinct words, scores
         are not renormalised over the allowed tokens, and the search runs maxlen = longest word + 1 steps -> BeamResult.
-        None: the unconstrained search of beam_search, launch for launch."""
+        None: the unconstrained search of beam_search, launch for launch.  Ragged clips: beam_search_len."""
+        return self.beam_search_len(encoder_outputs, None, beam_size, nbest, decode_max_len, log_prior, lexicon)
+
+    def beam_search_len(self, encoder_outputs, encoder_input_lengths, beam_size, nbest=1, decode_max_len=0, log_prior=None,
+                        lexicon=None):
+        """beam_search / beam_search_lex over a padded batch of ragged clips (those two keep their signatures and call this
+        with encoder_input_lengths = None, which is their code path of before, launch for launch).
+        encoder_input_lengths (see recognize_beam): clip n attends to its l_n frames and, without a lexicon and with
+        decode_max_len == 0, its maxlen is l_n as for the reference alone - every kept hypothesis ends at step l_n - 1 with
+        length l_n + 2, and the clip has no live hypothesis from step l_n on (Ti steps are still issued).  With
+        decode_max_len != 0 or a lexicon the step count stays uniform (decode_max_len, as in the reference; the longest
+        word's + 1) and only the cross-attention learns the lengths."""
         enc = encoder_outputs
         self._check_encoder(enc)
+        lens = self._kv_len(encoder_input_lengths, enc)
         N, T, D = enc.shape
         W, nbest = int(beam_size), int(nbest)
         maxlen = int(decode_max_len) or T
@@ -286,28 +330,38 @@ class Seq2SeqDecoder(nn.Module):
             raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
         self._fuse()
         with torch.no_grad():
+            # the step count is per clip where the reference's maxlen is the clip's frame count
+            clip_steps = lens if lexicon is None and int(decode_max_len) == 0 else None
             return self._beam_cached(enc, W, nbest, maxlen, None if log_prior is None else log_prior.contiguous(),
-                                     None if lexicon is None else lexicon.trie())
+                                     None if lexicon is None else lexicon.trie(), lens, clip_steps)
 
-    def _beam_cached(self, enc, W, nbest, maxlen, log_prior, trie=None):
+    def _beam_cached(self, enc, W, nbest, maxlen, log_prior, trie=None, kv_len=None, clip_steps=None):
         S = enc.size(0) * W       # the W slots of a clip read the clip's cross-attention K / V
         st = ops.BeamState(enc.size(0), W, maxlen, self.sos_id, enc.device, lex=trie is not None)
         tok0 = torch.full((S, 1), self.sos_id, dtype=torch.long, device=enc.device)
 
-        def attn(i, q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append):
+        def attn(i, q, k_new, v_new, k_cache, v_cache, Lcap, out, H, n_prev, append, **kw):
             # row i of slot b's cache is written at step i by whatever hypothesis lives in b then
-            ops.beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, st.anc[i % 2] if append else None, out, W, H, n_prev, append)
+            ops.beam_attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, st.anc[i % 2] if append else None, out, W, H, n_prev, append,
+                               **kw)
 
         self._cached_steps(enc, S, maxlen, tok0, attn,
-                           lambda y, w, i, *head: ops.beam_tail(y, w, log_prior, st, i, self.eos_id, *head, trie=trie))
-        return BeamResult(*ops.beam_finish(st, nbest, self.eos_id), st.history())
+                           lambda y, w, i, *head: ops.beam_tail(y, w, log_prior, st, i, self.eos_id, *head, trie=trie,
+                                                                clip_steps=clip_steps), kv_len=kv_len)
+        return BeamResult(*ops.beam_finish(st, nbest, self.eos_id, clip_steps=clip_steps), st.history())
 
     def recognize_words(self, encoder_outputs, lexicon, beam_size=8, nbest=1, log_prior=None):
         """Closed-vocabulary decode in one pass: the beam search restricted to `lexicon` (beam_search_lex),
         then one lookup launch that names the n-best -> WordBeamResult.  The score of a word is the model's own
         log P(word, eos | clip) (+ log_prior's bigram terms); with a beam no narrower than the trie it is the exact ranking
         of the lexicon.  No host read: capturable as one hipGraph once lexicon.trie() has been built."""
-        res = self.beam_search_lex(encoder_outputs, beam_size, nbest, 0, log_prior, lexicon)
+        return self.recognize_words_len(encoder_outputs, None, lexicon, beam_size, nbest, log_prior)
+
+    def recognize_words_len(self, encoder_outputs, encoder_input_lengths, lexicon, beam_size=8, nbest=1, log_prior=None):
+        """recognize_words over a padded batch of ragged clips: every cross-attention of clip n sees its first
+        encoder_input_lengths[n] encoder rows only (None: recognize_words).  The step count is the longest word's + 1 for
+        every clip, as without lengths."""
+        res = self.beam_search_len(encoder_outputs, encoder_input_lengths, beam_size, nbest, 0, log_prior, lexicon)
         cand = lexicon.lookup(res.yseq)
         return WordBeamResult(cand[:, 0].long(), cand, res.scores, res.n_hyps, res.yseq)
 
@@ -332,64 +386,91 @@ class Seq2SeqTransformer(nn.Module):
         for w in [p for p in self.parameters() if p.dim() > 1]:
             nn.init.xavier_uniform_(w)
 
-    def _encode(self, frames):
-        """frames (N, T, H, W) grayscale or an ops.RawClips -> (encoder output (N, T, 512), full lengths)."""
+    def _encode(self, frames, input_lengths=None):
+        """frames (N, T, H, W) grayscale or an ops.RawClips -> (encoder output (N, T, 512), lengths).  input_lengths = None:
+        full lengths, as the reference passes them; else the host lengths of forward or the device int32 (N,) frame counts of
+        Transformer._lengths (inference) - the frames behind a clip's count must be all-zero frames, what the loader pads
+        with and what the stem's temporal zero padding gives the clip cut to its count; the encoder keeps them out of its
+        attention and zeroes their rows."""
         if not isinstance(frames, ops.RawClips):
             frames = frames.unsqueeze(1)
         feats = self.lipreading(frames)
-        lengths = [feats.size(1)] * feats.size(0)
+        lengths = [feats.size(1)] * feats.size(0) if input_lengths is None else input_lengths
         enc, *_ = self.encoder(feats, lengths)
         return enc, lengths
 
-    def forward(self, padded_input, padded_target):
+    _lengths = staticmethod(Transformer._lengths)
+
+    def forward(self, padded_input, padded_target, input_lengths=None):
         """padded_input (N, T, H, W) or ops.RawClips; padded_target (N, To <= 13), IGNORE_ID padded.
-        Returns (pred (N, 14, V), gold (N, 14))."""
-        enc, lengths = self._encode(padded_input)
+        Returns (pred (N, 14, V), gold (N, 14)).  input_lengths: None, or the clips' frame counts for the encoder's and the
+        decoder's key masks (both honour them under autograd; BatchNorm's batch statistics still run over the padded
+        frames, as in the reference)."""
+        enc, lengths = self._encode(padded_input, input_lengths)
         pred, gold, *_ = self.decoder(padded_target, enc, lengths)
         return pred, gold
 
-    def recognize(self, input, char_list=None, args=None, cached=True):
+    def recognize(self, input, char_list=None, args=None, cached=True, input_lengths=None):
         """Greedy decode of (N, T, H, W) crops (or ops.RawClips): ys int64 (N, T + 1).  In eval() under torch.no_grad() the
-        whole call is capturable as one hipGraph (no host sync, no host read of device data)."""
-        enc, _ = self._encode(input)
-        return self.decoder.recognize_beam(enc, char_list, args, cached=cached)
+        whole call is capturable as one hipGraph (no host sync, no host read of device data).
+        input_lengths (here and in every inference method below; gradients disabled): None, or the clips' frame counts (N
+        ints, checked before anything runs, or a device int32 (N,) tensor, never read on the host: Transformer._lengths).
+        Clip n then decodes as it would alone, cut to its first input_lengths[n] frames (its frames behind the count must be
+        all-zero frames), and ys[n] is eos_id behind its input_lengths[n] tokens."""
+        lens = self._lengths(input, input_lengths)
+        enc, _ = self._encode(input, lens)
+        return self.decoder.recognize_beam(enc, char_list, args, cached=cached, encoder_input_lengths=lens)
 
-    def recognize_nbest(self, input, char_list, args, log_prior=None):
+    def recognize_nbest(self, input, char_list, args, log_prior=None, input_lengths=None):
         """The beam search of LRW1000/transformer/transformer.py:46-72 for every clip of a batch: args.beam_size, args.nbest and
         args.decode_max_len as there (char_list is unused there too).  Returns, per clip, the reference's
         [{'score': float, 'yseq': [ids]}], best first.  One synchronisation, the read of the result."""
-        enc, _ = self._encode(input)
-        res = self.decoder.beam_search(enc, args.beam_size, args.nbest, args.decode_max_len, log_prior)
+        lens = self._lengths(input, input_lengths)
+        enc, _ = self._encode(input, lens)
+        res = self.decoder.beam_search_len(enc, lens, args.beam_size, args.nbest, args.decode_max_len, log_prior)
         host = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True).copy_(t, non_blocking=True) for t in res[:4]]
         torch.cuda.current_stream(res.yseq.device).synchronize()
         yseq, lengths, scores, n_hyps = (t.tolist() for t in host)
         return [[{'score': scores[n][k], 'yseq': yseq[n][k][:lengths[n][k]]} for k in range(n_hyps[n])] for n in range(len(yseq))]
 
-    def validate(self, padded_input, padded_target, meter, valid_rows=None, beam_size=None, log_prior=None):
+    def validate(self, padded_input, padded_target, meter, valid_rows=None, beam_size=None, log_prior=None, input_lengths=None):
         """One validation batch (the body of LRW/train.py:229-254): greedy decode, then score ys against the (N, To)
         IGNORE_ID-padded targets into `meter` (metrics.ErrorRateMeter) on the device; capturable like recognize.  Returns ys.
         With beam_size the decode is the beam search (log_prior as in Seq2SeqDecoder.beam_search) and ys its 1-best yseq
-        (N, T + 2), whose eos padding the scorer strips like the greedy rows' tail."""
+        (N, T + 2), whose eos padding the scorer strips like the greedy rows' tail.  With input_lengths a clip's row is eos
+        behind its own tokens, so it is scored as if decoded alone."""
         if beam_size is None:
-            ys = self.recognize(padded_input)
+            ys = self.recognize(padded_input, input_lengths=input_lengths)
         else:
-            ys = self.decoder.beam_search(self._encode(padded_input)[0], beam_size, 1, 0, log_prior).yseq[:, 0]
+            lens = self._lengths(padded_input, input_lengths)
+            ys = self.decoder.beam_search_len(self._encode(padded_input, lens)[0], lens, beam_size, 1, 0, log_prior).yseq[:, 0]
         meter.update_single(ys, padded_target, valid_rows=valid_rows)
         return ys
 
     def recognize_words(self, input, lexicon, beam_size=8, nbest=1, log_prior=None):
         """Closed-vocabulary decode of (N, T, H, W) crops (or ops.RawClips): Seq2SeqDecoder.recognize_words on the encoder
-        output -> WordBeamResult, the lexicon word of every clip with the distinct words of its n-best and their scores."""
-        enc, _ = self._encode(input)
-        return self.decoder.recognize_words(enc, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
+        output -> WordBeamResult, the lexicon word of every clip with the distinct words of its n-best and their scores.
+        Ragged clips: recognize_words_len."""
+        return self.recognize_words_len(input, None, lexicon, beam_size, nbest, log_prior)
+
+    def recognize_words_len(self, input, input_lengths, lexicon, beam_size=8, nbest=1, log_prior=None):
+        """recognize_words with the clips' frame counts (input_lengths as in recognize; None: recognize_words)."""
+        lens = self._lengths(input, input_lengths)
+        enc, _ = self._encode(input, lens)
+        return self.decoder.recognize_words_len(enc, lens, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
 
     def validate_words(self, padded_input, gold_word, lexicon, meter, valid_rows=None, beam_size=8, nbest=1, log_prior=None):
         """One validation batch of a closed-vocabulary benchmark: recognize_words, then `meter` (metrics.WordAccuracyMeter)
         counts the clips whose word is gold_word (N,) int64 - word indices into `lexicon`, as Lexicon.from_targets returns
         them - and those whose n-best holds it (the meter's n_in_shortlist).  No host read: in eval() under torch.no_grad()
         the call is capturable as one hipGraph, like validate; `valid_rows` (device int32[1]) masks the tail of a short last
-        batch.  Returns the WordBeamResult."""
-        res = self.recognize_words(padded_input, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
+        batch.  Returns the WordBeamResult.  Ragged clips: validate_words_len."""
+        return self.validate_words_len(padded_input, None, gold_word, lexicon, meter, valid_rows, beam_size, nbest, log_prior)
+
+    def validate_words_len(self, padded_input, input_lengths, gold_word, lexicon, meter, valid_rows=None, beam_size=8, nbest=1,
+                           log_prior=None):
+        """validate_words with the clips' frame counts (input_lengths as in recognize; None: validate_words)."""
+        res = self.recognize_words_len(padded_input, input_lengths, lexicon, beam_size=beam_size, nbest=nbest, log_prior=log_prior)
         meter.update(res, gold_word, valid_rows=valid_rows)
         return res
 
