@@ -838,59 +838,22 @@ extern "C" int sbl_attention_seg_fwd(const float* q, long ldq, const float* k, l
     return 0;
 }
 
-// Grouped cross-attention, inference only: sbl_attention_seg_fwd with Lk_fixed > 0 and no mask, where sequence b of the B reads
-// the key / value rows of entry b / kv_group (k / v hold B / kv_group entries of Lk_fixed rows) and no probabilities are
-// written.  Same kernels, same size dispatch and same arithmetic per sequence as sbl_attention_seg_fwd on K/V repeated
-// kv_group-fold, without the repeated copy.
-extern "C" int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
-                                             long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
-                                             float scale, float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream) {
+// The launcher behind sbl_attention_seg_grouped_fwd and sbl_attention_seg_len_fwd: the requirements they share, refused under the
+// entry's `name`, then the size dispatch of sbl_attention_seg_fwd on the host-known shapes alone.  small_kernel / wg_kernel: the
+// entry's one-wavefront and workgroup kernels.  kv_len: nothing (grouped), or the one device pointer that the `len` kernels take
+// behind kv_group; it is never read here.
+template <class SmallKernel, class WgKernel, class... KvLen>
+static int at_grouped_launch(const char* name, SmallKernel small_kernel, WgKernel wg_kernel, const float* q, long ldq, const float* k,
+                             long ldk, const float* v, long ldv, float* o, long ldo, int B, int H, const int* seg_L, int nseg,
+                             int Lk_fixed, int kv_group, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
+                             sbl_stream_t stream, KvLen... kv_len) {
     SegDesc d;
-    SBL_REQUIRE(sbl_make_segs(d, seg_L, nseg, B, H, Lk_fixed) > 0, "sbl_attention_seg_grouped_fwd: bad segment list (nseg=%d, 1..%d)", nseg, SBL_MAX_SEG);
-    SBL_REQUIRE(Lk_fixed >= 1, "sbl_attention_seg_grouped_fwd: Lk=%d (cross-attention only)", Lk_fixed);
-    SBL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "sbl_attention_seg_grouped_fwd: B=%d is no multiple of the group size %d", B, kv_group);
-    if (int e = at_check("sbl_attention_seg_grouped_fwd", B, H, d, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
+    SBL_REQUIRE(sbl_make_segs(d, seg_L, nseg, B, H, Lk_fixed) > 0, "%s: bad segment list (nseg=%d, 1..%d)", name, nseg, SBL_MAX_SEG);
+    SBL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "%s: B=%d is no multiple of the group size %d", name, B, kv_group);
+    if (int e = at_check(name, B, H, d, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
     SBL_REQUIRE(q && k && v && o && sbl_aligned16(q) && sbl_aligned16(k) && sbl_aligned16(v) && sbl_aligned16(o),
-                "sbl_attention_seg_grouped_fwd: null/unaligned pointer");
-    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_seg_grouped_fwd: bad dropout args");
-    const uint32_t thresh = drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u;
-    const float keep_scale = 1.f / (1.f - drop_p);
-    const bool small = at_small_ok(d, Lk_fixed, 0);
-    if (small || at_qtile_ok(d, Lk_fixed, 0)) {
-        const SegDesc t = small ? d : at_qtile_desc(d.L[0], Lk_fixed);
-        const int nprob = (small ? nseg : 2) * B * H;
-        hipLaunchKernelGGL(attention_small_grouped_fwd_kernel, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk,
-                           v, ldv, o, ldo, B, H, t, Lk_fixed, kv_group, scale, thresh, keep_scale, seed, offset, nprob);
-        SBL_LAUNCH_CHECK("sbl_attention_seg_grouped_fwd(small)");
-        return 0;
-    }
-    const int sz = at_rows_sz(d, nseg, Lk_fixed);
-    static bool attr_set[64] = {false};
-    SBL_HIP(sbl_raise_lds_cap((const void*)attention_grouped_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
-    hipLaunchKernelGGL(attention_grouped_fwd_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k,
-                       ldk, v, ldv, o, ldo, B, H, d, Lk_fixed, kv_group, scale, thresh, keep_scale, seed, offset, sz);
-    SBL_LAUNCH_CHECK("sbl_attention_seg_grouped_fwd");
-    return 0;
-}
-
-// sbl_attention_seg_grouped_fwd with a device-side key count per K/V entry (include/sbl_hip.h); Lk_fixed == 0: one segment of
-// self-attention, the count per sequence.  The dispatch is the grouped entry's, on the host-known shapes alone: kv_len is never
-// read here.
-extern "C" int sbl_attention_seg_len_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
-                                         long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
-                                         const int32_t* kv_len, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
-                                         sbl_stream_t stream) {
-    SegDesc d;
-    SBL_REQUIRE(kv_len, "sbl_attention_seg_len_fwd: kv_len is NULL");
-    SBL_REQUIRE(sbl_make_segs(d, seg_L, nseg, B, H, Lk_fixed) > 0, "sbl_attention_seg_len_fwd: bad segment list (nseg=%d, 1..%d)", nseg, SBL_MAX_SEG);
-    SBL_REQUIRE(Lk_fixed >= 0, "sbl_attention_seg_len_fwd: Lk=%d", Lk_fixed);
-    SBL_REQUIRE(Lk_fixed > 0 || (nseg == 1 && kv_group == 1),
-                "sbl_attention_seg_len_fwd: self-attention (Lk = 0) takes one segment and kv_group 1 (got nseg=%d, kv_group=%d)", nseg, kv_group);
-    SBL_REQUIRE(kv_group >= 1 && B % kv_group == 0, "sbl_attention_seg_len_fwd: B=%d is no multiple of the group size %d", B, kv_group);
-    if (int e = at_check("sbl_attention_seg_len_fwd", B, H, d, Lk_fixed, ldq, ldk, ldv, ldo)) return e;
-    SBL_REQUIRE(q && k && v && o && sbl_aligned16(q) && sbl_aligned16(k) && sbl_aligned16(v) && sbl_aligned16(o),
-                "sbl_attention_seg_len_fwd: null/unaligned pointer");
-    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "sbl_attention_seg_len_fwd: bad dropout args");
+                "%s: null/unaligned pointer", name);
+    SBL_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (drop_p == 0.f || seed), "%s: bad dropout args", name);
     const uint32_t thresh = drop_p > 0.f ? sbl_drop_thresh(drop_p) : 0u;
     const float keep_scale = 1.f / (1.f - drop_p);
     const bool small = at_small_ok(d, Lk_fixed, 0);
@@ -898,18 +861,47 @@ extern "C" int sbl_attention_seg_len_fwd(const float* q, long ldq, const float* 
         const int Lk = Lk_fixed > 0 ? Lk_fixed : d.L[0];      // query tiles of a self-attention read the sequence's own L rows
         const SegDesc t = small ? d : at_qtile_desc(d.L[0], Lk);
         const int nprob = (small ? nseg : 2) * B * H;
-        hipLaunchKernelGGL(attention_small_len_fwd_kernel, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk,
-                           v, ldv, o, ldo, B, H, t, small ? Lk_fixed : Lk, kv_group, kv_len, scale, thresh, keep_scale, seed, offset, nprob);
-        SBL_LAUNCH_CHECK("sbl_attention_seg_len_fwd(small)");
+        hipLaunchKernelGGL(small_kernel, dim3(sbl_cdiv(nprob, 4)), dim3(256), 0, (hipStream_t)stream, q, ldq, k, ldk, v, ldv, o, ldo, B, H,
+                           t, small ? Lk_fixed : Lk, kv_group, kv_len..., scale, thresh, keep_scale, seed, offset, nprob);
+        if (hipError_t e = hipGetLastError()) {
+            sbl_set_error("%s(small): launch failed: %s", name, hipGetErrorString(e));
+            return (int)e;
+        }
         return 0;
     }
     const int sz = at_rows_sz(d, nseg, Lk_fixed);
-    static bool attr_set[64] = {false};
-    SBL_HIP(sbl_raise_lds_cap((const void*)attention_len_fwd_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
-    hipLaunchKernelGGL(attention_len_fwd_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k,
-                       ldk, v, ldv, o, ldo, B, H, d, Lk_fixed, kv_group, kv_len, scale, thresh, keep_scale, seed, offset, sz);
-    SBL_LAUNCH_CHECK("sbl_attention_seg_len_fwd");
+    static bool attr_set[64] = {false};      // one per instantiation, i.e. per workgroup kernel
+    SBL_HIP(sbl_raise_lds_cap((const void*)wg_kernel, sizeof(float) * 4 * AT_SZ, attr_set));
+    hipLaunchKernelGGL(wg_kernel, dim3(nseg * B * H), dim3(256), sizeof(float) * 4 * sz, (hipStream_t)stream, q, ldq, k, ldk, v, ldv, o,
+                       ldo, B, H, d, Lk_fixed, kv_group, kv_len..., scale, thresh, keep_scale, seed, offset, sz);
+    SBL_LAUNCH_CHECK(name);
     return 0;
+}
+
+// Grouped cross-attention, inference only: sbl_attention_seg_fwd with Lk_fixed > 0 and no mask, where sequence b of the B reads
+// the key / value rows of entry b / kv_group (k / v hold B / kv_group entries of Lk_fixed rows) and no probabilities are
+// written.  Same kernels, same size dispatch and same arithmetic per sequence as sbl_attention_seg_fwd on K/V repeated
+// kv_group-fold, without the repeated copy.
+extern "C" int sbl_attention_seg_grouped_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                                             long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
+                                             float scale, float drop_p, const uint64_t* seed, uint64_t offset, sbl_stream_t stream) {
+    SBL_REQUIRE(Lk_fixed >= 1, "sbl_attention_seg_grouped_fwd: Lk=%d (cross-attention only)", Lk_fixed);
+    return at_grouped_launch("sbl_attention_seg_grouped_fwd", attention_small_grouped_fwd_kernel, attention_grouped_fwd_kernel, q, ldq, k,
+                             ldk, v, ldv, o, ldo, B, H, seg_L, nseg, Lk_fixed, kv_group, scale, drop_p, seed, offset, stream);
+}
+
+// sbl_attention_seg_grouped_fwd with a device-side key count per K/V entry (include/sbl_hip.h); Lk_fixed == 0: one segment of
+// self-attention, the count per sequence.
+extern "C" int sbl_attention_seg_len_fwd(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, float* o,
+                                         long ldo, int B, int H, const int* seg_L, int nseg, int Lk_fixed, int kv_group,
+                                         const int32_t* kv_len, float scale, float drop_p, const uint64_t* seed, uint64_t offset,
+                                         sbl_stream_t stream) {
+    SBL_REQUIRE(kv_len, "sbl_attention_seg_len_fwd: kv_len is NULL");
+    SBL_REQUIRE(Lk_fixed >= 0, "sbl_attention_seg_len_fwd: Lk=%d", Lk_fixed);
+    SBL_REQUIRE(Lk_fixed > 0 || (nseg == 1 && kv_group == 1),
+                "sbl_attention_seg_len_fwd: self-attention (Lk = 0) takes one segment and kv_group 1 (got nseg=%d, kv_group=%d)", nseg, kv_group);
+    return at_grouped_launch("sbl_attention_seg_len_fwd", attention_small_len_fwd_kernel, attention_len_fwd_kernel, q, ldq, k, ldk, v, ldv,
+                             o, ldo, B, H, seg_L, nseg, Lk_fixed, kv_group, scale, drop_p, seed, offset, stream, kv_len);
 }
 
 extern "C" int sbl_attention_seg2_fwd(const float* q0, const float* q1, long ldq, const float* k0, const float* k1, long ldk,

@@ -197,24 +197,38 @@ __global__ __launch_bounds__(256) void pair_beam_tail_kernel(
     pb_write_prefixes(ys_old_l, ys_old_r, ys_new_l, ys_new_r, ldys, slot0, s_par, s_tok, step, maxlen, eos, W);
 }
 
+// The requirements the two entries share, refused under the entry's `name`.  hist_extra: one more output that must not be null
+// (the lex entry's hist_node; the plain entry passes one of its own again).
+static int pair_beam_tail_check(const char* name, const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r,
+                                const float* score, const float* score_dir, const int64_t* ys_old_l, const int64_t* ys_old_r,
+                                const int64_t* ys_new_l, const int64_t* ys_new_r, long ldys, const int32_t* hist_tok_l,
+                                const int32_t* hist_tok_r, const int32_t* hist_par, const float* hist_score,
+                                const int32_t* hist_extra, int step, int maxlen, int eos, int N, int W, int V, int D) {
+    SBL_REQUIRE(D == DH_D, "%s: D=%d (built for %d)", name, D, DH_D);
+    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "%s: V=%d (V <= %d)", name, V, DH_MAX_V);
+    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "%s: beam W=%d outside 1..%d", name, W, DH_MAX_W);
+    SBL_REQUIRE(W <= V, "%s: beam W=%d above V=%d", name, W, V);
+    SBL_REQUIRE(N > 0 && maxlen >= 1 && step >= 0 && step < maxlen, "%s: N=%d, step %d of %d", name, N, step, maxlen);
+    SBL_REQUIRE(eos >= 0 && eos < V, "%s: eos=%d outside the %d classes", name, eos, V);
+    SBL_REQUIRE(ldys >= maxlen + 1, "%s: prefix rows of %ld entries for maxlen=%d (+1)", name, ldys, maxlen);
+    SBL_REQUIRE(y_l && y_r && w_l && w_r && score && score_dir, "%s: null input", name);
+    SBL_REQUIRE(ys_old_l && ys_old_r && ys_new_l && ys_new_r && ys_old_l != ys_new_l && ys_old_r != ys_new_r,
+                "%s: null or aliased prefix buffers", name);
+    SBL_REQUIRE(hist_tok_l && hist_tok_r && hist_par && hist_score && hist_extra, "%s: null output", name);
+    SBL_REQUIRE(ldy >= D && ldy % 4 == 0, "%s: row stride %ld", name, ldy);
+    SBL_REQUIRE(sbl_aligned16(y_l) && sbl_aligned16(y_r) && sbl_aligned16(w_l) && sbl_aligned16(w_r), "%s: unaligned", name);
+    return 0;
+}
+
 extern "C" int sbl_pair_beam_tail(const float* y_l, const float* y_r, long ldy, const float* w_l, const float* w_r, float* score,
                                   float* score_dir, const int64_t* ys_old_l, const int64_t* ys_old_r, int64_t* ys_new_l,
                                   int64_t* ys_new_r, long ldys, int32_t* hist_tok_l, int32_t* hist_tok_r, int32_t* hist_par,
                                   float* hist_score, int step, int maxlen, int eos, int N, int W, int V, int D,
                                   sbl_stream_t stream) {
-    SBL_REQUIRE(D == DH_D, "sbl_pair_beam_tail: D=%d (built for %d)", D, DH_D);
-    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "sbl_pair_beam_tail: V=%d (V <= %d)", V, DH_MAX_V);
-    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_pair_beam_tail: beam W=%d outside 1..%d", W, DH_MAX_W);
-    SBL_REQUIRE(W <= V, "sbl_pair_beam_tail: beam W=%d above V=%d", W, V);
-    SBL_REQUIRE(N > 0 && maxlen >= 1 && step >= 0 && step < maxlen, "sbl_pair_beam_tail: N=%d, step %d of %d", N, step, maxlen);
-    SBL_REQUIRE(eos >= 0 && eos < V, "sbl_pair_beam_tail: eos=%d outside the %d classes", eos, V);
-    SBL_REQUIRE(ldys >= maxlen + 1, "sbl_pair_beam_tail: prefix rows of %ld entries for maxlen=%d (+1)", ldys, maxlen);
-    SBL_REQUIRE(y_l && y_r && w_l && w_r && score && score_dir, "sbl_pair_beam_tail: null input");
-    SBL_REQUIRE(ys_old_l && ys_old_r && ys_new_l && ys_new_r && ys_old_l != ys_new_l && ys_old_r != ys_new_r,
-                "sbl_pair_beam_tail: null or aliased prefix buffers");
-    SBL_REQUIRE(hist_tok_l && hist_tok_r && hist_par && hist_score, "sbl_pair_beam_tail: null output");
-    SBL_REQUIRE(ldy >= D && ldy % 4 == 0, "sbl_pair_beam_tail: row stride %ld", ldy);
-    SBL_REQUIRE(sbl_aligned16(y_l) && sbl_aligned16(y_r) && sbl_aligned16(w_l) && sbl_aligned16(w_r), "sbl_pair_beam_tail: unaligned");
+    if (int rc = pair_beam_tail_check("sbl_pair_beam_tail", y_l, y_r, ldy, w_l, w_r, score, score_dir, ys_old_l, ys_old_r, ys_new_l,
+                                      ys_new_r, ldys, hist_tok_l, hist_tok_r, hist_par, hist_score, hist_par, step, maxlen, eos, N, W,
+                                      V, D))
+        return rc;
     hipLaunchKernelGGL(pair_beam_tail_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, y_l, y_r, ldy, w_l, w_r, score, score_dir,
                        ys_old_l, ys_old_r, ys_new_l, ys_new_r, ldys, hist_tok_l, hist_tok_r, hist_par, hist_score, step, maxlen, eos,
                        W, V);
@@ -387,19 +401,10 @@ extern "C" int sbl_pair_beam_tail_lex(const float* y_l, const float* y_r, long l
                                       int32_t* hist_par, float* hist_score, int step, int maxlen, int eos, int N, int W, int V, int D,
                                       const int32_t* trie_begin, const int32_t* trie_key, const int32_t* trie_word, int P, int E,
                                       const int32_t* node_old, int32_t* node_new, int32_t* hist_node, sbl_stream_t stream) {
-    SBL_REQUIRE(D == DH_D, "sbl_pair_beam_tail_lex: D=%d (built for %d)", D, DH_D);
-    SBL_REQUIRE(V >= 1 && V <= DH_MAX_V, "sbl_pair_beam_tail_lex: V=%d (V <= %d)", V, DH_MAX_V);
-    SBL_REQUIRE(W >= 1 && W <= DH_MAX_W, "sbl_pair_beam_tail_lex: beam W=%d outside 1..%d", W, DH_MAX_W);
-    SBL_REQUIRE(W <= V, "sbl_pair_beam_tail_lex: beam W=%d above V=%d", W, V);
-    SBL_REQUIRE(N > 0 && maxlen >= 1 && step >= 0 && step < maxlen, "sbl_pair_beam_tail_lex: N=%d, step %d of %d", N, step, maxlen);
-    SBL_REQUIRE(eos >= 0 && eos < V, "sbl_pair_beam_tail_lex: eos=%d outside the %d classes", eos, V);
-    SBL_REQUIRE(ldys >= maxlen + 1, "sbl_pair_beam_tail_lex: prefix rows of %ld entries for maxlen=%d (+1)", ldys, maxlen);
-    SBL_REQUIRE(y_l && y_r && w_l && w_r && score && score_dir, "sbl_pair_beam_tail_lex: null input");
-    SBL_REQUIRE(ys_old_l && ys_old_r && ys_new_l && ys_new_r && ys_old_l != ys_new_l && ys_old_r != ys_new_r,
-                "sbl_pair_beam_tail_lex: null or aliased prefix buffers");
-    SBL_REQUIRE(hist_tok_l && hist_tok_r && hist_par && hist_score && hist_node, "sbl_pair_beam_tail_lex: null output");
-    SBL_REQUIRE(ldy >= D && ldy % 4 == 0, "sbl_pair_beam_tail_lex: row stride %ld", ldy);
-    SBL_REQUIRE(sbl_aligned16(y_l) && sbl_aligned16(y_r) && sbl_aligned16(w_l) && sbl_aligned16(w_r), "sbl_pair_beam_tail_lex: unaligned");
+    if (int rc = pair_beam_tail_check("sbl_pair_beam_tail_lex", y_l, y_r, ldy, w_l, w_r, score, score_dir, ys_old_l, ys_old_r,
+                                      ys_new_l, ys_new_r, ldys, hist_tok_l, hist_tok_r, hist_par, hist_score, hist_node, step, maxlen,
+                                      eos, N, W, V, D))
+        return rc;
     SBL_REQUIRE(P >= 1 && E >= 0, "sbl_pair_beam_tail_lex: P=%d trie nodes, E=%d edges", P, E);
     SBL_REQUIRE(trie_begin && trie_word && (trie_key || E == 0), "sbl_pair_beam_tail_lex: null trie table");
     SBL_REQUIRE(node_old && node_new && node_old != node_new, "sbl_pair_beam_tail_lex: null or aliased node buffers");

@@ -774,6 +774,13 @@ def out_ln_fwd(h, a, res, seed, off, bufs=None):
     return o, y, mean, rstd
 
 
+def _counts(t, n, what):
+    """The pointer of a per-clip counts tensor (key counts, step counts): contiguous CUDA int32 (n,), never read on the host."""
+    assert t.is_cuda and t.dtype == torch.int32 and t.shape == (n,) and t.is_contiguous(), \
+        "%s: a contiguous CUDA int32 tensor of %d counts" % (what, n)
+    return _p(t)
+
+
 def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o, kv_group=None, kv_len=None):
     """Attention sub-layer on the rows x (B * sum(segL), D) of a ragged batch: segment s has B sequences of length segL[s].
     kv = None: self-attention inside each segment; else cross-attention to the rows kv (B * Lk, 2 * H * 64) = [K|V] (a
@@ -786,28 +793,22 @@ def attn_fwd(a, x, B, segL, kv, mask_kind, mask_t, seed, off_a, off_o, kv_group=
     (sbl_attention_seg_len_fwd).  The counts are never read on the host; p = None."""
     HD = a.H * 64
     qkv = lin_fwd(a.inp, x)
-    if kv_len is not None:
+    if kv_len is not None or kv_group is not None:      # inference: the grouped entry, or the `len` one with the counts behind G
         G = 1 if kv_group is None else int(kv_group)
-        assert not torch.is_grad_enabled() and mask_kind == 0 and B % G == 0
-        assert kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.is_contiguous() and kv_len.numel() == B // G, \
-            "kv_len: a contiguous CUDA int32 tensor of %d counts" % (B // G)
+        assert mask_kind == 0 and B % G == 0
+        name, counts = "sbl_attention_seg_grouped_fwd", ()
+        if kv_len is not None:
+            assert not torch.is_grad_enabled()
+            name, counts = "sbl_attention_seg_len_fwd", (_counts(kv_len, B // G, "kv_len"),)
         if kv is None:
-            assert G == 1 and len(segL) == 1
+            assert kv_len is not None and G == 1 and len(segL) == 1
             k, v, ldk, Lk = qkv[:, HD:], qkv[:, 2 * HD:], 3 * HD, 0
         else:
             assert kv.size(0) % (B // G) == 0
             k, v, ldk, Lk = kv, kv[:, HD:], _rows(kv)[1], kv.size(0) // (B // G)
         att = _new(x, x.size(0), HD)
-        call("sbl_attention_seg_len_fwd", _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(att), HD, B, a.H, *_segs(segL), Lk, G,
-             _p(kv_len), 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
-        o, y, mean, rstd = out_ln_fwd(a, att, x, seed, off_o)
-        return y, (qkv, att, None, o, mean, rstd)
-    if kv_group is not None:
-        assert kv is not None and mask_kind == 0 and B % kv_group == 0 and kv.size(0) % (B // kv_group) == 0
-        ldk = _rows(kv)[1]
-        att = _new(x, x.size(0), HD)
-        call("sbl_attention_seg_grouped_fwd", _p(qkv), a.inp.N, _p(kv), ldk, _p(kv[:, HD:]), ldk, _p(att), HD, B, a.H, *_segs(segL),
-             kv.size(0) // (B // kv_group), int(kv_group), 1.0 / 8.0, a.drop_p, _p(seed) if a.drop_p > 0 else None, off_a, _s())
+        call(name, _p(qkv), a.inp.N, _p(k), ldk, _p(v), ldk, _p(att), HD, B, a.H, *_segs(segL), Lk, G, *counts, 1.0 / 8.0, a.drop_p,
+             _p(seed) if a.drop_p > 0 else None, off_a, _s())
         o, y, mean, rstd = out_ln_fwd(a, att, x, seed, off_o)
         return y, (qkv, att, None, o, mean, rstd)
     if kv is None:
@@ -2049,8 +2050,7 @@ def _attn_step(q, k_new, v_new, k_cache, v_cache, Lcap, anc, out, W, H, n_prev, 
     tail = (H, int(n_prev), int(bool(append)), scale)
     name, end = ("sbl_decode_attn_step", "sbl_beam_attn_step"), (_s(),)
     if kv_len is not None:
-        assert kv_len.is_cuda and kv_len.dtype == torch.int32 and kv_len.shape == (nc,) and kv_len.is_contiguous()
-        name, end = (name[0] + "_len", name[1] + "_len"), (_p(kv_len), _s())
+        name, end = (name[0] + "_len", name[1] + "_len"), (_counts(kv_len, nc, "kv_len"), _s())
     if W is None:
         call(name[0], *head, _p(out), out.stride(0), S, *tail, *end)
     else:
@@ -2118,11 +2118,6 @@ class BeamState(object):
         return self.hist_tok, self.hist_par, self.hist_score, self.hist_flag
 
 
-def _clip_steps(clip_steps, N):
-    assert clip_steps.is_cuda and clip_steps.dtype == torch.int32 and clip_steps.shape == (N,) and clip_steps.is_contiguous()
-    return _p(clip_steps)
-
-
 def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None, trie=None, clip_steps=None):
     """Tail of beam step `step` in one launch (sbl_beam_tail) on the rows y (N*W, 512): the best W candidates of every clip
     into the BeamState `st` (ancestry buffer step % 2 is read, the other one written), x_next = the next input rows.
@@ -2142,7 +2137,7 @@ def beam_tail(y, w, log_prior, st, step, eos_id, emb, pe, emb_scale, x_next=None
             _p(st.end_score), _p(st.end_ref), _p(st.end_count), int(step), st.maxlen, int(eos_id), _p(emb), _p(pe), pe.size(0),
             emb_scale, _p(x_next), st.N, st.W, V, D)
     if clip_steps is not None:
-        call("sbl_beam_tail_len", *args, _clip_steps(clip_steps, st.N), _s())
+        call("sbl_beam_tail_len", *args, _counts(clip_steps, st.N, "clip_steps"), _s())
         return
     if trie is None:
         call("sbl_beam_tail", *args, _s())
@@ -2168,7 +2163,7 @@ def beam_finish(st, nbest, eos_id, clip_steps=None):
     if clip_steps is None:
         call("sbl_beam_finish", *args, _s())
     else:
-        call("sbl_beam_finish_len", *args, _clip_steps(clip_steps, st.N), _s())
+        call("sbl_beam_finish_len", *args, _counts(clip_steps, st.N, "clip_steps"), _s())
     return yseq, lengths, scores, n_hyps
 
 
@@ -2219,41 +2214,41 @@ class PairBeamState(object):
         return self.hist_tok_l, self.hist_tok_r, self.hist_par, self.hist_score
 
 
-def pair_beam_tail(y_l, y_r, w_l, w_r, st, step):
-    """Tail of beam step `step` in one launch (sbl_pair_beam_tail) on the rows y_l / y_r (N*W, 512) the two heads read: the
-    best W pair candidates of every clip into the PairBeamState `st` (prefix buffer step % 2 is read, the other written)."""
+def _pair_beam_tail(y_l, y_r, w_l, w_r, st, step, pair_trie):
+    """The shape checks and the call behind pair_beam_tail (pair_trie = None) and pair_beam_tail_lex."""
     S, D = y_l.shape
     V = w_l.size(0)
     assert S == st.N * st.W and y_r.shape == y_l.shape and w_r.shape == w_l.shape
     assert y_l.stride(1) == 1 and y_r.stride(1) == 1 and y_l.stride(0) == y_r.stride(0) and w_l.is_contiguous() and w_r.is_contiguous()
-    _need_cuda(y_l, y_r, w_l, w_r, st.score)
+    _need_cuda(y_l, y_r, w_l, w_r, st.score, *(pair_trie or ()))
+    name, lex = "sbl_pair_beam_tail", ()
+    if pair_trie is not None:
+        begin, key, word = pair_trie
+        if st.node is None:
+            raise _lib.SblHipError("pair_beam_tail_lex: a pair trie needs a PairBeamState with node buffers (lex=True)")
+        P, E = word.numel(), key.numel()
+        ok = all(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == y_l.device for t in pair_trie)
+        if not ok or P < 1 or begin.numel() != P + 1:
+            raise _lib.SblHipError("pair trie tables must be contiguous int32 vectors begin (P + 1) / key (E) / word (P) on %s" % y_l.device)
+        name = "sbl_pair_beam_tail_lex"
+        lex = (_p(begin), _p(key), _p(word), P, E, _p(st.node[step % 2]), _p(st.node[1 - step % 2]), _p(st.hist_node))
     old, new = st.ys[:, step % 2], st.ys[:, 1 - step % 2]
-    call("sbl_pair_beam_tail", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
-         _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
-         _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _s())
+    call(name, _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]), _p(old[1]), _p(new[0]),
+         _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par), _p(st.hist_score), int(step), st.maxlen,
+         int(st.eos_id), st.N, st.W, V, D, *lex, _s())
+
+
+def pair_beam_tail(y_l, y_r, w_l, w_r, st, step):
+    """Tail of beam step `step` in one launch (sbl_pair_beam_tail) on the rows y_l / y_r (N*W, 512) the two heads read: the
+    best W pair candidates of every clip into the PairBeamState `st` (prefix buffer step % 2 is read, the other written)."""
+    _pair_beam_tail(y_l, y_r, w_l, w_r, st, step, None)
 
 
 def pair_beam_tail_lex(y_l, y_r, w_l, w_r, st, step, pair_trie):
     """pair_beam_tail restricted to a word list, in one launch (include/sbl_hip.h, sbl_pair_beam_tail_lex).  pair_trie: the
     (begin (P + 1), key (P - 1), word (P)) int32 tables of Lexicon.pair_trie() on the same device; st: a PairBeamState with
     lex=True, whose node buffer step % 2 is read and the other one written, like the prefixes."""
-    S, D = y_l.shape
-    V = w_l.size(0)
-    assert S == st.N * st.W and y_r.shape == y_l.shape and w_r.shape == w_l.shape
-    assert y_l.stride(1) == 1 and y_r.stride(1) == 1 and y_l.stride(0) == y_r.stride(0) and w_l.is_contiguous() and w_r.is_contiguous()
-    begin, key, word = pair_trie
-    _need_cuda(y_l, y_r, w_l, w_r, st.score, begin, key, word)
-    if st.node is None:
-        raise _lib.SblHipError("pair_beam_tail_lex: a pair trie needs a PairBeamState with node buffers (lex=True)")
-    P, E = word.numel(), key.numel()
-    ok = all(t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous() and t.device == y_l.device for t in pair_trie)
-    if not ok or P < 1 or begin.numel() != P + 1:
-        raise _lib.SblHipError("pair trie tables must be contiguous int32 vectors begin (P + 1) / key (E) / word (P) on %s" % y_l.device)
-    old, new = st.ys[:, step % 2], st.ys[:, 1 - step % 2]
-    call("sbl_pair_beam_tail_lex", _p(y_l), _p(y_r), y_l.stride(0), _p(w_l), _p(w_r), _p(st.score), _p(st.score_dir), _p(old[0]),
-         _p(old[1]), _p(new[0]), _p(new[1]), st.ys.stride(2), _p(st.hist_tok_l), _p(st.hist_tok_r), _p(st.hist_par),
-         _p(st.hist_score), int(step), st.maxlen, int(st.eos_id), st.N, st.W, V, D, _p(begin), _p(key), _p(word), P, E,
-         _p(st.node[step % 2]), _p(st.node[1 - step % 2]), _p(st.hist_node), _s())
+    _pair_beam_tail(y_l, y_r, w_l, w_r, st, step, pair_trie)
 
 
 # --------------------------------------------------------------------------- #

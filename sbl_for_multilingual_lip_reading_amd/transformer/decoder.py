@@ -10,6 +10,7 @@ from ._env import _lib, config, ops
 from . import decoder_stages
 from .attention import MultiHeadAttention
 from .module import PositionalEncoding, PositionwiseFeedForward, mask_rows
+from .utils import device_lengths
 
 IGNORE_ID = config.IGNORE_ID
 MAX_PAIR_BEAM = 16          # slots per clip of Decoder.beam_search (csrc/pair_beam.hip)
@@ -201,19 +202,7 @@ class Decoder(nn.Module):
                 kv[1] = [lay.enc_attn.project_kv(encoder_outputs) for lay in layers[1]]
         return layers, main, side, kv
 
-    @staticmethod
-    def _kv_len(encoder_input_lengths, encoder_outputs):
-        """The cross-attention key counts of a decode: None, or the clips' frame counts as a device int32 (N,) tensor (a CUDA
-        int32 tensor is used as it is and never read on the host)."""
-        lens = encoder_input_lengths
-        if lens is None:
-            return None
-        if not (isinstance(lens, torch.Tensor) and lens.is_cuda):
-            lens = torch.as_tensor(lens, dtype=torch.int32).to(encoder_outputs.device)
-        if lens.dtype != torch.int32 or lens.shape != (encoder_outputs.size(0),) or not lens.is_contiguous():
-            raise _lib.SblHipError("encoder_input_lengths: a contiguous int32 (%d,) tensor, got %s %s"
-                                   % (encoder_outputs.size(0), lens.dtype, tuple(lens.shape)))
-        return lens
+    _kv_len = staticmethod(device_lengths)
 
     def _stage(self, ys, B, segL, layers, main, side, kv, kv_group=None, kv_len=None):
         """One stage on B sequences per segment: embedding + PE of the token tables ys[direction], the n_layers layers of
@@ -342,31 +331,46 @@ class Decoder(nn.Module):
         Returns PairBeamResult(ys_l2r, ys_r2l (N, nbest, 17) int64, scores (N, nbest), scores_dir (N, nbest, 2), history =
         (l2r token, r2l token, parent rank, total score), each (N, 16, W) at [n][step][rank])."""
         enc = encoder_outputs
-        W, nbest = int(beam_size), int(nbest)
-        if not 1 <= W <= MAX_PAIR_BEAM:
-            raise _lib.SblHipError("Decoder.beam_search: beam_size = %d outside 1..%d" % (W, MAX_PAIR_BEAM))
-        if not 1 <= nbest <= W:
-            raise _lib.SblHipError("Decoder.beam_search: nbest = %d outside 1..beam_size = %d" % (nbest, W))
-        if not enc.is_cuda:
-            raise _lib.SblHipError("Decoder.beam_search needs the encoder output on the GPU (got a %s tensor); there is no "
-                                   "CPU path" % enc.device)
+        W, nbest = self._search_args("Decoder.beam_search", enc, beam_size, nbest)
         with torch.no_grad():
-            st = self._beam_run(enc, W, self._kv_len(encoder_input_lengths, enc))
+            kv_len = self._kv_len(encoder_input_lengths, enc)
+            st = self._beam_steps(enc, W, config.MAX_DECODE_LEN, kv_len, ops.pair_beam_tail)
         N, L = enc.size(0), config.MAX_DECODE_LEN + 1
         ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(config.MAX_DECODE_LEN))
         return PairBeamResult(ys_l, ys_r, st.score[:, :nbest], st.score_dir[:, :nbest], st.history())
 
-    def _beam_run(self, encoder_outputs, W, kv_len=None):
-        """The 16 steps of beam_search -> the final ops.PairBeamState.  The stage is `_run`'s, at batch N * W."""
-        maxlen = config.MAX_DECODE_LEN
-        N = encoder_outputs.size(0)
-        S = N * W
-        layers, main, side, kv = self._begin(encoder_outputs)
-        st = ops.PairBeamState(N, W, maxlen, self.sos_id, self.eos_id, encoder_outputs.device)
+    @staticmethod
+    def _search_args(who, enc, beam_size, nbest):
+        """(W, nbest) of a pair beam search as ints, after the refusals both searches share (`who`: the method, for the message)."""
+        W, nbest = int(beam_size), int(nbest)
+        if not 1 <= W <= MAX_PAIR_BEAM:
+            raise _lib.SblHipError("%s: beam_size = %d outside 1..%d" % (who, W, MAX_PAIR_BEAM))
+        if not 1 <= nbest <= W:
+            raise _lib.SblHipError("%s: nbest = %d outside 1..beam_size = %d" % (who, nbest, W))
+        Decoder._need_gpu(who, enc)
+        return W, nbest
+
+    @staticmethod
+    def _need_gpu(who, enc):
+        if not enc.is_cuda:
+            raise _lib.SblHipError("%s needs the encoder output on the GPU (got a %s tensor); there is no CPU path" % (who, enc.device))
+
+    def _check_lexicon(self, who, lexicon):
+        if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
+            raise _lib.SblHipError("%s: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
+                                   % (who, lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+
+    def _beam_steps(self, enc, W, steps, kv_len, tail, lex=False):
+        """The step loop of beam_search and beam_search_lex -> the final ops.PairBeamState (lex: with node buffers), on the
+        17-entry prefix rows the stage reads.  The stage is `_run`'s, at batch N * W; tail(last_l, last_r, head_l, head_r, st, i)
+        ends step i."""
+        N = enc.size(0)
+        layers, main, side, kv = self._begin(enc)
+        st = ops.PairBeamState(N, W, steps, self.sos_id, self.eos_id, enc.device, lex=lex, row_len=config.MAX_DECODE_LEN + 1)
         heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
-        for i in range(maxlen):
-            last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W, kv_len=kv_len)
-            ops.pair_beam_tail(last[0], last[1], heads[0], heads[1], st, i)
+        for i in range(steps):
+            last = self._stage_last(st.prefixes(i), N * W, (i + 1,), layers, main, side, kv, kv_group=W, kv_len=kv_len)
+            tail(last[0], last[1], heads[0], heads[1], st, i)
         return st
 
     def score_pairs(self, encoder_outputs, ys_l2r, ys_r2l, n_pos=None, group=1, encoder_input_lengths=None):
@@ -384,9 +388,7 @@ class Decoder(nn.Module):
         score in every group, the lower rank on an exact tie)."""
         enc = encoder_outputs
         G = int(group)
-        if not enc.is_cuda:
-            raise _lib.SblHipError("Decoder.score_pairs needs the encoder output on the GPU (got a %s tensor); there is no "
-                                   "CPU path" % enc.device)
+        self._need_gpu("Decoder.score_pairs", enc)
         maxlen = config.MAX_DECODE_LEN
         ys = [y.reshape(-1, maxlen + 1).contiguous() for y in (ys_l2r, ys_r2l)]
         S, N = ys[0].size(0), enc.size(0)
@@ -423,15 +425,11 @@ class Decoder(nn.Module):
         Returns WordResult(word (N,) int64, cand, cand_dist, cand_hyp (N, K) int32, score (N, K), score_dir (N, K, 2))."""
         enc = encoder_outputs
         K = int(shortlist)
-        if not enc.is_cuda:
-            raise _lib.SblHipError("Decoder.recognize_words needs the encoder output on the GPU (got a %s tensor); there is no "
-                                   "CPU path" % enc.device)
+        self._need_gpu("Decoder.recognize_words", enc)
         if not 1 <= K <= min(len(lexicon), ops.LEXICON_MAX_SHORTLIST):
             raise _lib.SblHipError("Decoder.recognize_words: shortlist = %d outside 1..min(%d words, %d)"
                                    % (K, len(lexicon), ops.LEXICON_MAX_SHORTLIST))
-        if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
-            raise _lib.SblHipError("Decoder.recognize_words: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
-                                   % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+        self._check_lexicon("Decoder.recognize_words", lexicon)
         kv_len = self._kv_len(encoder_input_lengths, enc)
         if beam_size is None:
             ys_l, ys_r = self.recognize_beam(enc, kv_len)
@@ -458,28 +456,14 @@ class Decoder(nn.Module):
         score (N, nbest), score_dir (N, nbest, 2), ys_l2r, ys_r2l (N, nbest, 17) int64 = sos, w, eos fill and sos,
         reversed(w), eos fill, history = (l2r token, r2l token, parent rank, total score, node), each (N, steps, W))."""
         enc = encoder_outputs
-        W, nbest = int(beam_size), int(nbest)
-        if not 1 <= W <= MAX_PAIR_BEAM:
-            raise _lib.SblHipError("Decoder.beam_search_lex: beam_size = %d outside 1..%d" % (W, MAX_PAIR_BEAM))
-        if not 1 <= nbest <= W:
-            raise _lib.SblHipError("Decoder.beam_search_lex: nbest = %d outside 1..beam_size = %d" % (nbest, W))
-        if not enc.is_cuda:
-            raise _lib.SblHipError("Decoder.beam_search_lex needs the encoder output on the GPU (got a %s tensor); there is no "
-                                   "CPU path" % enc.device)
-        if lexicon.vocab > self.n_tgt_vocab or (lexicon.sos_id, lexicon.eos_id) != (self.sos_id, self.eos_id):
-            raise _lib.SblHipError("Decoder.beam_search_lex: the lexicon (vocab %d, sos %d, eos %d) is not this decoder's (%d, %d, %d)"
-                                   % (lexicon.vocab, lexicon.sos_id, lexicon.eos_id, self.n_tgt_vocab, self.sos_id, self.eos_id))
+        W, nbest = self._search_args("Decoder.beam_search_lex", enc, beam_size, nbest)
+        self._check_lexicon("Decoder.beam_search_lex", lexicon)
         N, L = enc.size(0), config.MAX_DECODE_LEN + 1
-        S, steps = N * W, lexicon.max_len + 1
+        steps = lexicon.max_len + 1
         trie = lexicon.pair_trie()
         kv_len = self._kv_len(encoder_input_lengths, enc)
         with torch.no_grad():
-            layers, main, side, kv = self._begin(enc)
-            st = ops.PairBeamState(N, W, steps, self.sos_id, self.eos_id, enc.device, lex=True, row_len=L)
-            heads = (self.tgt_word_prj_l2r.weight, self.tgt_word_prj_r2l.weight)
-            for i in range(steps):
-                last = self._stage_last(st.prefixes(i), S, (i + 1,), layers, main, side, kv, kv_group=W, kv_len=kv_len)
-                ops.pair_beam_tail_lex(last[0], last[1], heads[0], heads[1], st, i, trie)
+            st = self._beam_steps(enc, W, steps, kv_len, lambda *a: ops.pair_beam_tail_lex(*a, trie), lex=True)
             cand = trie[2][st.nodes(steps)[:, :nbest].long()]      # a dead rank sits on node 0, whose word is -1
         ys_l, ys_r = (y.view(N, W, L)[:, :nbest] for y in st.prefixes(steps))
         return PairWordBeamResult(cand[:, 0].long(), cand, st.score[:, :nbest], st.score_dir[:, :nbest], ys_l, ys_r,

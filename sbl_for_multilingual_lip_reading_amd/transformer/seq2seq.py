@@ -16,7 +16,7 @@ from ._env import _lib, config, ops
 from .decoder import DecoderLayer
 from .module import PositionalEncoding
 from .transformer import Transformer
-from .utils import get_attn_pad_mask
+from .utils import device_lengths, get_attn_pad_mask
 from .video_frontend import Lipreading
 
 IGNORE_ID = config.IGNORE_ID
@@ -189,18 +189,7 @@ class Seq2SeqDecoder(nn.Module):
                 ys.masked_fill_(behind, self.eos_id)
             return ys
 
-    @staticmethod
-    def _kv_len(encoder_input_lengths, encoder_outputs):
-        """None, or the lengths as the device int32 (N,) tensor the `_len` kernels read (a host sequence is copied once)."""
-        lens = encoder_input_lengths
-        if lens is None:
-            return None
-        if not (isinstance(lens, torch.Tensor) and lens.is_cuda):
-            lens = torch.as_tensor(lens, dtype=torch.int32).to(encoder_outputs.device)
-        if lens.dtype != torch.int32 or lens.shape != (encoder_outputs.size(0),) or not lens.is_contiguous():
-            raise _lib.SblHipError("encoder_input_lengths: a contiguous int32 (%d,) tensor, got %s %s"
-                                   % (encoder_outputs.size(0), lens.dtype, tuple(lens.shape)))
-        return lens
+    _kv_len = staticmethod(device_lengths)
 
     def _new_ys(self, enc):
         return torch.full((enc.size(0), enc.size(1) + 1), self.sos_id, dtype=torch.long, device=enc.device)
@@ -226,7 +215,7 @@ class Seq2SeqDecoder(nn.Module):
         (rows, >= 1) token table tok0, then per step and layer the 11 launches of DESIGN.md section 4.4 and the tail;
         nothing is read back.  attn(step, ...) takes the arguments of ops.decode_attn_step; tail(y, w, step, emb, pe, scale,
         x_next) ends a step (x_next: the next step's input rows, None at the last one).  kv_len: None, or the clips' device
-        int32 key counts for every cross-attention (attn is then called with kv_len=)."""
+        int32 key counts for every cross-attention (attn's kv_len=)."""
         N, T, D = enc.shape
         layers = [(lay.slf_attn.handle(), lay.enc_attn.handle(cross=True), lay.pos_ffn.handle()) for lay in self.layer_stack]
         nl, H = len(layers), self.n_head
@@ -251,18 +240,18 @@ class Seq2SeqDecoder(nn.Module):
                 attn(i, qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], cache[l, 0], cache[l, 1], steps, att, H, i, True)
                 ops.out_ln_fwd(sa, att, cur, None, 0, (o, ya, mean, rstd))
                 ops.lin_fwd(ca.inp, ya, q)
-                if kv_len is None:
-                    attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False)
-                else:
-                    attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False, kv_len=kv_len)
+                attn(i, q, None, None, kv[l][:, :, :HD], kv[l][:, :, HD:], T, att, H, T, False, kv_len=kv_len)
                 ops.out_ln_fwd(ca, att, ya, None, 0, (o, yb, mean, rstd))
                 ops.ffn_fwd(ff, yb, None, 0, h, (o, yc, mean, rstd))
                 cur = yc
             tail(cur, w, i, emb, pe, scale, x if i + 1 < steps else None)
 
-    def _greedy_cached(self, enc, lens=None):
+    def _require_eval(self):
         if self.training and self.dropout.p > 0:
             raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+
+    def _greedy_cached(self, enc, lens=None):
+        self._require_eval()
         ys = self._new_ys(enc)
         self._cached_steps(enc, enc.size(0), enc.size(1), ys, lambda i, *a, **kw: ops.decode_attn_step(*a, **kw),
                            lambda y, w, i, *head: ops.decode_tail(y, w, ys, i, *head), kv_len=lens)
@@ -326,8 +315,7 @@ class Seq2SeqDecoder(nn.Module):
         if log_prior is not None and (log_prior.dtype != torch.float32 or tuple(log_prior.shape) != (V, V)
                                       or log_prior.device != enc.device):
             raise _lib.SblHipError("Seq2SeqDecoder.beam_search: log_prior must be a (%d, %d) fp32 tensor on %s" % (V, V, enc.device))
-        if self.training and self.dropout.p > 0:
-            raise _lib.SblHipError("Seq2SeqDecoder: the cached decode has no dropout; call eval() (or recognize_beam(cached=False))")
+        self._require_eval()
         self._fuse()
         with torch.no_grad():
             # the step count is per clip where the reference's maxlen is the clip's frame count

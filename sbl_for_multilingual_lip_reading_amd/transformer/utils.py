@@ -4,6 +4,8 @@ Of these, the encoder uses the two length masks (and only for ragged batches); t
 device.  The rest are kept for code written against the reference."""
 import torch
 
+from ._env import _lib
+
 _PAD_LEN = 16      # pad_list pads to a fixed length (the decoder's 16 steps), not to the longest sequence
 
 
@@ -51,3 +53,18 @@ def get_attn_pad_mask(padded_input, input_lengths, expand_length):
     """Bool (N, expand_length, T), True on padded key positions; a view expanded over the query length."""
     padded = ~_valid_positions(padded_input, input_lengths)
     return padded.unsqueeze(1).expand(-1, expand_length, -1)
+
+
+def device_lengths(encoder_input_lengths, encoder_outputs):
+    """The cross-attention key counts of a decode (the `_kv_len` of both decoders): None, or the clips' frame counts as the
+    device int32 (N,) tensor the `_len` kernels read.  A host sequence is copied once; a CUDA int32 tensor is used as it is and
+    never read on the host."""
+    lens = encoder_input_lengths
+    if lens is None:
+        return None
+    if not (isinstance(lens, torch.Tensor) and lens.is_cuda):
+        lens = torch.as_tensor(lens, dtype=torch.int32).to(encoder_outputs.device)
+    if lens.dtype != torch.int32 or lens.shape != (encoder_outputs.size(0),) or not lens.is_contiguous():
+        raise _lib.SblHipError("encoder_input_lengths: a contiguous int32 (%d,) tensor, got %s %s"
+                               % (encoder_outputs.size(0), lens.dtype, tuple(lens.shape)))
+    return lens

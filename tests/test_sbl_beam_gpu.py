@@ -310,3 +310,57 @@ def test_search_graph_replay(precision):
             for k in ref:
                 assert np.array_equal(got[k], ref[k]), k
     assert not np.array_equal(eager[0]["scores"], eager[1]["scores"])
+
+
+def test_sbl_decode_launch_sequences(monkeypatch):
+    """The library calls of recognize_beam, beam_search(W = 2), beam_search_lex(W = 2) and recognize_words(shortlist = 2) on a
+    2-layer SBL decoder, N = 2 clips of T = 3 encoder rows, in order.  Every decode hoists the cross-attention K/V (one GEMM per
+    layer and direction) and then runs one stage per step: the two embeddings, per layer the 11 launches of either direction's
+    layer (QKV GEMM, self-attention, fc GEMM, add + LayerNorm, Q GEMM, cross-attention, fc GEMM, add + LayerNorm, the two FFN
+    GEMMs, add + LayerNorm) and the fusion, then the two gathers of the rows the heads read; a step ends with the two head GEMMs
+    and the two arg-max launches (greedy) or with the search's tail.  recognize_words follows the greedy decode with the
+    shortlist, a second K/V hoist, ONE stage over all 16 prefixes and the scoring tail.  The W slots (K candidates) of a clip
+    share its K/V through the grouped cross-attention.  With encoder_input_lengths every cross-attention, grouped or not,
+    is sbl_attention_seg_len_fwd and nothing else changes."""
+    from sbl_for_multilingual_lip_reading_amd import _lib, ops
+    from sbl_for_multilingual_lip_reading_amd.transformer.decoder import Decoder
+    from sbl_for_multilingual_lip_reading_amd.transformer.lexicon import Lexicon
+    n_layers, N, T, W, steps = 2, 2, 3, 2, 16
+    torch.manual_seed(11)
+    dec = Decoder(0, 1, 58, 512, n_layers, 8, 64, 64, 512, 2048, dropout=0.0).to(DEV).eval()
+    enc = torch.randn(N, T, 512, device=DEV)
+    lex = Lexicon([[5, 9], [7], [9, 5]], device=DEV, vocab=58, sos_id=0, eos_id=1)
+    assert lex.max_len == 2
+    lex.pair_trie()
+    names = []
+    monkeypatch.setattr(ops, "call", lambda name, *a: names.append(name) or _lib.call(name, *a))
+    gemm, ln, seg = "sbl_gemm_f32", "sbl_add_layernorm_fwd", "sbl_attention_seg_fwd"
+    grouped, seg_len = "sbl_attention_seg_grouped_fwd", "sbl_attention_seg_len_fwd"
+
+    def stage(cross):
+        layer = [gemm, seg, gemm, ln, gemm, cross, gemm, ln, gemm, gemm, ln]
+        return 2 * ["sbl_embed_pe_seg_fwd"] + n_layers * (2 * layer + ["sbl_fusion_seg_fwd"]) + 2 * ["sbl_gather_last_fwd"]
+
+    hoist = 2 * n_layers * [gemm]
+
+    def expected(cross, cross_w):
+        """cross: the cross-attention entry of one sequence per clip, cross_w: that of several slots per clip."""
+        greedy = hoist + steps * (stage(cross) + 2 * [gemm] + 2 * ["sbl_argmax_select"])
+        return dict(
+            greedy=greedy,
+            beam=hoist + steps * (stage(cross_w) + ["sbl_pair_beam_tail"]),
+            beam_lex=hoist + (lex.max_len + 1) * (stage(cross_w) + ["sbl_pair_beam_tail_lex"]),
+            words=greedy + ["sbl_lexicon_shortlist"] + hoist + stage(cross_w) + ["sbl_pair_score_tail"])
+
+    lengths = torch.tensor([3, 1], dtype=torch.int32, device=DEV)
+    for lens, want in ((None, expected(seg, grouped)), (lengths, expected(seg_len, seg_len))):
+        runs = dict(
+            greedy=lambda: dec.recognize_beam(enc, encoder_input_lengths=lens),
+            beam=lambda: dec.beam_search(enc, W, encoder_input_lengths=lens),
+            beam_lex=lambda: dec.beam_search_lex(enc, lex, W, encoder_input_lengths=lens),
+            words=lambda: dec.recognize_words(enc, lex, shortlist=2, encoder_input_lengths=lens))
+        for key, run in runs.items():
+            del names[:]
+            run()
+            assert names == want[key], (key, lens is not None)
+    torch.cuda.synchronize()
