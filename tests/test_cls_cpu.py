@@ -100,6 +100,58 @@ def test_head_entry_points_reject_bad_arguments_on_the_host():
             call(3, None)
 
 
+def test_head_entry_points_reject_documented_limits_on_the_host():
+    """The rejections include/sbl_hip.h documents beyond N, lang_index and D: the class counts (C2 <= 16), T, accumulate, the
+    16-byte alignment of the operands read or written as vectors, and the inputs each requested gradient needs."""
+    from sbl_for_multilingual_lip_reading_amd import _lib
+    p = _ptr()
+
+    def fwd(T=31, C1=1500, C2=2, li=0, **ptr):
+        a = {k: ptr.get(k, p) for k in ("enc", "w1", "b1", "w2", "b2", "pooled", "pooled_t", "l1", "l2")}
+        return _lib.call("sbl_cls_head_fwd", *a.values(), 4, T, 512, C1, C2, li, None)
+
+    def bwd(T=31, C1=1500, C2=2, li=0, acc=1, **ptr):
+        a = {k: ptr.get(k, p) for k in ("enc", "pooled", "d1", "d2", "w1", "w2", "d_enc", "dw1", "db1", "dw2", "db2")}
+        return _lib.call("sbl_cls_head_bwd", *a.values(), 4, T, 512, C1, C2, li, acc, None)
+
+    for call in (fwd, bwd):
+        with pytest.raises(_lib.SblHipError, match=r"C1 = 1500, C2 = 17 classes \(need C1 >= 1, 1 <= C2 <= 16\)"):
+            call(C2=17)
+        with pytest.raises(_lib.SblHipError, match="C1 = 1500, C2 = 0 classes"):
+            call(C2=0)
+        with pytest.raises(_lib.SblHipError, match="C1 = 0, C2 = 2 classes"):
+            call(C1=0)
+        with pytest.raises(_lib.SblHipError, match="T = 0 frames"):
+            call(T=0)
+    for name in ("enc", "w1", "pooled"):
+        with pytest.raises(_lib.SblHipError, match="sbl_cls_head_fwd: enc, w1, w2 and pooled must be 16-byte aligned"):
+            fwd(**{name: p + 4})
+    for name in ("enc", "w1", "pooled", "dw1"):
+        with pytest.raises(_lib.SblHipError, match="sbl_cls_head_bwd: enc, pooled, w1, dw1 and dw2 must be 16-byte aligned"):
+            bwd(**{name: p + 8})
+    with pytest.raises(_lib.SblHipError, match=r"accumulate = 2 \(0 or 1\)"):
+        bwd(acc=2)
+    with pytest.raises(_lib.SblHipError, match=r"null pointer \(pooled, needed for dW1 / db1\)"):
+        bwd(pooled=None, db1=None, dw2=None, db2=None, d_enc=None)            # dw1 alone asks for it
+    with pytest.raises(_lib.SblHipError, match=r"null pointer \(enc, needed for dW2 / db2\)"):
+        bwd(enc=None, dw1=None, db1=None, db2=None, d_enc=None)
+    with pytest.raises(_lib.SblHipError, match=r"null pointer \(w1 / w2, needed for d_enc\)"):
+        bwd(w1=None, dw1=None, db1=None, dw2=None, db2=None)
+    # nothing asked for: nothing launched, nothing needed but the two gradients' addresses
+    none = dict(d_enc=None, dw1=None, db1=None, dw2=None, db2=None)
+    assert bwd(**none) is None
+    assert bwd(enc=None, pooled=None, w1=None, w2=None, acc=0, **none) is None
+    with pytest.raises(_lib.SblHipError, match=r"null pointer \(dlogits1 / dlogits2\)"):
+        bwd(d1=None, **none)
+    loss_fwd = lambda C1, C2: _lib.call("sbl_cls_loss_fwd", *([p] * 4), 3, C1, C2, 0.1, -100, p, p, None)
+    loss_bwd = lambda C1, C2: _lib.call("sbl_cls_loss_bwd", *([p] * 8), 3, C1, C2, 0.1, -100, None)
+    for call in (loss_fwd, loss_bwd):
+        with pytest.raises(_lib.SblHipError, match=r"C1 = 0, C2 = 2 classes \(must be >= 1\)"):
+            call(0, 2)
+        with pytest.raises(_lib.SblHipError, match="C1 = 9, C2 = 0 classes"):
+            call(9, 0)
+
+
 def test_autograd_functions_refuse_cpu_tensors():
     from sbl_for_multilingual_lip_reading_amd import _lib, ops
     enc = torch.zeros(2, 3, 512)
